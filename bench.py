@@ -19,6 +19,13 @@ them with the single plan on rank 0 (`preflight`).  The one-Teddy-pair-per-GPU r
 labelled extra (`replicas`), never `value`.  At N = 1 the same configs[3] figure is the `scale` object.
 
 One JSON line is printed by rank 0.
+
+A plain run does only what the headline figure needs: set-up, --warmup iterations, the --steps
+timed iterations, the outputs of the last one (--dump-outputs DIR) and the line.  Everything else
+the line can carry -- the CPU baselines and the comparisons with the oracle / the reference's
+libraries, the index-order extra, the drop-in boundary calls, the QPBO and segmentation legs, the
+3000 x 2000 x 256 `scale` object at N = 1, and at N > 1 the preflight, rank 0's single-GPU run and
+the gateway leg -- runs only with --full.
 """
 import argparse
 import json
@@ -99,12 +106,24 @@ def algorithmic_bytes_per_sweep_pair(info_deg, K):
     return float(fwd.sum() + bwd.sum())
 
 
-def scale_leg(args, rank, local_rank, world, dist, dev, index_order=False, minplus=False, steps=None, warmup=None):
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: the arrays the timed path handed its caller after the last timed step, one
+    DIR/<name>.npy each (float32 or float64)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def scale_leg(args, rank, local_rank, world, dist, dev, index_order=False, minplus=False, steps=None, warmup=None,
+              outputs=None):
     """Strong scaling of ONE large image (BASELINE.json configs[3]: synthetic 3000 x 2000 x 256-label
     volume) over the `world` GPUs: rank g owns band g of the rows (stereo_amd.strips), boundary
     messages / flags / labels go to the neighbour GPU as peer stores over xGMI, energy and bound are
     reduced as two doubles per iteration.  At world == 1 it is the plain single-GPU plan, so the N=1
-    figure of a scaling run is the single-GPU figure.  Returns the `scale` object (rank 0) or None."""
+    figure of a scaling run is the single-GPU figure.  Returns the `scale` object (rank 0) or None.
+    outputs (a dict): rank 0 receives the image's labels (float32, node order), energy and bound."""
     import torch
     from stereo_amd import dist as D
     from stereo_amd.trws import TrwsPlan
@@ -170,6 +189,14 @@ def scale_leg(args, rank, local_rank, world, dist, dev, index_order=False, minpl
         crc = int(D.sum_over_ranks(dist, float(np.asarray(lab, dtype=np.int64).sum()), dev))
         energy, lb = solver.energy, solver.lb
         own_nodes = len(idx)
+        if outputs is not None:
+            parts = [None] * world
+            dist.all_gather_object(parts, (idx, np.asarray(lab, dtype=np.float32)))
+            lab = np.zeros(N, np.float32)
+            for i, l in parts:
+                lab[i] = l
+    if outputs is not None and rank == 0:
+        outputs.update(labels=np.asarray(lab, dtype=np.float32), energy=np.array([energy]), lower_bound=np.array([lb]))
     # algorithmic bytes of one sweep launch on THIS rank: 13 K R per interior node; the
     # per-node figure with the real degrees is within 0.1 % of it at this size
     bytes_launch = 13.0 * K * 8.0 * own_nodes
@@ -506,11 +533,16 @@ def main():
     ap.add_argument("--scale-steps", type=int, default=3)
     ap.add_argument("--scale-warmup", type=int, default=1)
     ap.add_argument("--scale-options", action="store_true",
-                    help="N > 1: also time the labelled min-plus / index-order options of the scale leg (at N = 1 they always run)")
+                    help="N > 1: also time the labelled min-plus / index-order options of the scale leg (at N = 1 they run with --full)")
     ap.add_argument("--no-scale-n1", action="store_true",
                     help="N > 1: skip rank 0's own single-GPU run of the same image, same --steps / --warmup, after the strips "
                          "(the curve's first point measured in the same job, and a label / energy cross-check of the strips)")
     ap.add_argument("--no-preflight", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline figure (baselines, reference comparisons, extras, the other "
+                         "legs and sizes); the --no-* options above pick among those")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned after its last step as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gateway_leg > 0:
         print(json.dumps(gateway_leg(args.gateway_leg)))
@@ -549,7 +581,7 @@ def main():
         ranks_seen = [None] * world
         dist.all_gather_object(ranks_seen, me)
     pre = None
-    if world > 1 and not args.no_preflight:
+    if world > 1 and args.full and not args.no_preflight:
         pre = preflight(rank, world, dist, dev, one_gpu)
     big = N * K > (1 << 28)
     volume = args.volume if not big else "noise"
@@ -603,13 +635,17 @@ def main():
     rate, dt = D.throughput(dist, args.steps, dt, dev)
     sweep_ms, sweep_launches = plan.stats()
     serial_msgs = plan.serial_messages()
-    _, energy, lb, iters = plan.result(want_labels=False)
+    dump = args.dump_outputs is not None and world == 1   # (at N > 1 the timed path is the scale leg's)
+    labels, energy, lb, iters = plan.result(want_labels=dump)
+    if dump and rank == 0:
+        dump_outputs(args.dump_outputs, {"labels": labels, "energy": np.array([energy]), "lower_bound": np.array([lb]),
+                                         "iterations": np.array([iters], dtype=np.float64)})
     # labelled extra, never `value`: the same volume with the nodes visited in index order
     # (STEREO_TRWS_ORDER_INDEX: MRFEnergy without SetAutomaticOrdering; H + W - 1 dependency levels,
     # no serial border chain) -- a valid TRW-S schedule whose results are not the gateway's
     from stereo_amd.trws import ORDER_INDEX
     alt_dt = alt_en = alt_lb = float("nan")
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         alt = TrwsPlan(1, K, N, conn.T, message_mode=(0 if args.message_mode == "exact" else 1) | ORDER_INDEX)
         alt.bind_device(d_unary.data_ptr(), d_alpha.data_ptr(), 8.0, d_positions=d_pos.data_ptr())
         alt.iterate(args.warmup, max_relgap=NEVER)
@@ -684,9 +720,9 @@ def main():
                                    + " (one persistent launch per sweep)", "bytes_per_launch": bytes_per_launch,
                          "avg_launch_us": avg_launch_s * 1e6, "launches_per_step": launches_per_iter},
         }
-        if args.no_extras:
+        if args.no_extras or not args.full:
             out.pop("index_order_option")
-        if world == 1 and not args.no_cpu_baseline:  # reported baseline: rank 0 at N=1 only
+        if world == 1 and args.full and not args.no_cpu_baseline:  # reported baseline: rank 0 at N=1 only
             from oracle import pyoracle
             q = np.tile(np.arange(K, dtype=np.float64), (E, 1))
             ci = max(args.cpu_iters, 1)
@@ -719,7 +755,7 @@ def main():
                                "(profiles/r04_fp32_cones.txt: -9 % per iteration at 3000x2000x256, bound moves by 4e-10, and no "
                                "exactness certificate exists in fp32, so every message would take the serial construction); "
                                "one exact f64 path is kept instead of a second inexact one")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # the drop-in call itself: stereo_trws / stereo_rd exactly as trws.m:33 / rd.m:21 hand the
             # arrays over -- HOST K x E q and qprim, K x N unary, labels back -- set-up, transfers and everything included
             try:
@@ -830,18 +866,23 @@ def main():
             except Exception as exc:  # the headline number must not depend on the secondary one
                 out["binary_fusion"] = {"error": str(exc)}
     # second leg: one large image tiled across all ranks (strong scaling); every rank takes part
+    # (at N > 1 it is the headline; at N = 1 a --full extra)
     scale = None
-    if not args.no_scale:
+    if not args.no_scale and (args.full or world > 1):
         del plan, d_unary, d_alpha, d_pos
         torch.cuda.empty_cache()
         try:
             if world > 1:   # the top-level figure at N > 1: exactly --steps timed iterations after --warmup
-                scale = scale_leg(args, rank, local_rank, world, dist, dev, steps=args.steps, warmup=args.warmup)
+                outputs = {} if args.dump_outputs is not None else None
+                scale = scale_leg(args, rank, local_rank, world, dist, dev, steps=args.steps, warmup=args.warmup,
+                                  outputs=outputs)
+                if outputs:
+                    dump_outputs(args.dump_outputs, outputs)
             else:
                 scale = scale_leg(args, rank, local_rank, world, dist, dev)
         except Exception as exc:  # the headline line must not depend on the scaling leg
             scale = {"error": "%s: %s" % (type(exc).__name__, exc), "n_gpus": world}
-        if world > 1 and not args.no_scale_n1:
+        if world > 1 and args.full and not args.no_scale_n1:
             # the curve's first point in the same job: rank 0 alone, the plain single-GPU plan on the same image
             n1 = None
             if rank == 0:
@@ -908,7 +949,7 @@ def main():
                 "scaling": "strong", "data": "synthetic",
                 "config": {"workload": sc.get("workload", "configs[3]"), "nodes": Hs * Ws, "directed_edges": 4 * Hs * Ws - 2 * (Hs + Ws),
                            "message_mode": "exact (reference envelope)", "parallelism": "%d row strips, one per GPU" % world},
-                "preflight_ok": bool(pre and pre.get("ok")),
+                "preflight_ok": bool(pre and pre.get("ok")) if args.full else None,
             })
             if good:
                 fr = sc["hbm_frac_per_gpu"]
@@ -920,7 +961,7 @@ def main():
                                    "avg_launch_us": sc.get("sweep_launch_ms_rank0", 0.0) * 1e3, "launches_per_step": 2.0}
             else:
                 out["scale_error"] = sc.get("error", "scale leg skipped (--no-scale)")
-        if world > 1 and not args.no_gateway_leg:
+        if world > 1 and args.full and not args.no_gateway_leg:
             # the gateway sharding by itself over the node's devices: a process of its own (the ranks' work is done; whatever
             # happens there -- this path has only ever run on logical strips of one device -- the line above stands)
             import subprocess

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from helpers import fusion_problem, glass_problem
+from ref_calls import RefCalls
 from make_golden_rd import RD_RUNS, make_problem
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -40,25 +41,25 @@ def test_golden_rd_runs(run, oracle):
 
 
 def test_against_live_reference(oracle):
-    if not oracle.have_ref_qpbo():
-        pytest.skip("oracle/_ref/libref_qpbo.so not built (needs /root/reference)")
+    ref = RefCalls(oracle, "qpbo_live", oracle.have_ref_qpbo())
     probs = [fusion_problem(s, 12, 14, kernel=1 + s % 2, tol=8.0, nonsub_boost=3.0 * (s % 3)) for s in range(8)]
     probs += [fusion_problem(20 + s, 20, 25, integer=True) for s in range(3)]
     probs += [glass_problem(s, 8, 9, 3.0, s % 2 == 0) for s in range(8)]
     for k, p in enumerate(probs):
         a = _args(p)
-        rs, os_ = oracle.ref_rd(*a, stage=1), oracle.rd(*a, stage=1)
+        rs, os_ = ref.ref_rd(*a, stage=1), oracle.rd(*a, stage=1)
         assert np.array_equal(rs[0], os_[0]), k                   # strong persistency: flow invariant
-        rw, ow = oracle.ref_rd(*a), oracle.rd(*a)
+        rw, ow = ref.ref_rd(*a), oracle.rd(*a)
         det = rs[0] >= 0
         assert np.array_equal(rw[0][det], ow[0][det]), k
         assert np.all(ow[0][rw[0] < 0] < 0), k
         assert _rel(rw[2], ow[2]) < 1e-9, k
         if np.array_equal(rw[0], ow[0]):
             assert rw[3] == ow[3] and _rel(rw[1], ow[1]) < 1e-9, k
-        ri, oi = oracle.ref_rd(*a, improve=True, seed=k), oracle.rd(*a, improve=True, seed=k)
+        ri, oi = ref.ref_rd(*a, improve=True, seed=k), oracle.rd(*a, improve=True, seed=k)
         assert np.array_equal(ri[0], oi[0]), k
         assert _rel(ri[1], oi[1]) < 1e-9, k
+    ref.finish()
 
 
 def test_energy_is_the_model_energy_and_bounds_hold(oracle):
@@ -117,8 +118,7 @@ def test_tie_labels_of_the_reference_depend_on_its_own_edge_order(oracle):
           max-flow) gives the reference's labels at EVERY pixel, Improve included.
     The -m gpu half (tests/test_globalstereo_gpu.py) shows (3) for the HIP path and that on the
     unrounded inputs its differences from the reference lie in the same near-tie set."""
-    if not oracle.have_ref_qpbo():
-        pytest.skip("oracle/_ref/libref_qpbo.so not built (needs /root/reference)")
+    ref = RefCalls(oracle, "qpbo_near_ties", oracle.have_ref_qpbo())
     from example_inputs import TeddyGlobal
     from helpers import piecewise_planar
     T = TeddyGlobal(seed=5)
@@ -131,26 +131,27 @@ def test_tie_labels_of_the_reference_depend_on_its_own_edge_order(oracle):
         prop = piecewise_planar(T.H, T.W, cell, rng, d_lo, d_hi)
         U0, U1, E = T.move_terms(prop)
         ne = T.conn.shape[0]
-        base = oracle.ref_rd(U0, U1, *E, T.conn, stage=1)[0]
+        base = ref.ref_rd(U0, U1, *E, T.conn, stage=1)[0]
         near = np.abs(U0 - U1) <= NEAR_TIE
         assert (U0 == U1).sum() > 0.15 * T.N                       # the exact ties this is about
         U0g, U1g, Eg = grid(U0), grid(U1), [grid(x) for x in E]
-        base_g = oracle.ref_rd(U0g, U1g, *Eg, T.conn, stage=1)[0]
+        base_g = ref.ref_rd(U0g, U1g, *Eg, T.conn, stage=1)[0]
         F = np.zeros(T.N, bool)
         for name, pr in _reformulations(ne):
-            r = oracle.ref_rd(U0, U1, *[x[pr].copy() for x in E], T.conn[pr].copy(), stage=1)[0]
+            r = ref.ref_rd(U0, U1, *[x[pr].copy() for x in E], T.conn[pr].copy(), stage=1)[0]
             d = r != base
             assert not (d & ~near).any(), "move %d, %s: the reference's labels moved outside the near ties" % (k, name)
             F |= d
-            rg = oracle.ref_rd(U0g, U1g, *[x[pr].copy() for x in Eg], T.conn[pr].copy(), stage=1)[0]
+            rg = ref.ref_rd(U0g, U1g, *[x[pr].copy() for x in Eg], T.conn[pr].copy(), stage=1)[0]
             assert np.array_equal(rg, base_g), "move %d, %s: order dependence on the exact grid" % (k, name)   # (2)
         flipped_total += int(F.sum())
         if k > 0:
             assert F.any(), "move %d: no pixel of the reference depends on its edge order" % k                # (1)
         # (3) restatement == reference on the grid, strong labels and the full gateway behaviour with Improve
         assert np.array_equal(oracle.rd(U0g, U1g, *Eg, T.conn, stage=1)[0], base_g)
-        rf = oracle.ref_rd(U0g, U1g, *Eg, T.conn, improve=True, seed=1000 + k)
+        rf = ref.ref_rd(U0g, U1g, *Eg, T.conn, improve=True, seed=1000 + k)
         of = oracle.rd(U0g, U1g, *Eg, T.conn, improve=True, seed=1000 + k)
         assert np.array_equal(rf[0], of[0]) and rf[3] == of[3] and _rel(rf[1], of[1]) < 1e-12
-        T.accept(prop, oracle.ref_rd(U0, U1, *E, T.conn, improve=True, seed=1000 + k)[0])
+        T.accept(prop, ref.ref_rd(U0, U1, *E, T.conn, improve=True, seed=1000 + k)[0])
     assert flipped_total >= 40, flipped_total
+    ref.finish()

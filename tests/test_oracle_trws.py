@@ -13,6 +13,7 @@ import pytest
 
 from helpers import grid_conn, trws_problem
 from make_golden import RUNS  # tests/golden on sys.path via conftest
+from ref_calls import RefCalls
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -114,9 +115,8 @@ def test_golden_runs(run, oracle):
 
 
 def test_against_live_reference_types(oracle):
-    """Where oracle/_ref exists: fresh random messages through the reference classes."""
-    if not oracle.have_ref_types():
-        pytest.skip("oracle/_ref/libref_trws_types.so not built (needs /root/reference)")
+    """Fresh random messages through the reference classes (oracle/_ref where built, else their recorded answers)."""
+    ref = RefCalls(oracle, "trws_types_live", oracle.have_ref_types())
     rng = np.random.default_rng(7)
     for trial in range(1500):
         K = int(rng.integers(2, 66))
@@ -133,14 +133,19 @@ def test_against_live_reference_types(oracle):
         args = (kernel, Di, 0.25, msg, q, qp, float(rng.choice([0.0, 1.0, 2.5, 18.0])),
                 float(rng.choice([8.0, 0.5, 64.0])), int(rng.integers(0, 2)), int(rng.integers(0, 2)))
         a, va = oracle.update_message(*args, impl="envelope")
-        b, vb = oracle.update_message(*args, impl="ref")
+        b, vb = ref.update_message(*args, impl="ref")
         assert np.array_equal(a, b) and va == vb, trial
     # Vector::ComputeMin: first minimum wins
     v = np.array([3.0, 1.0, 1.0, 2.0])
     import ctypes as C
-    km = C.c_int()
-    r = oracle.ref_types().ref_vec_min(C.c_int(4), v.ctypes.data_as(C.POINTER(C.c_double)), C.byref(km))
-    assert (r, km.value) == (1.0, 1)
+
+    def vec_min(v):
+        km = C.c_int()
+        r = oracle.ref_types().ref_vec_min(C.c_int(4), v.ctypes.data_as(C.POINTER(C.c_double)), C.byref(km))
+        return r, km.value
+    r, km = ref.call(vec_min, v)
+    assert (r, km) == (1.0, 1)
+    ref.finish()
 
 
 def test_unsupported_kernel_and_modes(oracle):
@@ -155,8 +160,7 @@ def test_unsupported_kernel_and_modes(oracle):
 def test_restated_envelope_equals_reference_classes_on_adversarial_messages(oracle):
     """tests/adversarial.py (near-tangent cones, ramps, vTrunc ties, near-duplicate positions): the
     oracle's envelope restatement against the reference's own type classes, bit for bit."""
-    if not oracle.have_ref_types():
-        pytest.skip("oracle/_ref/libref_trws_types.so not present")
+    ref = RefCalls(oracle, "trws_types_adversarial", oracle.have_ref_types())
     import adversarial
     n = 0
     for seed in range(16):
@@ -167,7 +171,8 @@ def test_restated_envelope_equals_reference_classes_on_adversarial_messages(orac
             args = (kernel, b["Di"][m], float(b["gamma"][m]), b["msg"][m], b["qd"][m], b["qs"][m],
                     float(b["alpha"][m]), b["lam"], 0, 0)
             a, va = oracle.update_message(*args, impl="envelope")
-            r, vr = oracle.update_message(*args, impl="ref")
+            r, vr = ref.update_message(*args, impl="ref")
             assert np.array_equal(a, r) and va == vr, (seed, m)
             n += 1
     assert n == 2400
+    ref.finish()

@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+from ref_calls import RefCalls
 from stereo_amd import segment as S
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -99,19 +100,19 @@ def _random_images():
 
 
 def test_host_stages_against_the_reference_segmenters_live(oracle):
-    if not oracle.have_ref_segment() or oracle.ref_segment_gb_lib() is None:
-        pytest.skip("oracle/_ref not built")
+    ref = RefCalls(oracle, "segment_live", oracle.have_ref_segment() and oracle.ref_segment_gb_lib() is not None)
     for name, im in _random_images():
         H, W, _ = im.shape
         for h_s, h_r, mn in ((1, 1.5, 0), (2, 6.5, 4), (4, 5.0, 0), (3, 20.0, 10)):
             if name == "one colour" and mn > 0:
                 continue        # (one region and a minimum size: the reference reads a null adjacency list)
             seg = ms_through_the_host_stages(oracle, im, h_s, h_r, mn)[0]
-            assert np.array_equal(seg, oracle.ref_segment_ms(im, h_s, h_r, mn)), (name, h_s, h_r, mn)
+            assert np.array_equal(seg, ref.ref_segment_ms(im, h_s, h_r, mn)), (name, h_s, h_r, mn)
         w = gb_weights_numpy(im)
         for k, mn, compress in ((50.0, 2, 1), (300.0, 10, 1), (120.0, 0, 0)):
             seg = S.gb_regions(w, H, W, k, mn, compress=compress)
-            assert np.array_equal(seg, oracle.ref_segment_gb(im, 0, k, mn, compress)), (name, k, mn, compress)
+            assert np.array_equal(seg, ref.ref_segment_gb(im, 0, k, mn, compress)), (name, k, mn, compress)
+    ref.finish()
 
 
 def test_argument_checks_follow_the_gateways():

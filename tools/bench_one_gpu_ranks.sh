@@ -6,11 +6,11 @@ out=${1:-gpurun_out/one_gpu_ranks}; H=${2:-400}; W=${3:-600}
 mkdir -p $out
 for n in 2 4; do
   STEREO_BENCH_ONE_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-    --master-port 29533 bench.py --gpus $n --steps 3 --warmup 1 --no-cpu-baseline --scale-height $H --scale-width $W \
+    --master-port 29533 bench.py --full --gpus $n --steps 3 --warmup 1 --no-cpu-baseline --scale-height $H --scale-width $W \
     > $out/bench_n$n.json 2> $out/bench_n$n.err
   echo "n=$n rc=$?"; tail -3 $out/bench_n$n.err
 done
-python bench.py --no-cpu-baseline --steps 3 --warmup 1 --scale-height $H --scale-width $W > $out/bench_n1.json 2> $out/bench_n1.err
+python bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --scale-height $H --scale-width $W > $out/bench_n1.json 2> $out/bench_n1.err
 python - <<EOF2
 import json
 for n in (1, 2, 4):

@@ -15,7 +15,7 @@ export PYTHONUNBUFFERED=1
   timeout 400 python tools/stress_segpln.py 120 515 2>&1 | tail -2
   timeout 400 python tools/stress_terms.py 120 516 2>&1 | tail -2
 } > $out/${r}_stress.txt 2>&1
-timeout 1500 python bench.py > $out/${r}_bench_default.json 2> $out/${r}_bench_default.err
+timeout 1500 python bench.py --full > $out/${r}_bench_default.json 2> $out/${r}_bench_default.err
 bash tools/profile_bench.sh ${r}_trws_teddy60 --steps 20 --warmup 3 > $out/${r}_profile_teddy.txt 2>&1
 bash tools/profile_bench.sh ${r}_trws_wide256_3000x2000 --height 2000 --width 3000 --labels 256 --steps 3 --warmup 1 > $out/${r}_profile_wide.txt 2>&1
 tail -6 $out/${r}_gputests.txt; cat $out/${r}_stress.txt; tail -c 1500 $out/${r}_bench_default.json
