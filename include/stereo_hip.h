@@ -26,8 +26,9 @@ extern "C" {
  * library that reports another version (a stale libstereo_hip.so).  3: stereo_hip_device_cus, plan
  * entry points select their plan's device, wall-clock bound on cross-workgroup waits.  4: stereo_fusion_fit_planes,
  * stereo_fusion_fuse_until_convergence.  5: stereo_segpln_wta, stereo_segpln_planes.  6: stereo_segment_* (the segmenters
- * behind dispmap_globalstereo), stereo_trws_plan_debug_terms / _messages, stereo_segpln_planes_batch. */
-#define STEREO_HIP_ABI_VERSION 6
+ * behind dispmap_globalstereo), stereo_trws_plan_debug_terms / _messages, stereo_segpln_planes_batch.  7: TRW-S takes
+ * up to 4096 labels with one shared strictly ascending positions vector (stereo_trws_plan_path 5). */
+#define STEREO_HIP_ABI_VERSION 7
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -62,6 +63,8 @@ const char *stereo_hip_last_error(void);
  *             2 = truncated quadratic (TypeStereoQuadratic); anything else fails
  *             with "Unsupported kernel" (trws_mex.cpp:162).
  * unary       K x N   q, qprim  K x E   alphas  E   tol = lambda (trws_mex.cpp:37)
+ * K           1 .. 512 with any q / qprim; 513 .. 4096 when every column of q and qprim is one and
+ *             the same finite, strictly ascending vector; anything else fails with "K must be in ...".
  * maxiter, max_relgap: the two fields of the options struct (trws_mex.cpp:40-41;
  *             defaults 1000 and 0 are applied by the caller / gateway).
  * labelling   N doubles, ONE based (trws_mex.cpp:137).
@@ -104,6 +107,8 @@ typedef struct stereo_trws_plan stereo_trws_plan;
  * TRW-S schedule whose labels / energies are NOT the gateway's.  Explicit opt-in only. */
 #define STEREO_TRWS_ORDER_INDEX 0x100
 
+/* K in [1, 4096]; above 512 the plan takes only a shared positions vector that is finite and strictly
+ * ascending (upload / bind_device fail with "K must be in ..." otherwise). */
 int stereo_trws_plan_create(int kernel, int K, int64_t N, int64_t E, const uint32_t *conn,
                             int message_mode, stereo_trws_plan **plan, char *err,
                             size_t errcap);
@@ -182,7 +187,8 @@ int stereo_trws_messages(int kernel, int K, int64_t M, const double *Di, const d
 /* Diagnostics: which sweep implementation the plan's current inputs select.
  * 1 generic persistent kernel, 2 pipelined kernel (K <= 64),
  * 3 wide pipelined kernel (64 < K <= 256, shared strictly ascending positions),
- * 4 two-labels-per-lane pipelined kernel (64 < K <= 128, linear kernel, any positions).
+ * 4 two-labels-per-lane pipelined kernel (64 < K <= 128, linear kernel, any positions),
+ * 5 large-label kernel (512 < K <= 4096, shared strictly ascending positions, any graph, both modes).
  * All give identical results.  Negative on a NULL plan. */
 int stereo_trws_plan_path(stereo_trws_plan *plan);
 

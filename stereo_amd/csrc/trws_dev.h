@@ -48,6 +48,7 @@ struct DevParams {
   unsigned long long *prof;       // optional: 8 phase-cycle accumulators (development)
   const int32_t *desc[2];         // packed node descriptors of the pipelined kernels
   int prof_run;
+  double *large_scratch;  // trws_large_kernel: per workgroup 3 (Kp + 2) doubles, the serial construction's stack
   int debug;  // development switches: 2 / 4 profile backward / forward sweeps only, 256 no windowed paths,
               // 512 serial envelopes by the lane-read loop instead of the mask construction, 2048 by the
               // bit-set walk instead of the closed form (build_envelope_parallel)
@@ -98,6 +99,8 @@ constexpr int kWave = 64;
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kWaveVecs = 5;  // K-vectors of LDS scratch per wave
+constexpr int kGenericMaxK = 8 * kWave;  // trws_generic.hip: eight labels per lane
+constexpr int kLargeMaxK = 4096;         // trws_large.hip (shared strictly ascending positions)
 
 // ---- hand-over accesses (sc0 sc1): data handed between workgroups inside one launch never sits
 // in a per-CU L1 or a non-coherent L2 (cdna_hip_programming.md G16, R1/R2).  System scope, not

@@ -14,6 +14,11 @@ size_t generic_lds_bytes(int Kp);
 void generic_set_attributes(int lds);
 void launch_generic(int kernel, int mode, int what, int blocks, size_t lds, hipStream_t s, const DevParams &p, int epoch);
 
+size_t large_lds_bytes(int Kp);
+size_t large_scratch_doubles(int Kp);
+void large_set_attributes(int lds);
+void launch_large(int kernel, int mode, int what, int blocks, size_t lds, hipStream_t s, const DevParams &p, int epoch);
+
 size_t pipe_lds_bytes();
 int pipe_threads();
 void pipe_set_attributes();

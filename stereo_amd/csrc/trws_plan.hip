@@ -18,6 +18,7 @@
 //   trws_pipe2.hip    64 < K <= 128, two labels per lane, linear kernel, per-edge positions
 //   trws_wide.hip     64 < K <= 256, shared strictly ascending positions, linear kernel
 //   trws_generic.hip  everything else (any graph, K <= 512, min-plus message mode)
+//   trws_large.hip    512 < K <= 4096, shared strictly ascending positions (any graph, both modes)
 // The three descriptor-driven families walk the chain schedule of trws_graph.h; messages take a
 // certified min-plus fast path and fall back to the reference's serial envelope
 // construction when the certificate fails.  This file: plan object, host logic, C ABI.
@@ -173,6 +174,8 @@ struct stereo_trws_plan {
   bool wide = false;  // 64 < K <= 256 with shared strictly ascending positions: trws_wide_kernel
   bool fast2 = false; // 64 < K <= 128, any positions, both smoothness kernels: trws_pipe2_kernel (when not wide)
   bool wide_allowed = false;
+  bool large = false;  // 512 < K <= 4096 (shared strictly ascending positions only): trws_large_kernel
+  DevBuf<double> d_large_scr;  // its serial construction's stack, one slab per workgroup
   bool pos_ascending = false;  // shared positions finite and strictly ascending
   double pos_first = 0, pos_last = 0, pos_gap = 0;
   int window = 0;
@@ -247,7 +250,9 @@ struct stereo_trws_plan {
 
 namespace {
 
-size_t persistent_lds_bytes(int Kp) { return generic_lds_bytes(Kp); }
+size_t persistent_lds_bytes(int K, int Kp) { return K > kGenericMaxK ? large_lds_bytes(Kp) : generic_lds_bytes(Kp); }
+
+const char *const kKRange = "stereo_trws: K must be in [1, 512] (up to 4096 with one strictly ascending positions vector shared by every edge)";
 
 // The speculative schedule runs where its runner's arithmetic is what message_regs returns under a passed certificate:
 // trws_pipe_kernel, linear kernel, certified messages, shared strictly ascending positions, uniformly spaced over the
@@ -302,6 +307,7 @@ DevParams make_params(stereo_trws_plan *P, bool allow_spec = true) {
   p.timeline = P->d_timeline.p;
   p.desc[0] = P->d_desc[0].p; p.desc[1] = P->d_desc[1].p;
   p.prof_run = -1;
+  p.large_scratch = P->d_large_scr.p;
   p.window = P->window;
   p.uniform_step = P->uniform_step;
   p.pos_first = P->pos_first; p.pos_last = P->pos_last;
@@ -341,7 +347,8 @@ void launch_persistent(stereo_trws_plan *P, const DevParams &p, int what, hipStr
     if (be && std::atoi(be) > 0) blocks = std::min(blocks, std::atoi(be));
     launch_pipe(P->kernel, P->pos != nullptr, what, blocks, s, p, epoch);
   }
-  else launch_generic(P->kernel, P->mode, what, P->grid_blocks, persistent_lds_bytes(P->Kp), s, p, epoch);
+  else if (P->large) launch_large(P->kernel, P->mode, what, P->grid_blocks, persistent_lds_bytes(P->K, P->Kp), s, p, epoch);
+  else launch_generic(P->kernel, P->mode, what, P->grid_blocks, persistent_lds_bytes(P->K, P->Kp), s, p, epoch);
   if (what != 3) P->sweep_launches += 1;
 }
 
@@ -448,6 +455,21 @@ void finish_inputs(stereo_trws_plan *P) {
   // already with the OLD inputs (persistent_iteration fuses it with the primal pass), so the
   // messages on the device belong to no state the reference could be in with the new ones.
   if (P->iterations > 0 || P->fwd_pending) reset_state(P);
+  if (P->large) {
+    // more than 512 labels: one shared positions vector, finite and strictly ascending (trws_large_kernel)
+    P->have_inputs = false;
+    bool asc = P->pos != nullptr;
+    if (asc) {
+      std::vector<double> hp(P->K);
+      STEREO_HIP_CHECK(hipMemcpy(hp.data(), P->pos, sizeof(double) * P->K, hipMemcpyDeviceToHost));
+      asc = std::isfinite(hp[0]);
+      for (int k = 1; k < P->K && asc; ++k) asc = std::isfinite(hp[k]) && hp[k] > hp[k - 1];
+      P->pos_first = hp[0]; P->pos_last = hp[P->K - 1];
+      P->pos_gap = std::numeric_limits<double>::infinity();
+      for (int k = 1; k < P->K; ++k) P->pos_gap = std::min(P->pos_gap, hp[k] - hp[k - 1]);
+    }
+    if (!asc) throw HipError{kKRange};
+  }
   if (P->pos) {
     P->d_perm_pos.alloc(P->K);
     run_argsort(P->pos, P->d_perm_pos.p, P->K, 1, nullptr);
@@ -566,7 +588,7 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
   if (nstrips < 1 || strip < 0 || strip >= nstrips) return fail("stereo_trws_plan_create: strip out of range", err, errcap);
   if (nstrips > 1 && !owner && !share) return fail("stereo_trws_plan_create: strips need an owner per node", err, errcap);
   if (kernel != 1 && kernel != 2) return fail("Unsupported kernel", err, errcap);
-  if (K < 1 || K > 8 * kWave) return fail("stereo_trws: K must be in [1, 512]", err, errcap);
+  if (K < 1 || K > kLargeMaxK) return fail(kKRange, err, errcap);
   const int ordering = (message_mode & STEREO_TRWS_ORDER_INDEX) ? 1 : 0;
   message_mode &= ~STEREO_TRWS_ORDER_INDEX;
   if (message_mode != STEREO_TRWS_MESSAGES_EXACT && message_mode != STEREO_TRWS_MESSAGES_MINPLUS)
@@ -589,7 +611,8 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
     }
     // (kernel 1 in either message mode -- MINPLUS runs it lean --, kernel 2 with exact messages)
     const bool wide_candidate = (kernel == 1 || message_mode == STEREO_TRWS_MESSAGES_EXACT) && K > kWave && K <= 256;
-    const int64_t per_cu = std::min<int64_t>(std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)persistent_lds_bytes(P->Kp)), 4);
+    P->large = K > kGenericMaxK;
+    const int64_t per_cu = std::min<int64_t>(std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)persistent_lds_bytes(K, P->Kp)), 4);
     const int64_t capacity = wide_candidate ? P->cus : P->cus * per_cu;
     // The analysis depends on the connectivity only (ordering, lists, schedules: 0.2-0.6 s at Teddy
     // size); consecutive plans for the same image grid -- every trws() call of a fusion loop --
@@ -748,6 +771,7 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
       if (max_blocks > 0) P->grid_blocks = std::min(P->grid_blocks, max_blocks);
     }
     if (fine) P->d_msg.alloc_fine_grained((size_t)P->El * K); else P->d_msg.alloc((size_t)P->El * K);
+    if (P->large) P->d_large_scr.alloc((size_t)P->grid_blocks * large_scratch_doubles(P->Kp));
     P->d_lbterms.alloc(P->n_lb);
     P->d_eterms.alloc(P->n_en);
     if (fine) P->d_x.alloc_fine_grained(P->Nl); else P->d_x.alloc(P->Nl);
@@ -762,9 +786,9 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
     STEREO_HIP_CHECK(hipStreamCreateWithFlags(&P->copy_stream, hipStreamNonBlocking));
     STEREO_HIP_CHECK(hipDeviceSynchronize());
     // every sweep kernel may need more than the default 64 KiB of dynamic LDS
-    const int plds = (int)persistent_lds_bytes(P->Kp);
+    const int plds = (int)persistent_lds_bytes(K, P->Kp);
     if (plds > 160 * 1024) return fail("stereo_trws: K too large for LDS", err, errcap);
-    generic_set_attributes(plds);
+    if (P->large) large_set_attributes(plds); else generic_set_attributes(plds);
     if (P->fast || strip_api) pipe_set_attributes();
     if (P->fast2) pipe2_set_attributes();
     if (P->wide_allowed || strip_api) wide_set_attributes();
@@ -886,6 +910,7 @@ int stereo_trws_plan_upload(stereo_trws_plan *P, const double *unary, const doub
   const bool shared = (q == nullptr && qprim == nullptr);
   if (shared && !positions) return fail("stereo_trws_plan_upload: need q/qprim or positions", err, errcap);
   if (!shared && (!q || !qprim)) return fail("stereo_trws_plan_upload: q and qprim must both be given", err, errcap);
+  if (P->large && !shared) return fail(kKRange, err, errcap);
   try {
     const size_t K = P->K;
     // a strip keeps the rows of its own nodes + halo and of the edges with an own endpoint
@@ -924,6 +949,7 @@ int stereo_trws_plan_bind_device(stereo_trws_plan *P, const double *d_unary, con
   const bool shared = (d_q == nullptr && d_qprim == nullptr);
   if (shared && !d_positions) return fail("stereo_trws_plan_bind_device: need q/qprim or positions", err, errcap);
   if (!shared && (!d_q || !d_qprim)) return fail("stereo_trws_plan_bind_device: q and qprim must both be given", err, errcap);
+  if (P->large && !shared) return fail(kKRange, err, errcap);
   try {
     P->lambda = tol;
     if (P->nstrips > 1) {
@@ -1435,7 +1461,7 @@ int stereo_trws_messages(int kernel, int K, int64_t M, const double *Di, const d
 
 int stereo_trws_plan_path(stereo_trws_plan *P) {
   if (!P) return -1;
-  return P->wide ? 3 : P->fast2 ? 4 : P->fast ? 2 : 1;
+  return P->large ? 5 : P->wide ? 3 : P->fast2 ? 4 : P->fast ? 2 : 1;
 }
 
 }  // extern "C"
@@ -1703,8 +1729,9 @@ int stereo_trws(int kernel, const double *unary, const uint32_t *conn, const dou
     stereo_trws_plan *P = nullptr;
     int rc = stereo_trws_plan_create(kernel, K, N, E, conn, mode, &P, err, errcap);
     if (rc) return rc;
-    rc = trws_solve_on(P, unary, q, qprim, alphas, tol, maxiter, max_relgap, false, labelling, energy, lower_bound, iterations,
-                       err, errcap);
+    // (above 512 labels only the shared positions vector is taken: look for it there)
+    rc = trws_solve_on(P, unary, q, qprim, alphas, tol, maxiter, max_relgap, K > kGenericMaxK, labelling, energy, lower_bound,
+                       iterations, err, errcap);
     stereo_trws_plan_destroy(P);
     return rc;
   }

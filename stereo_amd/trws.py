@@ -172,7 +172,8 @@ class TrwsPlan:
 
     def path(self):
         """1 generic persistent, 2 pipelined (K <= 64), 3 wide pipelined, 4 pipelined with two
-        labels per lane (64 < K <= 128)."""
+        labels per lane (64 < K <= 128), 5 large-label kernel (512 < K <= 4096, shared ascending
+        positions)."""
         return int(_lib.lib().stereo_trws_plan_path(self._h))
 
     def serial_messages(self, reset=False):
