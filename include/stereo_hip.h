@@ -299,6 +299,11 @@ int stereo_trws_spec_schedule(int64_t N, int64_t E, const uint32_t *connectivity
                               int64_t *nruns, int64_t *run_ptr, int64_t *kind, int64_t *ticket_run, char *err,
                               size_t errcap);
 
+/* Host only (no device): the descriptors of the descriptor-driven kernels' chain schedule, N x 64 int32 in schedule
+ * order (stereo_trws_schedule's positions; layout in trws_graph.h).  No reference counterpart. */
+int stereo_trws_descriptors_host(int64_t N, int64_t E, const uint32_t *connectivity0, int direction, int32_t *desc,
+                                 char *err, size_t errcap);
+
 /* stereo_trws_schedule with strips: additionally run_strip (N provided, *nruns used) = strip of
  * every run, remote (N, by rank) = descriptor word 43 (bits 0-7: outgoing message k is written
  * to a neighbour, 8-15: which one, 16 / 17: flag and label also raised at strip - 1 / + 1). */

@@ -80,6 +80,11 @@ struct DevParams {
   double *peer_msg0, *peer_msg1;      // (scalars, not arrays: an index computed at run time would put
   int32_t *peer_done0, *peer_done1;   //  the whole parameter block into scratch memory)
   int32_t *peer_x0, *peer_x1;
+  // Tagged-granule hand-over between ordinary runs (trws_graph.h: kDescGran; trws_pipe.hip), or null: off
+  // (STEREO_HIP_TRWS_GRANULES=0, or a kernel other than trws_pipe_kernel).  Every 8-byte granule is
+  // {32-bit value, tag = the sweep's epoch} (tag in the high word), zeroed wherever `done` is.
+  unsigned long long *gran;   // [E][K][2]: the high and the low half of a message entry
+  unsigned long long *xgran;  // [N]: a node's label (primal sweeps)
 };
 
 // Several strips of one problem in ONE launch (row strips that share a device: logical strips, or
@@ -993,9 +998,10 @@ __device__ __forceinline__ void wait_for_dependencies(const DevParams &p, int nd
 // The same wait with the lane's own dependency already in the lane (`myrank`: lane j < ndep watches
 // dependency j -- the caller takes it from the descriptor word with one ds_bpermute instead of four scalar
 // reads and a chain of selects).
+// (`watch`: bit j -- dependency j is waited for here; trws_pipe.hip leaves out those whose rows come as granules)
 __device__ __forceinline__ void wait_for_dependencies_w(const DevParams &p, int ndep, int myrank, int visiting_rank, int epoch,
-                                                        int lane, int *abort_word) {
-  const bool watching = lane < ndep;
+                                                        int lane, int *abort_word, unsigned watch = ~0u) {
+  const bool watching = lane < ndep && ((watch >> (lane & 31)) & 1u);
   int spins = 0;
   long long t0 = 0;
   for (;;) {

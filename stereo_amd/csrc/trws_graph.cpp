@@ -608,6 +608,48 @@ bool build_trws_graph(int64_t N, int64_t E, const uint32_t *conn, TrwsGraph &g,
           S.spec = std::move(sp);
         }
       }
+      // ---- tagged-granule hand-over (word 57, trws_graph.h): the rows a node fetches from another ordinary run that
+      // drew an earlier ticket come as granules, published by the producer as soon as they are final; everything
+      // else -- the speculative schedule's cut run (its segments hold their flags back until they commit, a granule
+      // must never show an uncommitted row), rows of the same run, strips -- keeps the completion flags.
+      // (serial: a consumer marks its producer's descriptor too)
+      if (!own) {
+        std::vector<int32_t> pos_at(N), ticket_of(RR);
+        for (int64_t p = 0; p < N; ++p) pos_at[S.chain_rank[p]] = (int32_t)p;
+        for (int64_t t = 0; t < RR; ++t) ticket_of[S.chain_run_order.empty() ? t : S.chain_run_order[t]] = (int32_t)t;
+        const int32_t cut = S.spec.ok ? S.spec.run : -1;
+        for (int64_t p = 0; p < N; ++p) {
+          const int32_t r = S.chain_rank[p], kr = run_at[r];
+          if (kr == cut) continue;
+          int32_t *D = &S.desc[(size_t)p * W];
+          const int nd = (D[2] >> 8) & 15;
+          const uint32_t fetch = (uint32_t)D[kDescFetch];
+          uint32_t gm = 0;
+          for (int k = 0; k < 8; ++k) {
+            if (!((fetch >> k) & 1)) continue;
+            const int32_t ko = run_at[g.rank[D[32 + k]]];
+            if (ko != kr && ko != cut && ticket_of[ko] < ticket_of[kr]) gm |= 1u << k;
+          }
+          if (__builtin_popcount(gm) > 4) gm = 0;   // (the kernel sweeps at most four granule rows)
+          if (!gm) continue;
+          // a dependency whose rows all come as granules is no longer waited for by its flag
+          uint32_t flags = 0;
+          for (int q = 0; q < nd; ++q) {
+            bool feeds = false, covered = true;
+            for (int k = 0; k < 8; ++k)
+              if (((fetch >> k) & 1) && g.rank[D[32 + k]] == D[20 + q]) { feeds = true; covered = covered && ((gm >> k) & 1); }
+            if (!(feeds && covered)) flags |= 1u << q;
+          }
+          D[kDescGran] |= (int32_t)(gm | (flags << 16));
+          for (int k = 0; k < 8; ++k) {
+            if (!((gm >> k) & 1)) continue;
+            int32_t *P = &S.desc[(size_t)pos_at[g.rank[D[32 + k]]] * W];
+            const int pout = P[2] & 15;
+            for (int j = 0; j < pout; ++j)
+              if (P[4 + j] == D[4 + k]) P[kDescGran] |= (int32_t)((1u << (8 + j)) | (1u << 20));
+          }
+        }
+      }
     };
 #undef DTICK
     std::thread backward([&] { build_direction(1); });
@@ -794,6 +836,23 @@ extern "C" int stereo_trws_spec_schedule(int64_t N, int64_t E, const uint32_t *c
   for (size_t k = 0; run_ptr && k < sp.run_ptr.size(); ++k) run_ptr[k] = sp.run_ptr[k];
   for (size_t k = 0; kind && k < sp.kind.size(); ++k) kind[k] = sp.kind[k];
   for (size_t k = 0; ticket_run && k < sp.run_order.size(); ++k) ticket_run[k] = sp.run_order[k];
+  return 0;
+}
+
+// Host-only view of the descriptors of the chain schedule (N x kDescWords int32, schedule order), for CPU tests of
+// what the host marks in them (word 57: the granule hand-over).  Same graph as stereo_trws_spec_schedule.
+extern "C" int stereo_trws_descriptors_host(int64_t N, int64_t E, const uint32_t *conn, int direction, int32_t *desc,
+                                            char *err, size_t errcap) {
+  if (!conn || !desc || (direction != 0 && direction != 1)) return stereo::fail("stereo_trws_descriptors_host: bad argument", err, errcap);
+  try {
+    stereo::TrwsGraph g;
+    std::string gerr;
+    if (!stereo::build_trws_graph(N, E, conn, g, gerr)) return stereo::fail(gerr, err, errcap);
+    if (!g.fast_ok) return stereo::fail("stereo_trws_descriptors_host: graph outside the descriptor-driven kernels' range", err, errcap);
+    std::copy(g.sweep[direction].desc.begin(), g.sweep[direction].desc.end(), desc);
+  } catch (const std::exception &e) {
+    return stereo::fail(std::string("stereo_trws_descriptors_host: ") + e.what(), err, errcap);
+  }
   return 0;
 }
 

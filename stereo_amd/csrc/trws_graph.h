@@ -136,6 +136,16 @@ constexpr int kDescPeerEdge = 45, kDescPeerNode = 53;
 constexpr int kDescFetch = 55;
 //   word 56: nibble k: the outgoing message that goes to the same neighbour as outgoing message k (k itself: none)
 constexpr int kDescTwin = 56;
+//   word 57: the tagged-granule hand-over between two ordinary runs (trws_pipe.hip) --
+//            bits 0-7:   incoming row k (a bit of word 55) arrives as granules in slot "edge id of row k" of the
+//                        granule array, not behind the other end's completion flag
+//            bits 8-15:  outgoing message k is published as granules as soon as it is final
+//            bit 20:     the node publishes its label as a granule (primal sweeps; set with any bit 8-15)
+//            bits 16-19: which of the dependencies (words 20-23) are still waited for by their flags, with
+//                        granules on (the others only feed rows of bits 0-7)
+//            Marked only where both ends are ordinary runs of the same sweep (no segment of the speculative
+//            schedule, not its runner, no strips) and the producer's run draws the earlier ticket; 0 elsewhere.
+constexpr int kDescGran = 57;
 
 // Strip-local storage.  A strip keeps arrays only for what it touches: its own nodes, the nodes
 // one edge away (whose flags it waits on and whose labels its primal pass reads), and the edges

@@ -15,6 +15,39 @@ namespace {
 
 #define RLI(v, i) __builtin_amdgcn_readlane((v), (i))
 
+// ---- tagged-granule hand-over (kDescGran, DevParams::gran): a message entry travels as two 8-byte
+// granules {high half, epoch} {low half, epoch}, ONE aligned 16-byte write-through store per lane; the consumer re-reads
+// them until every tag is the sweep's epoch -- the data is the flag, no drain, no flag store, no second round trip.
+// Inline assembly because the loads must be repeated: the compiler takes the buffer-load builtins for loads of
+// unchanging memory and keeps a single one out of the spin loop, and volatile loads wait for each other one by one.
+typedef unsigned int gran4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void publish_granules(unsigned long long *a, double v, int epoch) {
+  const gran4 d = {(unsigned)__double2hiint(v), (unsigned)epoch, (unsigned)__double2loint(v), (unsigned)epoch};
+  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(a), "v"(d) : "memory");
+}
+__device__ __forceinline__ void load_granules2(const unsigned long long *a, const unsigned long long *b, gran4 &x, gran4 &y) {
+  asm volatile("global_load_dwordx4 %0, %2, off sc0 sc1\n\tglobal_load_dwordx4 %1, %3, off sc0 sc1\n\ts_waitcnt vmcnt(0)"
+               : "=&v"(x), "=&v"(y) : "v"(a), "v"(b) : "memory");
+}
+__device__ __forceinline__ void load_granules2x(const unsigned long long *a, const unsigned long long *b, const unsigned long long *c,
+                                                gran4 &x, gran4 &y, unsigned long long &z) {
+  asm volatile("global_load_dwordx4 %0, %3, off sc0 sc1\n\tglobal_load_dwordx4 %1, %4, off sc0 sc1\n\t"
+               "global_load_dwordx2 %2, %5, off sc0 sc1\n\ts_waitcnt vmcnt(0)"
+               : "=&v"(x), "=&v"(y), "=&v"(z) : "v"(a), "v"(b), "v"(c) : "memory");
+}
+__device__ __forceinline__ void load_granule_x(const unsigned long long *c, unsigned long long &z) {
+  asm volatile("global_load_dwordx2 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(z) : "v"(c) : "memory");
+}
+__device__ __forceinline__ bool granules_tagged(gran4 x, unsigned epoch) { return x.y == epoch && x.w == epoch; }
+__device__ __forceinline__ double granules_value(gran4 x) { return __hiloint2double((int)x.x, (int)x.z); }
+// development switch 262144 (tests): a hashed quarter of the nodes publishes a few microseconds late -- consumers
+// find old tags and sweep again; nothing is skipped or changed
+__device__ __forceinline__ void granule_delay(const DevParams &p, int node) {
+  if (!(p.debug & 262144) || (((unsigned)node * 2654435761u) >> 30) != 0) return;
+  const long long t0 = (long long)wall_clock64();
+  while ((long long)wall_clock64() - t0 < 400) __builtin_amdgcn_s_sleep(2);
+}
+
 // ---- pipelined persistent sweep (K <= 64): role-specialised waves ---------------------
 // Same dataflow schedule and arithmetic as trws_persistent_kernel, but the global-memory traffic
 // of a visit is taken off the critical path by dedicated waves of the workgroup:
@@ -192,6 +225,7 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
           const int nout = f & 15, md = (f >> 16) & 255;
           const int myrow = sti[72 + (lane & 7)];  // LDS offsets (doubles) of the node's message rows, from the loader
           const unsigned twins = SHARED ? (unsigned)__builtin_amdgcn_readfirstlane(sti[kDescTwin]) : 0x76543210u;
+          const int gpub = p.gran ? (__builtin_amdgcn_readfirstlane(sti[kDescGran]) >> 8) & 255 : 0;   // messages published as granules
           VSTAMP(0);
           if (wave < nout || (BACKWARD && wave == 0)) {  // waves without a message stay out of the way
           double Di = act ? st[kStD + lane] : 0.0;
@@ -262,6 +296,16 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
                   hcur[partner * kWave + lane] = newm;
                   if (BACKWARD && lane == 0) sc[partner] = v;
                 }
+                // final: to the consumer in another run as granules now, not behind the storer's flag one visit later
+                // (lanes < K only: the granules of a lane beyond K are nobody's)
+                const int gmine = gpub & ((1 << j) | (cp.active() ? 1 << partner : 0));
+                if (gmine) {
+                  granule_delay(p, __builtin_amdgcn_readfirstlane(sti[0]));
+                  if ((gmine >> j) & 1)
+                    if (act) publish_granules(p.gran + 2 * ((size_t)(unsigned)__builtin_amdgcn_readfirstlane(sti[4 + j]) * (unsigned)Kv + lane), newm, epoch);
+                  if ((gmine >> partner) & 1 && partner != j)
+                    if (act) publish_granules(p.gran + 2 * ((size_t)(unsigned)__builtin_amdgcn_readfirstlane(sti[4 + partner]) * (unsigned)Kv + lane), newm, epoch);
+                }
               }
             }
           }
@@ -313,6 +357,9 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
           const int nout = f & 15, ntot = nout + ((f >> 4) & 15);
           int ndep = (f >> 8) & 15;
           int fm = RLI(w, kDescFetch) & 255;   // incoming rows that come from global memory (behind flags)
+          const int gw = p.gran ? RLI(w, kDescGran) : 0;
+          const int gm = gw & 255;             // ... of them those that come as granules instead
+          fm &= ~gm;
           const int j8 = lane & 7;
           int sl = __shfl(w, 12 + j8, kWave);  // lane j: hand-over slot of the node's edge j, label source
           const int xn = __shfl(w, 32 + j8, kWave);
@@ -361,7 +408,8 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
 #ifdef STEREO_HIP_VISIT_PROFILE
           const long long lb0 = (long long)__builtin_readcyclecounter();
 #endif
-          if (ndep > 0) wait_for_dependencies_w(p, ndep, deprank, RLI(w, 1), epoch, lane, ctl + 1);
+          const unsigned watch = gm ? (unsigned)(gw >> 16) & 15u : ~0u;   // (granule rows: their producers' flags are not waited for)
+          if (ndep > 0 && watch) wait_for_dependencies_w(p, ndep, deprank, RLI(w, 1), epoch, lane, ctl + 1, watch);
 #ifdef STEREO_HIP_VISIT_PROFILE
           const long long lb1 = (long long)__builtin_readcyclecounter();
 #endif
@@ -378,6 +426,52 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
             mrest &= mrest - 1;
             stn[kStM + jx * kWave + lane] = ld_sc1((SPEC && spec_in && ((smask >> jx) & 1)) ? PIPE_ROW((p.spec_rows + lkv), seg * 8 + jx)
                                                                                 : PIPE_ROW((p.msg + lkv), __builtin_amdgcn_readlane(w, 4 + jx)));
+          }
+          if (gm) {
+            // rows (and labels) of other runs' nodes that arrive as granules: re-read until every tag is this sweep's
+            // epoch -- bounded by the wall clock like the flag wait, and a give-up aborts the workgroup the same way
+            int gr = gm;
+            const int g0 = __builtin_ctz(gr);
+            int gj[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { gj[k] = gr ? __builtin_ctz(gr) : g0; gr &= gr - 1; }
+            const bool more = __builtin_popcount(gm) > 2;
+            const unsigned long long *ga[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ga[k] = p.gran + 2 * ((size_t)(unsigned)RLI(w, 4 + gj[k]) * (unsigned)Kv + lkv);
+            const unsigned long long *xg = p.xgran + xn;
+            const bool want_x = PRIMAL && lane < 8 && ((gm >> lane) & 1);
+            const unsigned ep = (unsigned)epoch;
+            gran4 a0 = {0, 0, 0, 0}, a1 = a0, a2 = a0, a3 = a0;
+            unsigned long long xv = 0;
+            int spins = 0;
+            long long t0 = 0;
+            for (;;) {
+              bool ok = true;
+              if (UPDATE) {
+                if (PRIMAL) load_granules2x(ga[0], ga[1], xg, a0, a1, xv);
+                else load_granules2(ga[0], ga[1], a0, a1);
+                ok = granules_tagged(a0, ep) && granules_tagged(a1, ep);
+                if (more) { load_granules2(ga[2], ga[3], a2, a3); ok = ok && granules_tagged(a2, ep) && granules_tagged(a3, ep); }
+              } else {
+                load_granule_x(xg, xv);
+              }
+              if (want_x) ok = ok && (unsigned)(xv >> 32) == ep;
+              if (!UNI(!ok)) break;
+              if (!keep_waiting(p, spins, t0, false)) {
+                if (lane == 0) {
+                  report_give_up(p, RLI(w, 1), RLI(w, 20 + __builtin_ctz(~(gw >> 16) | 16)), (int)a0.y, epoch);
+                  ctl[1] = 1;
+                }
+                break;
+              }
+            }
+            if (UPDATE) {
+              stn[kStM + gj[0] * kWave + lane] = granules_value(a0);
+              stn[kStM + gj[1] * kWave + lane] = granules_value(a1);
+              if (more) { stn[kStM + gj[2] * kWave + lane] = granules_value(a2); stn[kStM + gj[3] * kWave + lane] = granules_value(a3); }
+            }
+            if (want_x) pxv = (int)(unsigned)xv;
           }
           if (lane < 8) stni[64 + lane] = pxv;
 #ifdef STEREO_HIP_VISIT_PROFILE
@@ -625,6 +719,11 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
           xprev2 = xprev; xprev = bi;
           const double eb = readlane_f64(db, bi);
           if (lane == 0) { sc[9] = eb; ((int *)(sc + 10))[0] = bi; }
+          if (p.gran && ((__builtin_amdgcn_readfirstlane(sti[kDescGran]) >> 20) & 1)) {   // the label, for consumers in other runs
+            const int node = __builtin_amdgcn_readfirstlane(sti[0]);
+            granule_delay(p, node);
+            if (lane == 0) __hip_atomic_store(p.xgran + node, ((unsigned long long)(unsigned)epoch << 32) | (unsigned)bi, __ATOMIC_RELAXED, STEREO_HANDOVER_SCOPE);
+          }
         }
       }
       if (p.prof) busy += (unsigned long long)((long long)__builtin_readcyclecounter() - tstart);

@@ -165,6 +165,8 @@ struct stereo_trws_plan {
   DevBuf<int32_t> d_tail, d_order, d_fptr, d_fidx, d_bptr, d_bidx, d_lbn, d_lbe, d_x;
   DevBuf<uint8_t> d_mdir;
   DevBuf<double> d_gamma, d_msg, d_lbterms, d_eterms;
+  // tagged-granule hand-over of trws_pipe_kernel (DevParams::gran / xgran); unallocated: off
+  DevBuf<unsigned long long> d_gran, d_xgran;
   // persistent sweep schedule
   DevBuf<int32_t> d_run_order[2], d_chain_run_ptr[2], d_chain_run_order[2];
   DevBuf<int32_t> d_run_ptr[2], d_dep_ptr[2], d_dep_rank[2], d_done, d_ctl;  // d_ctl: [ticket, abort, give-up report x 4]
@@ -297,6 +299,7 @@ DevParams make_params(stereo_trws_plan *P, bool allow_spec = true) {
   p.peer_msg0 = P->peer_msg[0]; p.peer_msg1 = P->peer_msg[1];
   p.peer_done0 = P->peer_done[0]; p.peer_done1 = P->peer_done[1];
   p.peer_x0 = P->peer_x[0]; p.peer_x1 = P->peer_x[1];
+  p.gran = P->d_gran.p; p.xgran = P->d_xgran.p;
   p.done = P->d_done.p; p.ticket = P->d_ctl.p; p.abort_flag = P->d_ctl.p + 1; p.N = (int)P->Nl;
   p.spin_ticks = P->spin_ticks;
   p.n_own = P->layout ? (int)P->layout->n_own : (int)P->Nl;
@@ -383,6 +386,8 @@ void reset_state(stereo_trws_plan *P) {
   STEREO_HIP_CHECK(hipMemset(P->d_msg.p, 0, sizeof(double) * (size_t)P->El * P->K));
   STEREO_HIP_CHECK(hipMemset(P->d_x.p, 0, sizeof(int32_t) * P->Nl));
   STEREO_HIP_CHECK(hipMemset(P->d_done.p, 0, sizeof(int32_t) * P->d_done.n));
+  if (P->d_gran.p) STEREO_HIP_CHECK(hipMemset(P->d_gran.p, 0, sizeof(unsigned long long) * P->d_gran.n));   // (tags: epochs restart)
+  if (P->d_xgran.p) STEREO_HIP_CHECK(hipMemset(P->d_xgran.p, 0, sizeof(unsigned long long) * P->d_xgran.n));
   STEREO_HIP_CHECK(hipMemset(P->d_ctl.p, 0, sizeof(int32_t) * kCtlWords));
   STEREO_HIP_CHECK(hipDeviceSynchronize());
   P->iterations = 0; P->energy = 0; P->lb = 0; P->epoch = 0; P->fwd_pending = false;
@@ -771,6 +776,17 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
       if (max_blocks > 0) P->grid_blocks = std::min(P->grid_blocks, max_blocks);
     }
     if (fine) P->d_msg.alloc_fine_grained((size_t)P->El * K); else P->d_msg.alloc((size_t)P->El * K);
+    {
+      // the granule hand-over between ordinary runs (trws_graph.h: kDescGran): trws_pipe_kernel of one plan;
+      // STEREO_HIP_TRWS_GRANULES=0 keeps every row behind the completion flags
+      bool gran = P->fast && nstrips == 1;
+      if (const char *e = std::getenv("STEREO_HIP_TRWS_GRANULES")) gran = gran && std::atoi(e) != 0;
+      if (gran) {
+        P->d_gran.alloc(2 * (size_t)P->El * K); P->d_xgran.alloc(P->Nl);
+        STEREO_HIP_CHECK(hipMemset(P->d_gran.p, 0, sizeof(unsigned long long) * P->d_gran.n));
+        STEREO_HIP_CHECK(hipMemset(P->d_xgran.p, 0, sizeof(unsigned long long) * P->d_xgran.n));
+      }
+    }
     if (P->large) P->d_large_scr.alloc((size_t)P->grid_blocks * large_scratch_doubles(P->Kp));
     P->d_lbterms.alloc(P->n_lb);
     P->d_eterms.alloc(P->n_en);
@@ -1481,7 +1497,8 @@ namespace {
 std::string trws_env_key() {
   std::string k;
   for (const char *name : {"STEREO_HIP_GPUS", "STEREO_HIP_TRWS_CERTIFICATE", "STEREO_HIP_TRWS_FAST", "STEREO_HIP_TRWS_SPIN_SECONDS", "STEREO_HIP_TRWS_PROF",
-                           "STEREO_HIP_TRWS_TIMELINE", "STEREO_HIP_TRWS_SPEC", "STEREO_HIP_TRWS_SPEC_SEG", "STEREO_HIP_STRIPS_FINEGRAINED"}) {
+                           "STEREO_HIP_TRWS_TIMELINE", "STEREO_HIP_TRWS_SPEC", "STEREO_HIP_TRWS_SPEC_SEG", "STEREO_HIP_STRIPS_FINEGRAINED",
+                           "STEREO_HIP_TRWS_GRANULES"}) {
     const char *v = std::getenv(name);
     k += v ? v : "-";
     k += '|';

@@ -319,6 +319,20 @@ def spec_schedule(N, connectivity0, direction):
                 run_ptr=run_ptr[:R + 1], kind=kind[:R], ticket_run=ticket_run[:R + 1])
 
 
+def descriptors(N, connectivity0, direction):
+    """Host-only: the descriptors of the chain schedule (stereo_trws_descriptors_host), (N, 64) int32 in the
+    positions of schedule(N, connectivity0, direction); layout in trws_graph.h."""
+    c = np.asarray(connectivity0)
+    if c.ndim != 2 or c.shape[0] != 2:
+        raise StereoHipError("connectivity must be 2 x E")
+    c = np.asfortranarray(c, dtype=np.uint32)
+    desc = np.zeros((N, 64), np.int32)
+    err = _lib.errbuf()
+    _lib.check(_lib.lib().stereo_trws_descriptors_host(C.c_int64(N), C.c_int64(c.shape[1]), _ptr(c, C.c_uint32), C.c_int(direction),
+                                                       _ptr(desc, C.c_int32), err, C.c_size_t(len(err))), err)
+    return desc
+
+
 def simulate_spec_schedule(sched, spec, workgroups, visit=1.0, runner_visit=0.25, handover=0.0):
     """Discrete simulation of a sweep on the speculative schedule with `workgroups` resident workgroups
     that take tickets in order.  sched: schedule() of the same graph and direction (positions, dependencies);
