@@ -892,6 +892,12 @@ __device__ __forceinline__ bool keep_waiting(const DevParams &p, int &spins, lon
   if (t0 == 0) { t0 = now | 1; return true; }
   return now - t0 < (halo ? p.spin_ticks : 2 * p.spin_ticks);
 }
+// The run behind the next ticket of direction D: tickets in processing order, nruns[D] once none is left.
+template <int D>
+__device__ __forceinline__ int next_run(const DevParams &p) {
+  const int t = atomicAdd(p.ticket, 1);
+  return t < p.ntickets[D] ? (p.run_order[D] ? p.run_order[D][t] : t) : p.nruns[D];
+}
 // The first visit that gives up says what it was waiting for (the host turns it into the error text):
 // abort_flag[1..4] = visiting rank, awaited rank, value seen in its flag, epoch expected.
 __device__ __forceinline__ void report_give_up(const DevParams &p, int visiting_rank, int awaited_rank, int seen, int epoch) {

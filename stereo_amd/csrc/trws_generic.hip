@@ -399,7 +399,7 @@ __global__ __launch_bounds__(kBlock) void trws_persistent_kernel(DevParams p, in
   const int8_t *in_slot = p.in_slot[D];
   const int N = p.N;
   for (;;) {
-    if (tid == 0) { const int t_ = atomicAdd(p.ticket, 1); *s_run = t_ < p.ntickets[BACKWARD ? 1 : 0] ? (p.run_order[BACKWARD ? 1 : 0] ? p.run_order[BACKWARD ? 1 : 0][t_] : t_) : p.nruns[BACKWARD ? 1 : 0]; }
+    if (tid == 0) *s_run = next_run<D>(p);
     __syncthreads();
     const int run = *s_run;
     __syncthreads();

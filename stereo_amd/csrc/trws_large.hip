@@ -290,7 +290,7 @@ __global__ __launch_bounds__(kLBlock) void trws_large_kernel(DevParams p, int ep
   for (int k = tid; k < K; k += kLBlock) L.P[k] = p.pos[k];
   __syncthreads();
   for (;;) {
-    if (tid == 0) { const int t_ = atomicAdd(p.ticket, 1); *s_run = t_ < p.ntickets[D] ? (p.run_order[D] ? p.run_order[D][t_] : t_) : p.nruns[D]; }
+    if (tid == 0) *s_run = next_run<D>(p);
     __syncthreads();
     const int run = *s_run;
     __syncthreads();

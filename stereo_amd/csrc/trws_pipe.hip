@@ -88,15 +88,8 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
   // iteration either way).  At this point only the kernel arguments are live.
   bool have_ticket = false;
   if (SPEC) {
-    if (threadIdx.x == 0) {
-      const int t_ = atomicAdd(p.ticket, 1);
-      ctl[0] = t_ < p.ntickets[D] ? (p.run_order[D] ? p.run_order[D][t_] : t_) : p.nruns[D];
-      ctl[1] = 0; ctl[2] = 0; ctl[3] = 0;
-    }
-    __syncthreads();
-    const int first = __builtin_amdgcn_readfirstlane(ctl[0]);
-    __syncthreads();
-    if (first == -1) chain_runner<BACKWARD, PRIMAL, UPDATE>(p.self, epoch, kPipeLdsDoubles, kPipeCtlOff);
+    if (threadIdx.x == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; }
+    if (draw_first_ticket<D>(p, ctl) == -1) chain_runner<PipeRunner, BACKWARD, PRIMAL, UPDATE>(p.self, epoch);
     else have_ticket = true;
   }
   const int K = p.K;
@@ -734,7 +727,7 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
     }
     }
     if (SPEC && seg >= 0) {
-      const int verdict = spec_commit<BACKWARD, PRIMAL, UPDATE>(p.self, epoch, p0, p1, seg, spec_in ? 1 : 0);
+      const int verdict = spec_commit<1, kPipeWaves, 2, BACKWARD, PRIMAL, UPDATE>(p.self, epoch, p0, p1, seg, spec_in ? 1 : 0, 2 * kPipeCtlOff);
       if (verdict == 2) return;
       if (verdict == 1) continue;   // (ctl[3] is set: the same run once more)
     }
@@ -783,7 +776,7 @@ size_t pipe_lds_bytes() {
                                    kPipeCompute * kPipeXchg + kPipeCompute / 2, "LDS layout of pipe_body");
   return sizeof(double) * kPipeLdsDoubles;
 }
-size_t pipe_spec_lds_bytes() { return sizeof(double) * (kPipeLdsDoubles + kRunDoubles + kRunDummy); }   // ... with the runner's ring behind
+size_t pipe_spec_lds_bytes() { return sizeof(double) * (kRunBase + kRunDoubles + kRunDummy); }   // ... with the runner's ring behind
 int pipe_threads() { return kPipeThreads; }
 
 void pipe_set_attributes() {

@@ -1,5 +1,6 @@
-// The RUNNER of the speculative schedule (trws_graph.h: Sweep::Spec), for trws_pipe_kernel with shared
-// uniformly spaced positions and the linear kernel.  One workgroup draws the runner's ticket and walks the whole cut run
+// The speculative schedule (trws_graph.h: Sweep::Spec): first what both runners share (word layout, LDS
+// waits, publisher, the segment commit; trws_wspec.h holds the wide kernel's runner), then the RUNNER of trws_pipe_kernel
+// with shared uniformly spaced positions and the linear kernel.  One workgroup draws the runner's ticket and walks the whole cut run
 // computing nothing but the recurrence that makes the run serial:
 //   wave 0      messages: Di of node i from the staged prefix sum and the row(s) node i - 1 handed over, H = gamma Di - m,
 //               plain windowed min-plus (what message_regs returns whenever its certificate holds), the row for node i + 1
@@ -10,7 +11,7 @@
 //   wave 10     publisher: at every cut, the rows / label of the node in front go to p.spec_rows / p.spec_x, drained, then
 //               the segment's flag done[N + s].
 // Nothing here decides a result: the segments recompute every visit with the certified routine and compare what they
-// started from with what the segment in front produced (pipe_body's commit).  A wrong row costs a second walk of one or
+// started from with what the segment in front produced (spec_commit).  A wrong row costs a second walk of one or
 // more segments, never a wrong bit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,52 +23,78 @@
 namespace stereo {
 namespace {
 
-constexpr int kRunSlots = 10;
-constexpr int kRunLoaders = 8;
-// a staged node (doubles): prefix sum P | up to three staged rows of the tail | old rows of the (up to two) messages to
-// compute | unary | the node's own (outgoing) rows | words
-constexpr int kRunRowP = 0, kRunRowS = 64, kRunRowM = 256, kRunRowTH = 384, kRunRowOUT = 448, kRunSc = 704;
-constexpr int kRunSlotDoubles = kRunSc + 16;
-constexpr int kRunTab = kRunSlots * kRunSlotDoubles;   // 16 + 64 + 16: H with +inf on both sides
-constexpr int kRunPub = kRunTab + 96;                  // 2 x (2 rows): what the publisher stores
-constexpr int kRunWords = kRunPub + 256;               // 64 ints (below)
-constexpr int kRunDoubles = kRunWords + 32;
-constexpr int kRunDummy = 32;                           // 64 more words: where the lanes that have nothing to say store (run_visit_m)
-// words: consumed by messages, by labels | publisher flags (rows x 2, labels x 2) | slots freed | label x 2 | node x 2 |
-//        row kinds x 2
-constexpr int kRwConsM = 12, kRwConsP = 13, kRwPubM = 14, kRwPubP = 16, kRwFree = 18, kRwLabel = 20, kRwNode = 22, kRwKinds = 24;
+// ==== shared by both runners (this file: trws_pipe_kernel, K <= 64; trws_wspec.h: trws_wide_kernel, 64 < K <= 256) ====
+// A runner's LDS: a ring of staged nodes, slot layout in rows of R = 64 C labels (C: 64-label chunks per lane) -- prefix
+// sum P | up to three staged rows of the tail | old rows of the (up to two) messages to compute | unary | the node's own
+// (outgoing) rows | words -- then per runner the H table(s), the rows for the publisher and 64 words:
+//   labels consumed 13 | label published x 2: 16 | slots freed 18 | label x 2: 20 | node x 2: 22 | row kinds x 2: 24 |
+//   rows published, per message wave, x 2: 32-39 (the rest per runner)
+constexpr int kSwConsP = 13, kSwPubP = 16, kSwFree = 18, kSwLabel = 20, kSwNode = 22, kSwKinds = 24, kSwPubM = 32;
 // words of a staged node: tail length | tail kinds (a nibble each: 0-2 staged row, 8 / 9 first / second handed-over row;
-// the length once more in bits 16-)
-// | messages to compute (0, 1, 2) | cut: segment that starts behind this node (0: none) | kinds of that segment's first
-// node's rows (a nibble per row) | n_out | incoming rows | their label (-1: the node in front) x 4 | their direction
-// bits | node id | word 15: the TAG, schedule position + 1, written last (behind a release fence): a reader that
-// finds it finds the node.  doubles 8-15: alpha x 2, gamma, alpha of the incoming rows x 4
+// the length once more in bits 16-) | messages to compute (0, 1, 2) | cut: segment that starts behind this node (0: none)
+// | kinds of that segment's first node's rows (a nibble per row) | n_out | incoming rows | their label (-1: the node in
+// front) x 4 | their direction bits | node id | word 15: the TAG, schedule position + 1, written last (behind a release
+// fence): a reader that finds it finds the node.  doubles 8-15: alpha x 2, gamma, alpha of the incoming rows x 4
 constexpr int kRsNt = 0, kRsKinds = 1, kRsNmsg = 2, kRsCut = 5, kRsPubKinds = 6, kRsNout = 7, kRsNin = 8, kRsSrc = 9, kRsMd = 13,
               kRsNode = 14, kRsTag = 15;
 
-__device__ __forceinline__ int lds_load(const int *w) { return __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void lds_store(int *w, int v) { __hip_atomic_store(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+// Words of the runner's LDS, addressed AS LDS: through a generic pointer these become flat accesses, whose completion is
+// counted together with the global loads -- a loader that polls a word would wait for the rows it has just requested
+// for its next node; the fences are LDS-only for the same reason.
+typedef __attribute__((address_space(3))) int spec_lds_int;
+__device__ __forceinline__ int lds_load(const int *w) { return __hip_atomic_load((const spec_lds_int *)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void lds_store(int *w, int v) { __hip_atomic_store((spec_lds_int *)w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+#define SPEC_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local")
+#define SPEC_RELEASE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local")
 
-// Waits until *word >= want.  Everything the runner's waves wait for inside the workgroup ends with a loader's wait for
-// another workgroup, which is bounded by the wall clock and raises the abort word when it gives up; this wait looks at
-// that word (and, as a last resort against a hang, at the clock itself).
-__device__ __forceinline__ bool run_wait(const DevParams &p, const int *word, int want, int *abort_word) {
+// The bound of the waits below.  Everything a runner's waves wait for inside the workgroup ends with a loader's wait for
+// another workgroup, which is bounded by the wall clock and raises the abort word when it gives up; a wait looks at that
+// word (and, as a last resort against a hang, at the clock itself) every MASK + 1 polls.
+template <int MASK>
+__device__ __forceinline__ bool spec_keep_waiting(int &spins, long long &t0, int *abort_word, int32_t *abort_flag, long long spin_ticks) {
+  spins = (spins + 1) & MASK;
+  if (spins != 0) return true;
+  if (lds_load(abort_word) || ld_sc1(abort_flag)) return false;
+  const long long now = (long long)wall_clock64();
+  if (t0 == 0) { t0 = now | 1; return true; }
+  if (now - t0 > 4 * spin_ticks) { lds_store(abort_word, 1); return false; }
+  return true;
+}
+// Waits until *word >= want.  SLEEP: an s_sleep between polls; without it (waits inside a loader's turn or the labels'
+// visit, which are short) the clock is looked at every 4096 polls.
+template <bool SLEEP>
+__device__ __forceinline__ bool run_wait_i(const int *word, int want, int *abort_word, int32_t *abort_flag, long long spin_ticks) {
   int spins = 0;
   long long t0 = 0;
   while (lds_load(word) < want) {
-    __builtin_amdgcn_s_sleep(1);
-    spins = (spins + 1) & 1023;
-    if (spins != 0) continue;
-    if (lds_load(abort_word) || ld_sc1(p.abort_flag)) return false;
-    const long long now = (long long)wall_clock64();
-    if (t0 == 0) { t0 = now | 1; continue; }
-    if (now - t0 > 4 * p.spin_ticks) { lds_store(abort_word, 1); return false; }
+    if (SLEEP) __builtin_amdgcn_s_sleep(1);
+    if (!spec_keep_waiting<SLEEP ? 1023 : 4095>(spins, t0, abort_word, abort_flag, spin_ticks)) return false;
   }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  SPEC_ACQUIRE();
   return true;
 }
-
-#define RLI(v, i) __builtin_amdgcn_readlane((v), (i))
+// (the same as a call: the slow path of a visit that found its node not staged yet)
+__device__ __attribute__((noinline)) bool run_wait(const int *word, int want, int *abort_word, int32_t *abort_flag, long long spin_ticks) {
+  return run_wait_i<true>(word, want, abort_word, abort_flag, spin_ticks);
+}
+// ... until all of words[0 .. N - 1] >= want (N = 1: the sleeping wait; N = 4: 16-byte aligned, the four words come with
+// ONE LDS read per look)
+template <int N>
+__device__ __forceinline__ bool run_wait_n(const int *words, int want, int *abort_word, int32_t *abort_flag, long long spin_ticks) {
+  static_assert(N == 1 || N == 4, "run_wait_n");
+  if (N == 1) return run_wait_i<true>(words, want, abort_word, abort_flag, spin_ticks);
+  typedef int spec_v4i __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(3))) const volatile spec_v4i spec_lds_v4i;
+  int spins = 0;
+  long long t0 = 0;
+  for (;;) {
+    const spec_v4i v = *(spec_lds_v4i *)words;
+    if (min(min(v.x, v.y), min(v.z, v.w)) >= want) break;
+    if (!spec_keep_waiting<4095>(spins, t0, abort_word, abort_flag, spin_ticks)) return false;
+  }
+  SPEC_ACQUIRE();
+  return true;
+}
 
 // Arguments of a real (non-inlined) device function arrive in vector registers and the compiler must take them, and
 // everything loaded through them, for lane-varying: every branch on such a value becomes an exec-mask region, every loop
@@ -98,6 +125,198 @@ __device__ __forceinline__ DevParams uniform_params(const DevParams *pp) {
   return q;
 }
 
+// The first ticket of a sweep, drawn before the visit loops exist: ticket 0 is the runner's (run -1), which the workgroup
+// that draws it serves at once; `word`: an LDS word the visit loops do not hold yet.
+template <int D>
+__device__ __forceinline__ int draw_first_ticket(const DevParams &p, int *word) {
+  if (threadIdx.x == 0) *word = next_run<D>(p);
+  __syncthreads();
+  const int run = __builtin_amdgcn_readfirstlane(*word);
+  __syncthreads();
+  return run;
+}
+
+// ---- the publisher: at every cut the rows / label of the node in front go to p.spec_rows / p.spec_x, drained, then the
+// segment's flag done[N + s].  RL: the runner's layout (C chunks, LDS base, rows for the publisher, words, abort word).
+template <class RL, bool PRIMAL, bool UPDATE>
+__device__ __attribute__((noinline)) void run_publisher(const DevParams *pp_, int epoch_) {
+  extern __shared__ __attribute__((aligned(16))) double spec_lds[];
+  const DevParams p = uniform_params(pp_);
+  constexpr int R = RL::C * kWave;
+  double *rb = spec_lds + RL::kBase;
+  int *abort_word = (int *)spec_lds + RL::kAbortInt;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int epoch = __builtin_amdgcn_readfirstlane(epoch_);
+  const int K = p.K;
+  int *rw = (int *)(rb + RL::kWords);
+  for (int s = 1; s < p.spec_nseg; ++s) {
+    const int ps = s & 1;
+    if (UPDATE) {
+      if (!run_wait_n<RL::C>(rw + kSwPubM + 4 * ps, s, abort_word, p.abort_flag, p.spin_ticks)) return;
+      const double *pb = rb + RL::kPub + ps * 2 * R;
+      const int kinds = lds_load(rw + kSwKinds + ps);
+#pragma unroll
+      for (int c = 0; c < RL::C; ++c) {
+        const int kk = c * kWave + lane;
+        if (kk < K) {
+          double a0 = pb[kk], a1 = pb[R + kk];
+          if ((p.debug & 16384) && s % 3 == 1 && kk == 0) a0 = __longlong_as_double(__double_as_longlong(a0) ^ 1ll);   // (development: a wrong row)
+          if ((p.debug & 65536) && s % 3 == 1 && (kk & 1)) a0 += 0.375;                                                // (development: a VERY wrong row)
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const int kd = (kinds >> (4 * k)) & 15;
+            if (kd) st_sc1(p.spec_rows + ((size_t)s * 8 + k) * K + kk, kd == 8 ? a0 : a1);
+          }
+        }
+      }
+    }
+    if (PRIMAL) {
+      if (!run_wait_i<true>(rw + kSwPubP + ps, s, abort_word, p.abort_flag, p.spin_ticks)) return;
+      int label = lds_load(rw + kSwLabel + ps);
+      if ((p.debug & 32768) && s % 5 == 2) label = label > 0 ? label - 1 : (K > 1 ? 1 : 0);                          // (development: a wrong label)
+      if (lane == 0) st_sc1(p.spec_x + s, label);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0) { st_sc1(p.done + p.N + s, epoch); lds_store(rw + kSwFree, s); }
+  }
+}
+
+// ---- commit of a speculative segment (called by all WAVES waves of the workgroup behind the barrier that ended the
+// segment's last visit: the storer has drained the last node's rows).  The segment in front commits first (its flag);
+// then what this segment started from is compared, bit for bit, with what that segment's last node really handed over:
+// equal -> every visit here saw the sequential sweep's inputs and the nodes' flags go up; different (the runner's plain
+// min-plus row was not the reference's envelope, or a row of the runner's was stale) -> the overwritten rows are put back
+// and the caller walks the visits again from the real rows.  ctl: the kernel's control words ([1] abort, [3] walk again,
+// [VERDICT] free between visits).  Returns 0 committed, 1 walk again (ctl[3] set), 2 gave up (p.abort_flag raised: the
+// abort word may also have come from a wait of the visits that reports nothing itself).
+template <int C, int WAVES, int VERDICT, bool BACKWARD, bool PRIMAL, bool UPDATE>
+__device__ __attribute__((noinline)) int spec_commit(const DevParams *pp_, int epoch_, int p0_, int p1_, int seg_, int compare_, int ctl_off_) {
+  extern __shared__ __attribute__((aligned(16))) double spec_lds[];
+  const DevParams &p = *pp_;
+  const int epoch = epoch_, p0 = p0_, p1 = p1_, seg = seg_, compare = compare_;
+  constexpr int D = BACKWARD ? 1 : 0;
+  constexpr int DW = TrwsGraph::kDescWords;
+  const int32_t *desc = p.desc[D];
+  int *ctl = (int *)spec_lds + ctl_off_;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int K = p.K;
+  if (compare) {
+    if (wave == 0) {
+      int differ = 0;
+      if (!wait_flag(p, p.N + p.spec_nseg + seg, epoch, -2)) { if (lane == 0) ctl[1] = 1; }
+      else {
+        const int w = desc[(size_t)p0 * DW + lane];
+        const int f = __builtin_amdgcn_readlane(w, 2);
+        const int nout = f & 15, ntot = nout + ((f >> 4) & 15);
+        for (int j = nout; j < ntot; ++j) {
+          if (__builtin_amdgcn_readlane(w, 12 + j) < 0) continue;
+          if (UPDATE) {
+            const size_t ea = ((size_t)seg * 8 + j) * K, eb = (size_t)__builtin_amdgcn_readlane(w, 4 + j) * K;
+            for (int c = 0; c < C; ++c) {
+              const int kk = c * kWave + lane, kc = kk < K ? kk : K - 1;
+              const double a = ld_sc1(p.spec_rows + ea + kc), b = ld_sc1(p.msg + eb + kc);
+              differ |= UNI(__double_as_longlong(a) != __double_as_longlong(b)) ? 1 : 0;
+            }
+          }
+          if (PRIMAL) differ |= ld_sc1(p.spec_x + seg) != ld_sc1(p.x + __builtin_amdgcn_readlane(w, 32 + j)) ? 1 : 0;
+        }
+      }
+      if (lane == 0) ctl[VERDICT] = differ;
+    }
+    __syncthreads();
+    const int differ = __builtin_amdgcn_readfirstlane(ctl[VERDICT]);
+    const int gave_up = __builtin_amdgcn_readfirstlane(ctl[1]);
+    __syncthreads();
+    if (tid == 0) ctl[VERDICT] = 0;
+    if (gave_up) { if (tid == 0) st_sc1(p.abort_flag, 1); return 2; }
+    if (differ) {
+      if (UPDATE) {
+        for (int pos = p0 + wave; pos < p1; pos += WAVES) {
+          const int w = desc[(size_t)pos * DW + lane];
+          const int nout = __builtin_amdgcn_readlane(w, 2) & 15;
+          for (int j = 0; j < nout && j < 4; ++j) {
+            const size_t em = (size_t)__builtin_amdgcn_readlane(w, 4 + j) * K, eu = ((size_t)(seg * p.spec_max_len + (pos - p0)) * 4 + j) * K;
+            for (int c = 0; c < C; ++c) {
+              const int kk = c * kWave + lane;
+              if (kk < K) st_sc1(p.msg + em + kk, ld_sc1(p.spec_undo + eu + kk));
+            }
+          }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");   // (the second walk's plain loads must not find this CU's L1 holding anything of the first)
+      }
+      if (tid == 0) { ctl[3] = 1; if (p.spec_stat) atomicAdd(p.spec_stat, 1ull); }
+      __syncthreads();
+      return 1;
+    }
+  }
+  if (wave == 0) {
+    // the segment behind first (the commits are a serial chain), then the nodes' own flags
+    if (seg + 1 < p.spec_nseg && lane == 0) st_sc1(p.done + p.N + p.spec_nseg + seg + 1, epoch);
+    for (int pos = p0 + lane; pos < p1; pos += kWave) st_sc1(p.done + desc[(size_t)pos * DW + 1], epoch);
+    if (lane == 0 && p.spec_stat) atomicAdd(p.spec_stat + 1, 1ull);
+  }
+  return 0;
+}
+
+// ---- the runner's entry: ring words and tags cleared, +inf on both sides of the H table(s), RL::prepare, the roles by
+// wave -- RL::kMsgWaves message waves, the labels, RL::kLoaders loaders, the publisher -- and the development stamps
+// (timeline[2 tl_stride + D]; spec_stat[8 + 4 D + ...]: when the messages, the labels, the last loader and the publisher
+// were done, 100 MHz ticks since the roles started).  RL also gives the layout (C, base, slots, tables, words, abort word)
+// and kOverlay: the runner's LDS overlays the visit loops' (which clear it, so an abort word left up goes to p.abort_flag).
+// (noinline, parameters through a pointer to their copy in global memory, LDS through the dynamic allocation's own
+//  symbol: nothing of this routine -- registers, scalars, the parameter block's address -- leaks into the kernel it is
+//  called from, whose visit loops sit at the register limits; it is called before they exist)
+template <class RL, bool BACKWARD, bool PRIMAL, bool UPDATE>
+__device__ __attribute__((noinline)) void chain_runner(const DevParams *pp_, int epoch_) {
+  extern __shared__ __attribute__((aligned(16))) double spec_lds[];
+  const DevParams &p = *pp_;
+  const int epoch = epoch_;
+  constexpr int R = RL::C * kWave, M = RL::kMsgWaves, D = BACKWARD ? 1 : 0;
+  double *rb = spec_lds + RL::kBase;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int c0 = p.spec_c0[D], c1 = p.spec_c1[D];
+  int *rw = (int *)(rb + RL::kWords);
+  if (tid < 64) rw[tid] = 0;
+  if (tid < RL::kSlots) ((int *)(rb + tid * RL::kSlotDoubles + RL::kSc))[kRsTag] = 0;   // (no node staged)
+  if (tid < 32 * RL::kTabs) {
+    const int t = tid >> 5, e = tid & 31;
+    rb[RL::kTab + t * (R + 32) + (e < 16 ? e : R + e)] = __builtin_huge_val();
+  }
+  RL::prepare(p, rb, tid);
+  if (p.timeline && tid == 0) p.timeline[((size_t)2 * p.tl_stride + D) * 2] = wall_clock64();
+  __syncthreads();
+  const unsigned long long trole0 = wall_clock64();
+  if (wave < M) { if (UPDATE) { __builtin_amdgcn_s_setprio(3); RL::template messages<BACKWARD>(pp_, wave); __builtin_amdgcn_s_setprio(0); } }
+  else if (wave == M) { if (PRIMAL) { __builtin_amdgcn_s_setprio(3); RL::template labels<BACKWARD>(pp_); __builtin_amdgcn_s_setprio(0); } }
+  else if (wave < M + 1 + RL::kLoaders) RL::template loader<BACKWARD, PRIMAL, UPDATE>(pp_, epoch, wave - M - 1);
+  else if (wave == M + 1 + RL::kLoaders) run_publisher<RL, PRIMAL, UPDATE>(pp_, epoch);
+  if (p.timeline && p.spec_stat && (tid & (kWave - 1)) == 0 && (wave == 0 || wave == M || wave == M + RL::kLoaders || wave == M + 1 + RL::kLoaders))
+    p.spec_stat[8 + 4 * D + (wave == 0 ? 0 : wave == M ? 1 : wave == M + RL::kLoaders ? 2 : 3)] = wall_clock64() - trole0;
+  __syncthreads();
+  if (RL::kOverlay && lds_load((int *)spec_lds + RL::kAbortInt) && tid == 0) st_sc1(p.abort_flag, 1);
+  if (p.timeline && tid == 0) p.timeline[((size_t)2 * p.tl_stride + D) * 2 + 1] = wall_clock64();
+  if (p.spec_stat && tid == 0) atomicAdd(p.spec_stat + 2, (unsigned long long)(c1 - c0));
+  if (RL::kOverlay) __syncthreads();
+}
+
+// ==== the runner of trws_pipe_kernel (K <= 64: one label per lane) ====================================================
+constexpr int kRunSlots = 10;
+constexpr int kRunLoaders = 8;
+constexpr int kRunRowP = 0, kRunRowS = 64, kRunRowM = 256, kRunRowTH = 384, kRunRowOUT = 448, kRunSc = 704;
+constexpr int kRunSlotDoubles = kRunSc + 16;
+constexpr int kRunTab = kRunSlots * kRunSlotDoubles;   // 16 + 64 + 16: H with +inf on both sides
+constexpr int kRunPub = kRunTab + 96;                  // 2 x (2 rows): what the publisher stores
+constexpr int kRunWords = kRunPub + 256;               // 64 ints (above; 12: nodes consumed by the message wave)
+constexpr int kRunDoubles = kRunWords + 32;
+constexpr int kRunDummy = 32;                           // 64 more words: where the lanes that have nothing to say store (run_visit_m)
+constexpr int kRwConsM = 12;
+constexpr int kRunBase = kPipeLdsDoubles, kRunAbortInt = 2 * kPipeCtlOff + 1;   // (behind the visit loops' LDS; abort word: ctl[1])
+
+#define RLI(v, i) __builtin_amdgcn_readlane((v), (i))
+
 // ---- wave 0: the message recurrence ------------------------------------------------------------------------------
 // What a visit reads from its staged node, requested in one go and WITHOUT waiting for the node to be there: the words
 // first (tag included: one instruction, one snapshot), the rows behind a compiler barrier -- LDS serves a wave's
@@ -123,23 +342,6 @@ struct RunArgsM {
   unsigned long long *stat;
 };
 
-// Waits until *word >= want (the slow path of a visit that found its node not staged yet).
-__device__ __attribute__((noinline)) bool run_wait_m(const int *word, int want, int *abort_word, int32_t *abort_flag, long long spin_ticks) {
-  int spins = 0;
-  long long t0 = 0;
-  while (lds_load(word) < want) {
-    __builtin_amdgcn_s_sleep(1);
-    spins = (spins + 1) & 1023;
-    if (spins != 0) continue;
-    if (lds_load(abort_word) || ld_sc1(abort_flag)) return false;
-    const long long now = (long long)wall_clock64();
-    if (t0 == 0) { t0 = now | 1; continue; }
-    if (now - t0 > 4 * spin_ticks) { lds_store(abort_word, 1); return false; }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  return true;
-}
-
 // One visit of the recurrence.  `cur`: the node's words and rows (asked for during the previous visit), `nxt`: where the
 // next node's go.  Everything that steers the visit is a scalar; the lanes only ever do the arithmetic.
 template <bool BACKWARD, int G>
@@ -150,7 +352,7 @@ __device__ __forceinline__ bool run_visit_m(const RunArgsM &a, double *rb, int *
   if (__builtin_amdgcn_readlane(cur.sw, kRsTag) != i + 1) {   // (not there yet when it was asked for)
     const long long t0_ = (long long)wall_clock64();
     // (a real call's result arrives in a vector register: say that it is uniform, or the loop gets exec-mask exits)
-    if (!__builtin_amdgcn_readfirstlane((int)run_wait_m((const int *)(rb + slot_off + kRunSc) + kRsTag, i + 1, abort_word, a.abort_flag, a.spin_ticks))) return false;
+    if (!__builtin_amdgcn_readfirstlane((int)run_wait((const int *)(rb + slot_off + kRunSc) + kRsTag, i + 1, abort_word, a.abort_flag, a.spin_ticks))) return false;
     run_request_m(rb + slot_off, lane, cur);
     if (a.stat && lane == 0) { atomicAdd(a.stat + 3 + 2 * (BACKWARD ? 1 : 0), 1ull); atomicAdd(a.stat + 4 + 2 * (BACKWARD ? 1 : 0), (unsigned long long)((long long)wall_clock64() - t0_)); }
   }
@@ -213,13 +415,13 @@ __device__ __forceinline__ bool run_visit_m(const RunArgsM &a, double *rb, int *
   if (cut) {
     // the rows the segment behind this node starts from: to the publisher
     const int ps = cut & 1;
-    if (__builtin_amdgcn_readfirstlane(lds_load(rw + kRwFree)) < cut - 2 &&
-        !__builtin_amdgcn_readfirstlane((int)run_wait_m(rw + kRwFree, cut - 2, abort_word, a.abort_flag, a.spin_ticks))) return false;
+    if (__builtin_amdgcn_readfirstlane(lds_load(rw + kSwFree)) < cut - 2 &&
+        !__builtin_amdgcn_readfirstlane((int)run_wait(rw + kSwFree, cut - 2, abort_word, a.abort_flag, a.spin_ticks))) return false;
     double *pb = rb + kRunPub + ps * 128;
     pb[lane] = A0; pb[64 + lane] = A1;
-    if (lane == 0) lds_store(rw + kRwKinds + ps, __builtin_amdgcn_readlane(sw, kRsPubKinds));
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (lane == 0) lds_store(rw + kRwPubM + ps, cut);
+    if (lane == 0) lds_store(rw + kSwKinds + ps, __builtin_amdgcn_readlane(sw, kRsPubKinds));
+    SPEC_RELEASE();
+    if (lane == 0) lds_store(rw + kSwPubM + 4 * ps, cut);
   }
   return true;
 }
@@ -247,15 +449,15 @@ __device__ __forceinline__ void run_messages_g(const RunArgsM &a, double *rb, in
 }
 
 template <bool BACKWARD>
-__device__ __attribute__((noinline)) void run_messages(const DevParams *pp, int rb_off_, int abort_off_) {
+__device__ __attribute__((noinline)) void run_messages(const DevParams *pp) {
   extern __shared__ __attribute__((aligned(16))) double run_lds[];
   constexpr int D = BACKWARD ? 1 : 0;
   RunArgsM a;
   a.K = uniform_value(pp->K); a.window = uniform_value(pp->window); a.c0 = uniform_value(pp->spec_c0[D]); a.c1 = uniform_value(pp->spec_c1[D]);
   a.lambda = uniform_value(pp->lambda); a.step = uniform_value(pp->uniform_step);
   a.abort_flag = uniform_value(pp->abort_flag); a.spin_ticks = uniform_value(pp->spin_ticks); a.stat = uniform_value(pp->spec_stat);
-  double *rb = run_lds + __builtin_amdgcn_readfirstlane(rb_off_);
-  int *abort_word = (int *)(run_lds + __builtin_amdgcn_readfirstlane(abort_off_)) + 1;
+  double *rb = run_lds + kRunBase;
+  int *abort_word = (int *)run_lds + kRunAbortInt;
   const int lane = threadIdx.x & (kWave - 1);
   // the window in groups of four entries (entries beyond it cost >= vTrunc bit for bit, finish_inputs checks the spacing);
   // windows of more than eight entries keep the plain schedule (spec_active, trws_plan.hip)
@@ -276,11 +478,11 @@ __device__ __forceinline__ void run_request_p(const double *sl, int lane, RunNod
   n.O0 = sl[kRunRowOUT + lane]; n.O1 = sl[kRunRowOUT + 64 + lane]; n.O2 = sl[kRunRowOUT + 128 + lane]; n.O3 = sl[kRunRowOUT + 192 + lane];
 }
 template <bool BACKWARD>
-__device__ __attribute__((noinline)) void run_labels(const DevParams *pp_, int rb_off_, int abort_off_) {
+__device__ __attribute__((noinline)) void run_labels(const DevParams *pp_) {
   extern __shared__ __attribute__((aligned(16))) double run_lds[];
   const DevParams p = uniform_params(pp_);
-  double *rb = run_lds + __builtin_amdgcn_readfirstlane(rb_off_);
-  int *abort_word = (int *)(run_lds + __builtin_amdgcn_readfirstlane(abort_off_)) + 1;
+  double *rb = run_lds + kRunBase;
+  int *abort_word = (int *)run_lds + kRunAbortInt;
   const int lane = threadIdx.x & (kWave - 1);
   const int c0 = p.spec_c0[BACKWARD ? 1 : 0], c1 = p.spec_c1[BACKWARD ? 1 : 0];
   const double inf = __builtin_huge_val();
@@ -296,7 +498,7 @@ __device__ __attribute__((noinline)) void run_labels(const DevParams *pp_, int r
   for (int i = c0; i < c1; ++i) {
     const double *sl = rb + ((i - c0) % kRunSlots) * kRunSlotDoubles;
     if (RLI(cur.sw, kRsTag) != i + 1) {
-      if (!run_wait(p, (const int *)(sl + kRunSc) + kRsTag, i + 1, abort_word)) return;
+      if (!run_wait_i<true>((const int *)(sl + kRunSc) + kRsTag, i + 1, abort_word, p.abort_flag, p.spin_ticks)) return;
       run_request_p(sl, lane, cur);
     }
     const int sw = cur.sw;
@@ -304,7 +506,7 @@ __device__ __attribute__((noinline)) void run_labels(const DevParams *pp_, int r
     const int nout = RLI(sw, kRsNout), nin = RLI(sw, kRsNin), md = RLI(sw, kRsMd), cut = RLI(sw, kRsCut);
     double db = act ? cur.TH : 0.0;
     const double o0 = cur.O0, o1 = cur.O1, o2 = cur.O2, o3 = cur.O3;
-    if (lane == 0) lds_store(rw + kRwConsP, i + 1 - c0);
+    if (lane == 0) lds_store(rw + kSwConsP, i + 1 - c0);
     if (i + 1 < c1) run_request_p(rb + ((i + 1 - c0) % kRunSlots) * kRunSlotDoubles, lane, nxt);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -326,10 +528,10 @@ __device__ __attribute__((noinline)) void run_labels(const DevParams *pp_, int r
     xprev = __builtin_ctzll(__builtin_amdgcn_ballot_w64(dim == vbest));
     if (cut) {
       const int ps = cut & 1;
-      if (!run_wait(p, rw + kRwFree, cut - 2, abort_word)) return;
-      if (lane == 0) { rw[kRwLabel + ps] = xprev; rw[kRwNode + ps] = RLI(sw, kRsNode); }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      if (lane == 0) lds_store(rw + kRwPubP + ps, cut);
+      if (!run_wait_i<true>(rw + kSwFree, cut - 2, abort_word, p.abort_flag, p.spin_ticks)) return;
+      if (lane == 0) { rw[kSwLabel + ps] = xprev; rw[kSwNode + ps] = RLI(sw, kRsNode); }
+      SPEC_RELEASE();
+      if (lane == 0) lds_store(rw + kSwPubP + ps, cut);
     }
     cur = nxt;
   }
@@ -337,11 +539,11 @@ __device__ __attribute__((noinline)) void run_labels(const DevParams *pp_, int r
 
 // ---- waves 2-9: staging ---------------------------------------------------------------------------------------------
 template <bool BACKWARD, bool PRIMAL, bool UPDATE>
-__device__ __attribute__((noinline)) void run_loader(const DevParams *pp_, int epoch_, int rb_off_, int abort_off_, int lw_) {
+__device__ __attribute__((noinline)) void run_loader(const DevParams *pp_, int epoch_, int lw_) {
   extern __shared__ __attribute__((aligned(16))) double run_lds[];
   const DevParams p = uniform_params(pp_);
-  double *rb = run_lds + __builtin_amdgcn_readfirstlane(rb_off_);
-  int *abort_word = (int *)(run_lds + __builtin_amdgcn_readfirstlane(abort_off_)) + 1;
+  double *rb = run_lds + kRunBase;
+  int *abort_word = (int *)run_lds + kRunAbortInt;
   const int lane = threadIdx.x & (kWave - 1);
   const int epoch = __builtin_amdgcn_readfirstlane(epoch_), lw = __builtin_amdgcn_readfirstlane(lw_);
   constexpr int D = BACKWARD ? 1 : 0;
@@ -422,8 +624,8 @@ __device__ __attribute__((noinline)) void run_loader(const DevParams *pp_, int e
     }
     // the ring slot: both recurrences have taken the node that had it into their registers
     double *sl = rb + ((i - c0) % kRunSlots) * kRunSlotDoubles;
-    if (UPDATE && !run_wait(p, rw + kRwConsM, i - c0 - kRunSlots + 1, abort_word)) return;
-    if (PRIMAL && !run_wait(p, rw + kRwConsP, i - c0 - kRunSlots + 1, abort_word)) return;
+    if (UPDATE && !run_wait_i<true>(rw + kRwConsM, i - c0 - kRunSlots + 1, abort_word, p.abort_flag, p.spin_ticks)) return;
+    if (PRIMAL && !run_wait_i<true>(rw + kSwConsP, i - c0 - kRunSlots + 1, abort_word, p.abort_flag, p.spin_ticks)) return;
     if (UPDATE) {
       double P = theta;
 #pragma unroll
@@ -472,153 +674,25 @@ __device__ __attribute__((noinline)) void run_loader(const DevParams *pp_, int e
       const double g = (double)1 / (double)(nout > nin ? nout : nin > 0 ? nin : 1);
       if (lane < 8) sl[kRunSc + 8 + lane] = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? g : ain;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    SPEC_RELEASE();
     if (lane == 0) lds_store((int *)(sl + kRunSc) + kRsTag, i + 1);
   }
 }
 
-// ---- wave 10: what a segment starts from, to global memory ------------------------------------------------------------
-template <bool PRIMAL, bool UPDATE>
-__device__ __attribute__((noinline)) void run_publisher(const DevParams *pp_, int epoch_, int rb_off_, int abort_off_) {
-  extern __shared__ __attribute__((aligned(16))) double run_lds[];
-  const DevParams p = uniform_params(pp_);
-  double *rb = run_lds + __builtin_amdgcn_readfirstlane(rb_off_);
-  int *abort_word = (int *)(run_lds + __builtin_amdgcn_readfirstlane(abort_off_)) + 1;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int epoch = __builtin_amdgcn_readfirstlane(epoch_);
-  const int K = p.K;
-  const int lk = lane < K ? lane : K - 1;
-  int *rw = (int *)(rb + kRunWords);
-  for (int s = 1; s < p.spec_nseg; ++s) {
-    const int ps = s & 1;
-    if (UPDATE) {
-      if (!run_wait(p, rw + kRwPubM + ps, s, abort_word)) return;
-      const double *pb = rb + kRunPub + ps * 128;
-      double a0 = pb[lk], a1 = pb[64 + lk];
-      const int kinds = lds_load(rw + kRwKinds + ps);
-      if ((p.debug & 16384) && s % 3 == 1 && lane == 0) a0 = __longlong_as_double(__double_as_longlong(a0) ^ 1ll);   // (development: a wrong row)
-      if ((p.debug & 65536) && s % 3 == 1 && (lane & 1)) a0 += 0.375;                                                // (development: a VERY wrong row)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int kd = (kinds >> (4 * k)) & 15;
-        if (kd) st_sc1(p.spec_rows + ((size_t)s * 8 + k) * K + lk, kd == 8 ? a0 : a1);
-      }
-    }
-    if (PRIMAL) {
-      if (!run_wait(p, rw + kRwPubP + ps, s, abort_word)) return;
-      int label = lds_load(rw + kRwLabel + ps);
-      const int node = lds_load(rw + kRwNode + ps);
-      if ((p.debug & 32768) && s % 5 == 2) label = label > 0 ? label - 1 : (K > 1 ? 1 : 0);                          // (development: a wrong label)
-      (void)node;
-      if (lane == 0) st_sc1(p.spec_x + s, label);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) { st_sc1(p.done + p.N + s, epoch); lds_store(rw + kRwFree, s); }
-  }
-}
-
-// (noinline, parameters through a pointer to their copy in global memory, LDS through the dynamic allocation's own
-//  symbol: nothing of this routine -- registers, scalars, the parameter block's address -- leaks into the kernel it is
-//  called from, whose visit loops sit at the register limits)
-template <bool BACKWARD, bool PRIMAL, bool UPDATE>
-__device__ __attribute__((noinline)) void chain_runner(const DevParams *pp_, int epoch_, int rb_off_, int abort_off_) {
-  extern __shared__ __attribute__((aligned(16))) double run_lds[];
-  const DevParams &p = *pp_;
-  const int epoch = epoch_, rb_off = rb_off_, abort_off = abort_off_;
-  double *rb = run_lds + rb_off;
-  int *abort_word = (int *)(run_lds + abort_off) + 1;
-  constexpr int D = BACKWARD ? 1 : 0;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-  const int c0 = p.spec_c0[D], c1 = p.spec_c1[D];
-  int *rw = (int *)(rb + kRunWords);
-  if (tid < 64) rw[tid] = 0;
-  if (tid < kRunSlots) ((int *)(rb + tid * kRunSlotDoubles + kRunSc))[kRsTag] = 0;   // (no node staged)
-  if (tid < 16) { rb[kRunTab + tid] = __builtin_huge_val(); rb[kRunTab + 80 + tid] = __builtin_huge_val(); }
-  if (p.timeline && tid == 0) p.timeline[((size_t)2 * p.tl_stride + D) * 2] = wall_clock64();
-  __syncthreads();
-  const unsigned long long trole0 = wall_clock64();
-  if (wave == 0) { if (UPDATE) { __builtin_amdgcn_s_setprio(3); run_messages<BACKWARD>(pp_, rb_off, abort_off_); __builtin_amdgcn_s_setprio(0); } }
-  else if (wave == 1) { if (PRIMAL) { __builtin_amdgcn_s_setprio(3); run_labels<BACKWARD>(pp_, rb_off, abort_off_); __builtin_amdgcn_s_setprio(0); } }
-  else if (wave < 2 + kRunLoaders) run_loader<BACKWARD, PRIMAL, UPDATE>(pp_, epoch, rb_off, abort_off_, wave - 2);
-  else if (wave == 2 + kRunLoaders) run_publisher<PRIMAL, UPDATE>(pp_, epoch, rb_off, abort_off_);
-  // (development: when each role was done, 100 MHz ticks since the roles started -- messages, labels, last loader, publisher)
-  if (p.timeline && p.spec_stat && lane == 0 && (wave <= 1 || wave == 1 + kRunLoaders || wave == 2 + kRunLoaders))
-    p.spec_stat[8 + 4 * D + (wave <= 1 ? wave : wave - kRunLoaders + 1)] = wall_clock64() - trole0;
-  __syncthreads();
-  if (p.timeline && tid == 0) p.timeline[((size_t)2 * p.tl_stride + D) * 2 + 1] = wall_clock64();
-  if (p.spec_stat && tid == 0) atomicAdd(p.spec_stat + 2, (unsigned long long)(c1 - c0));
-}
-
-// ---- commit of a speculative segment (called by all waves of the workgroup behind the barrier that ended the segment's
-// last visit: the storer has drained the last node's rows).  The segment in front commits first (its flag); then what
-// this segment started from is compared, bit for bit, with what that segment's last node really handed over: equal ->
-// every visit here saw the sequential sweep's inputs and the nodes' flags go up; different (the runner's plain min-plus
-// row was not the reference's envelope, or a row of the runner's was stale) -> the overwritten rows are put back and the
-// caller walks the visits again from the real rows.  Returns 0 committed, 1 walk again (ctl[3] set), 2 gave up.
-template <bool BACKWARD, bool PRIMAL, bool UPDATE>
-__device__ __attribute__((noinline)) int spec_commit(const DevParams *pp_, int epoch_, int p0_, int p1_, int seg_, int compare_) {
-  extern __shared__ __attribute__((aligned(16))) double run_lds[];
-  const DevParams &p = *pp_;
-  const int epoch = epoch_, p0 = p0_, p1 = p1_, seg = seg_, compare = compare_;
-  constexpr int D = BACKWARD ? 1 : 0;
-  constexpr int DW = TrwsGraph::kDescWords;
-  const int32_t *desc = p.desc[D];
-  int *ctl = (int *)(run_lds + kPipeCtlOff);
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-  const int K = p.K;
-  const int lkc = lane < K ? lane : K - 1;
-  if (compare) {
-    if (wave == 0) {
-      int differ = 0;
-      if (!wait_flag(p, p.N + p.spec_nseg + seg, epoch, -2)) { if (lane == 0) ctl[1] = 1; }
-      else {
-        const int w = desc[(size_t)p0 * DW + lane];
-        const int f = RLI(w, 2);
-        const int nout = f & 15, ntot = nout + ((f >> 4) & 15);
-        for (int j = nout; j < ntot; ++j) {
-          if (__builtin_amdgcn_readlane(w, 12 + j) < 0) continue;
-          if (UPDATE) {
-            const double a = ld_sc1(p.spec_rows + ((size_t)seg * 8 + j) * K + lkc);
-            const double b = ld_sc1(p.msg + (size_t)__builtin_amdgcn_readlane(w, 4 + j) * K + lkc);
-            differ |= UNI(__double_as_longlong(a) != __double_as_longlong(b)) ? 1 : 0;
-          }
-          if (PRIMAL) differ |= ld_sc1(p.spec_x + seg) != ld_sc1(p.x + __builtin_amdgcn_readlane(w, 32 + j)) ? 1 : 0;
-        }
-      }
-      if (lane == 0) ctl[2] = differ;
-    }
-    __syncthreads();
-    const int differ = __builtin_amdgcn_readfirstlane(ctl[2]);
-    const int gave_up = __builtin_amdgcn_readfirstlane(ctl[1]);
-    __syncthreads();
-    if (gave_up) return 2;
-    if (differ) {
-      if (UPDATE) {
-        for (int pos = p0 + wave; pos < p1; pos += kPipeWaves) {
-          const int w = desc[(size_t)pos * DW + lane];
-          const int nout = RLI(w, 2) & 15;
-          for (int j = 0; j < nout && j < 4; ++j)
-            st_sc1(p.msg + (size_t)__builtin_amdgcn_readlane(w, 4 + j) * K + lkc,
-                   ld_sc1(p.spec_undo + ((size_t)(seg * p.spec_max_len + (pos - p0)) * 4 + j) * K + lkc));
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");   // (the second walk's plain loads must not find this CU's L1 holding anything of the first)
-      }
-      if (tid == 0) { ctl[3] = 1; if (p.spec_stat) atomicAdd(p.spec_stat, 1ull); }
-      __syncthreads();
-      return 1;
-    }
-  }
-  if (wave == 0) {
-    // the segment behind first (the commits are a serial chain), then the nodes' own flags
-    if (seg + 1 < p.spec_nseg && lane == 0) st_sc1(p.done + p.N + p.spec_nseg + seg + 1, epoch);
-    for (int pos = p0 + lane; pos < p1; pos += kWave) st_sc1(p.done + desc[(size_t)pos * DW + 1], epoch);
-    if (lane == 0 && p.spec_stat) atomicAdd(p.spec_stat + 1, 1ull);
-  }
-  return 0;
-}
+// the narrow runner's layout and roles for chain_runner: wave 0 messages, wave 1 labels, waves 2-9 loaders, wave 10
+// publisher (wave 11 idle)
+struct PipeRunner {
+  static constexpr int C = 1, kBase = kRunBase, kAbortInt = kRunAbortInt, kSlots = kRunSlots, kSlotDoubles = kRunSlotDoubles,
+                       kSc = kRunSc, kTab = kRunTab, kTabs = 1, kPub = kRunPub, kWords = kRunWords, kMsgWaves = 1, kLoaders = kRunLoaders;
+  static constexpr bool kOverlay = false;
+  static __device__ __forceinline__ void prepare(const DevParams &, double *, int) {}
+  template <bool BACKWARD>
+  static __device__ __forceinline__ void messages(const DevParams *pp, int) { run_messages<BACKWARD>(pp); }
+  template <bool BACKWARD>
+  static __device__ __forceinline__ void labels(const DevParams *pp) { run_labels<BACKWARD>(pp); }
+  template <bool BACKWARD, bool PRIMAL, bool UPDATE>
+  static __device__ __forceinline__ void loader(const DevParams *pp, int epoch, int lw) { run_loader<BACKWARD, PRIMAL, UPDATE>(pp, epoch, lw); }
+};
 
 #undef RLI
 

@@ -241,82 +241,6 @@ __device__ __forceinline__ void wide_collect(const double *xd, int *flag, int se
   }
 }
 
-// The commit of a speculative segment (SPEC instantiation below; the protocol is trws_spec.h's spec_commit): called by all
-// waves behind the barrier that ended the segment's last visit.  The segment in front commits first (its flag); then what
-// this segment started from is compared, bit for bit, with what that segment's last node really handed over: equal ->
-// the nodes' flags go up; different -> the overwritten rows are put back and the caller walks the visits again from the
-// real rows.  Returns 0 committed, 1 walk again (ctl[3] set), 2 gave up.
-template <bool BACKWARD, bool PRIMAL, bool UPDATE>
-__device__ __attribute__((noinline)) int wide_spec_commit(const DevParams *pp_, int epoch_, int p0_, int p1_, int seg_, int compare_, int ctl_off_) {
-  extern __shared__ __attribute__((aligned(16))) double wc_lds[];
-  const DevParams &p = *pp_;
-  const int epoch = epoch_, p0 = p0_, p1 = p1_, seg = seg_, compare = compare_;
-  constexpr int D = BACKWARD ? 1 : 0;
-  constexpr int DW = TrwsGraph::kDescWords;
-  const int32_t *desc = p.desc[D];
-  int *ctl = (int *)wc_lds + ctl_off_;   // [1] abort, [3] walk again, [4] (the first exchange flag, idle here) the verdict
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-  const int K = p.K;
-  if (compare) {
-    if (wave == 0) {
-      int differ = 0;
-      if (!wait_flag(p, p.N + p.spec_nseg + seg, epoch, -2)) { if (lane == 0) ctl[1] = 1; }
-      else {
-        const int w = desc[(size_t)p0 * DW + lane];
-        const int f = WRLI(w, 2);
-        const int nout = f & 15, ntot = nout + ((f >> 4) & 15);
-        for (int j = nout; j < ntot; ++j) {
-          if (__builtin_amdgcn_readlane(w, 12 + j) < 0) continue;
-          if (UPDATE) {
-            const size_t ea = ((size_t)seg * 8 + j) * K, eb = (size_t)__builtin_amdgcn_readlane(w, 4 + j) * K;
-            for (int c = 0; c < 4; ++c) {
-              const int kk = c * kWave + lane, kc = kk < K ? kk : K - 1;
-              const double a = ld_sc1(p.spec_rows + ea + kc), b = ld_sc1(p.msg + eb + kc);
-              differ |= UNI(__double_as_longlong(a) != __double_as_longlong(b)) ? 1 : 0;
-            }
-          }
-          if (PRIMAL) differ |= ld_sc1(p.spec_x + seg) != ld_sc1(p.x + __builtin_amdgcn_readlane(w, 32 + j)) ? 1 : 0;
-        }
-      }
-      if (lane == 0) ctl[4] = differ;
-    }
-    __syncthreads();
-    const int differ = __builtin_amdgcn_readfirstlane(ctl[4]);
-    const int gave_up = __builtin_amdgcn_readfirstlane(ctl[1]);
-    __syncthreads();
-    if (tid == 0) ctl[4] = 0;
-    if (gave_up) return 2;
-    if (differ) {
-      if (UPDATE) {
-        for (int pos = p0 + wave; pos < p1; pos += kWideWaves) {
-          const int w = desc[(size_t)pos * DW + lane];
-          const int nout = WRLI(w, 2) & 15;
-          for (int j = 0; j < nout && j < 4; ++j) {
-            const size_t em = (size_t)__builtin_amdgcn_readlane(w, 4 + j) * K, eu = ((size_t)(seg * p.spec_max_len + (pos - p0)) * 4 + j) * K;
-            for (int c = 0; c < 4; ++c) {
-              const int kk = c * kWave + lane;
-              if (kk < K) st_sc1(p.msg + em + kk, ld_sc1(p.spec_undo + eu + kk));
-            }
-          }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");   // (the second walk's plain loads must not find this CU's L1 holding anything of the first)
-      }
-      if (tid == 0) { ctl[3] = 1; if (p.spec_stat) atomicAdd(p.spec_stat, 1ull); }
-      __syncthreads();
-      return 1;
-    }
-  }
-  if (wave == 0) {
-    // the segment behind first (the commits are a serial chain), then the nodes' own flags
-    if (seg + 1 < p.spec_nseg && lane == 0) st_sc1(p.done + p.N + p.spec_nseg + seg + 1, epoch);
-    for (int pos = p0 + lane; pos < p1; pos += kWave) st_sc1(p.done + desc[(size_t)pos * DW + 1], epoch);
-    if (lane == 0 && p.spec_stat) atomicAdd(p.spec_stat + 1, 1ull);
-  }
-  return 0;
-}
-
 // SPEC: the instantiation that knows the speculative schedule of the long serial run (trws_wspec.h; even K, linear kernel,
 // uniformly spaced positions): a kernel of its own, launched only when a plan's sweeps use it.
 template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SPEC = false>
@@ -332,15 +256,8 @@ __device__ __forceinline__ void wide_body(DevParams p, int epoch) {
   bool have_ticket = false;
   int first_ticket = 0;
   if (SPEC) {
-    int *ent = (int *)lds;
-    if (tid == 0) {
-      const int t_ = atomicAdd(p.ticket, 1);
-      ent[0] = t_ < p.ntickets[D] ? (p.run_order[D] ? p.run_order[D][t_] : t_) : p.nruns[D];
-    }
-    __syncthreads();
-    first_ticket = __builtin_amdgcn_readfirstlane(ent[0]);
-    __syncthreads();
-    if (first_ticket == -1) wide_chain_runner<BACKWARD, PRIMAL, UPDATE>(p.self, epoch);
+    first_ticket = draw_first_ticket<D>(p, (int *)lds);
+    if (first_ticket == -1) chain_runner<WideRunner, BACKWARD, PRIMAL, UPDATE>(p.self, epoch);
     else have_ticket = true;
   }
   const int K = p.K;
@@ -1376,8 +1293,9 @@ __device__ __forceinline__ void wide_body(DevParams p, int epoch) {
 #undef WIDE_VISITS_END
 #undef WIDE_VISITS_END_
     if (SPEC && seg >= 0) {
-      const int verdict = wide_spec_commit<BACKWARD, PRIMAL, UPDATE>(p.self, epoch, p0, p1, seg, spec_in ? 1 : 0, (int)(L.ctl - (int *)lds));
-      if (verdict == 2) { if (tid == 0) st_sc1(p.abort_flag, 1); return; }
+      // (verdict word: ctl[4], the first twin exchange flag, idle between visits)
+      const int verdict = spec_commit<4, kWideWaves, 4, BACKWARD, PRIMAL, UPDATE>(p.self, epoch, p0, p1, seg, spec_in ? 1 : 0, (int)(L.ctl - (int *)lds));
+      if (verdict == 2) return;
       if (verdict == 1) continue;   // (ctl[3] is set: the same run once more)
     }
     if (p.timeline && tid == 0) p.timeline[((size_t)D * p.tl_stride + run) * 2 + 1] = wall_clock64();

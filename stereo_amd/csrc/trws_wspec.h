@@ -21,6 +21,7 @@
 #include <cstdint>
 
 #include "trws_dev.h"
+#include "trws_spec.h"
 
 #define WRLI(v, i) __builtin_amdgcn_readlane((v), (i))
 
@@ -29,8 +30,7 @@ namespace {
 
 constexpr int kWrSlots = 6, kWrLoaders = 6, kWrMsg = 4;
 constexpr int kWrK = 256;   // row stride (labels)
-// a staged node (doubles): prefix sum P | up to three staged rows of the tail | old rows of the (up to two) messages to
-// compute | unary | the node's own (outgoing) rows | words
+// a staged node: the slot layout of trws_spec.h in rows of kWrK doubles
 constexpr int kWrRowP = 0, kWrRowS = kWrK, kWrRowM = 4 * kWrK, kWrRowTH = 6 * kWrK, kWrRowOUT = 7 * kWrK, kWrSc = 11 * kWrK;
 constexpr int kWrSlotDoubles = kWrSc + 16;
 constexpr int kWrTab = kWrSlots * kWrSlotDoubles;   // 2 tables of 16 + 256 + 16 doubles: H with +inf on both sides
@@ -40,101 +40,9 @@ constexpr int kWrPub = kWrPm + 16;                  // 2 x (2 rows): what the pu
 constexpr int kWrWords = kWrPub + 4 * kWrK;         // 64 ints
 constexpr int kWrPos = kWrWords + 32 + 32;          // (behind the words and the 64 words where lanes that have nothing to say store) the positions
 constexpr int kWrDoubles = kWrPos + kWrK;
-// words: labels consumed 13 | label published x 2: 16 | slots freed 18 | label x 2: 20 | node x 2: 22 | row kinds x 2: 24 |
-// rows published, per wave, x 2: 32-39 | arrival of the four message waves: 40-43 | nodes consumed by message wave w: 48-51
-constexpr int kWwConsP = 13, kWwPubP = 16, kWwFree = 18, kWwLabel = 20, kWwNode = 22, kWwKinds = 24, kWwPubM = 32, kWwArrive = 40, kWwConsM = 48;
-// words of a staged node: as in trws_spec.h (tail length | tail kinds | messages to compute | cut | kinds of the next
-// segment's first rows | n_out | incoming rows | their label x 4 | direction bits | node | TAG = position + 1, written last);
-// doubles 8-15: alpha x 2, gamma, alpha of the incoming rows x 4
-constexpr int kWsNt = 0, kWsKinds = 1, kWsNmsg = 2, kWsCut = 5, kWsPubKinds = 6, kWsNout = 7, kWsNin = 8, kWsSrc = 9, kWsMd = 13, kWsNode = 14, kWsTag = 15;
-
-// (words of the runner's LDS, addressed AS LDS: through a generic pointer these become flat accesses, whose completion is
-//  counted together with the global loads -- a loader that polls a word would wait for the rows it has just requested
-//  for its next node; the fences are LDS-only for the same reason)
-typedef __attribute__((address_space(3))) int wr_lds_int;
-__device__ __forceinline__ int wr_load(const int *w) { return __hip_atomic_load((const wr_lds_int *)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void wr_store(int *w, int v) { __hip_atomic_store((wr_lds_int *)w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-#define WR_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local")
-#define WR_RELEASE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local")
-
-template <class T>
-__device__ __forceinline__ T wr_uniform(T v) {
-  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "wr_uniform");
-  if (sizeof(T) == 4) {
-    int w;
-    __builtin_memcpy(&w, &v, 4);
-    w = __builtin_amdgcn_readfirstlane(w);
-    __builtin_memcpy(&v, &w, 4);
-  } else {
-    int w[2];
-    __builtin_memcpy(w, &v, 8);
-    w[0] = __builtin_amdgcn_readfirstlane(w[0]); w[1] = __builtin_amdgcn_readfirstlane(w[1]);
-    __builtin_memcpy(&v, w, 8);
-  }
-  return v;
-}
-__device__ __forceinline__ DevParams wr_params(const DevParams *pp) {
-  DevParams q;
-#define U(f) q.f = wr_uniform(pp->f)
-  U(K); U(lambda); U(unary); U(msg); U(pos); U(alpha); U(x); U(done); U(abort_flag); U(spin_ticks); U(n_own); U(N);
-  U(desc[0]); U(desc[1]); U(window); U(uniform_step); U(spec_c0[0]); U(spec_c0[1]); U(spec_c1[0]); U(spec_c1[1]);
-  U(spec_len); U(spec_nseg); U(spec_max_len); U(spec_rows); U(spec_x); U(spec_undo); U(spec_stat); U(timeline); U(tl_stride); U(debug);
-#undef U
-  return q;
-}
-
-// Waits until *word >= want (words of the runner's own LDS).  What a role of the runner waits for ends, in the last
-// instance, with a loader's wait for another workgroup, which is bounded by the wall clock and raises the abort word.
-__device__ __attribute__((noinline)) bool wr_wait(const int *word, int want, int *abort_word, int32_t *abort_flag, long long spin_ticks) {
-  int spins = 0;
-  long long t0 = 0;
-  while (wr_load(word) < want) {
-    __builtin_amdgcn_s_sleep(1);
-    spins = (spins + 1) & 1023;
-    if (spins != 0) continue;
-    if (wr_load(abort_word) || ld_sc1(abort_flag)) return false;
-    const long long now = (long long)wall_clock64();
-    if (t0 == 0) { t0 = now | 1; continue; }
-    if (now - t0 > 4 * spin_ticks) { wr_store(abort_word, 1); return false; }
-  }
-  WR_ACQUIRE();
-  return true;
-}
-// (the same, inlined: a call inside a loader's turn makes it spill the rows it holds in registers around the call)
-__device__ __forceinline__ bool wr_wait_i(const int *word, int want, int *abort_word, int32_t *abort_flag, long long spin_ticks) {
-  int spins = 0;
-  long long t0 = 0;
-  while (wr_load(word) < want) {
-    spins = (spins + 1) & 4095;
-    if (spins != 0) continue;
-    if (wr_load(abort_word) || ld_sc1(abort_flag)) return false;
-    const long long now = (long long)wall_clock64();
-    if (t0 == 0) { t0 = now | 1; continue; }
-    if (now - t0 > 4 * spin_ticks) { wr_store(abort_word, 1); return false; }
-  }
-  WR_ACQUIRE();
-  return true;
-}
-// ... until all four of words[0 .. 3] >= want (16-byte aligned: the four words come with ONE LDS read per look)
-__device__ __forceinline__ bool wr_wait4(const int *words, int want, int *abort_word, int32_t *abort_flag, long long spin_ticks) {
-  typedef int wr_v4i __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) const volatile wr_v4i wr_lds_v4i;
-  int spins = 0;
-  long long t0 = 0;
-  for (;;) {
-    const wr_v4i v = *(wr_lds_v4i *)words;
-    const int lo = min(min(v.x, v.y), min(v.z, v.w));
-    if (lo >= want) break;
-    spins = (spins + 1) & 4095;
-    if (spins != 0) continue;
-    if (wr_load(abort_word) || ld_sc1(abort_flag)) return false;
-    const long long now = (long long)wall_clock64();
-    if (t0 == 0) { t0 = now | 1; continue; }
-    if (now - t0 > 4 * spin_ticks) { wr_store(abort_word, 1); return false; }
-  }
-  WR_ACQUIRE();
-  return true;
-}
+// words beyond trws_spec.h's: arrival of the four message waves: 40-43 | nodes consumed by message wave w: 48-51
+constexpr int kWwArrive = 40, kWwConsM = 48;
+constexpr int kWrAbortInt = 2 * (kWrWords + 31);   // (the last double of the words)
 
 // ---- waves 0-3: the message recurrence, 64 labels each -----------------------------------------------------------------
 struct WrNodeM {
@@ -159,9 +67,9 @@ struct WrArgsM {
 // The four waves meet: everybody's table entries and partial minimum are written, then read.  `seq` counts the meetings.
 __device__ __forceinline__ bool wr_meet(int *rw, int wv, int lane, int seq, int *abort_word, const WrArgsM &a, int dir) {
   const long long t0_ = a.stat ? (long long)wall_clock64() : 0;
-  WR_RELEASE();
-  if (lane == 0) wr_store(rw + kWwArrive + wv, seq);
-  const bool ok = wr_wait4(rw + kWwArrive, seq, abort_word, a.abort_flag, a.spin_ticks);
+  SPEC_RELEASE();
+  if (lane == 0) lds_store(rw + kWwArrive + wv, seq);
+  const bool ok = run_wait_n<4>(rw + kWwArrive, seq, abort_word, a.abort_flag, a.spin_ticks);
   if (a.stat && wv == 0 && lane == 0) atomicAdd(a.stat + 16 + dir, (unsigned long long)((long long)wall_clock64() - t0_));
   return ok;
 }
@@ -183,14 +91,14 @@ __device__ __forceinline__ void wr_messages_g(const WrArgsM &a, double *rb, int 
   nxt = cur;
   int slot_off = 0, seq = 0, tsel = 0, nsel = 0;
   for (int i = a.c0; i < a.c1; ++i) {
-    if (__builtin_amdgcn_readlane(cur.sw, kWsTag) != i + 1) {   // (not there yet when it was asked for)
+    if (__builtin_amdgcn_readlane(cur.sw, kRsTag) != i + 1) {   // (not there yet when it was asked for)
       const long long t0_ = (long long)wall_clock64();
-      if (!__builtin_amdgcn_readfirstlane((int)wr_wait((const int *)(rb + slot_off + kWrSc) + kWsTag, i + 1, abort_word, a.abort_flag, a.spin_ticks))) return;
+      if (!__builtin_amdgcn_readfirstlane((int)run_wait((const int *)(rb + slot_off + kWrSc) + kRsTag, i + 1, abort_word, a.abort_flag, a.spin_ticks))) return;
       wr_request_m(rb + slot_off, lane, k, cur);
       if (a.stat && wv == 0 && lane == 0) { atomicAdd(a.stat + 3 + 2 * (BACKWARD ? 1 : 0), 1ull); atomicAdd(a.stat + 4 + 2 * (BACKWARD ? 1 : 0), (unsigned long long)((long long)wall_clock64() - t0_)); }
     }
     const int sw = cur.sw;
-    const int key = __builtin_amdgcn_readlane(sw, kWsKinds), nmsg = __builtin_amdgcn_readlane(sw, kWsNmsg), cut = __builtin_amdgcn_readlane(sw, kWsCut);
+    const int key = __builtin_amdgcn_readlane(sw, kRsKinds), nmsg = __builtin_amdgcn_readlane(sw, kRsNmsg), cut = __builtin_amdgcn_readlane(sw, kRsCut);
     double Di = cur.P;
     // the tail of the node's list from the first handed-over row on, in list order (the order of the reference's additions)
     if (key == 0x20098) { Di += A0; Di += A1; }
@@ -206,7 +114,7 @@ __device__ __forceinline__ void wr_messages_g(const WrArgsM &a, double *rb, int 
     }
     const double sd = cur.sd, mold0 = cur.M0, mold1 = cur.M1;
     // this node's words and rows are in registers: its place in the ring is free for this wave, the next node's are asked for
-    wr_store(cons_word, i + 1 - a.c0);
+    lds_store(cons_word, i + 1 - a.c0);
     slot_off += kWrSlotDoubles;
     if (slot_off == kWrSlots * kWrSlotDoubles) slot_off = 0;
     if (i + 1 < a.c1) wr_request_m(rb + slot_off, lane, k, nxt);
@@ -252,28 +160,28 @@ __device__ __forceinline__ void wr_messages_g(const WrArgsM &a, double *rb, int 
     if (cut) {
       // the rows the segment behind this node starts from: to the publisher
       const int ps = cut & 1;
-      if (__builtin_amdgcn_readfirstlane(wr_load(rw + kWwFree)) < cut - 2 &&
-          !__builtin_amdgcn_readfirstlane((int)wr_wait(rw + kWwFree, cut - 2, abort_word, a.abort_flag, a.spin_ticks))) return;
+      if (__builtin_amdgcn_readfirstlane(lds_load(rw + kSwFree)) < cut - 2 &&
+          !__builtin_amdgcn_readfirstlane((int)run_wait(rw + kSwFree, cut - 2, abort_word, a.abort_flag, a.spin_ticks))) return;
       double *pb = rb + kWrPub + ps * 2 * kWrK;
       pb[k] = A0; pb[kWrK + k] = A1;
-      if (wv == 0 && lane == 0) wr_store(rw + kWwKinds + ps, __builtin_amdgcn_readlane(sw, kWsPubKinds));
-      WR_RELEASE();
-      if (lane == 0) wr_store(rw + kWwPubM + 4 * ps + wv, cut);
+      if (wv == 0 && lane == 0) lds_store(rw + kSwKinds + ps, __builtin_amdgcn_readlane(sw, kRsPubKinds));
+      SPEC_RELEASE();
+      if (lane == 0) lds_store(rw + kSwPubM + 4 * ps + wv, cut);
     }
     cur = nxt;
   }
 }
 
 template <bool BACKWARD>
-__device__ __attribute__((noinline)) void wr_messages(const DevParams *pp, int wv_, int abort_off_) {
+__device__ __attribute__((noinline)) void wr_messages(const DevParams *pp, int wv_) {
   extern __shared__ __attribute__((aligned(16))) double wr_lds[];
   constexpr int D = BACKWARD ? 1 : 0;
   WrArgsM a;
-  a.K = wr_uniform(pp->K); a.c0 = wr_uniform(pp->spec_c0[D]); a.c1 = wr_uniform(pp->spec_c1[D]);
-  a.lambda = wr_uniform(pp->lambda); a.step = wr_uniform(pp->uniform_step);
-  a.abort_flag = wr_uniform(pp->abort_flag); a.spin_ticks = wr_uniform(pp->spin_ticks); a.stat = wr_uniform(pp->timeline) ? wr_uniform(pp->spec_stat) : nullptr;   // (development counters: with STEREO_HIP_TRWS_TIMELINE only)
-  const int window = wr_uniform(pp->window);
-  int *abort_word = (int *)(wr_lds + __builtin_amdgcn_readfirstlane(abort_off_));
+  a.K = uniform_value(pp->K); a.c0 = uniform_value(pp->spec_c0[D]); a.c1 = uniform_value(pp->spec_c1[D]);
+  a.lambda = uniform_value(pp->lambda); a.step = uniform_value(pp->uniform_step);
+  a.abort_flag = uniform_value(pp->abort_flag); a.spin_ticks = uniform_value(pp->spin_ticks); a.stat = uniform_value(pp->timeline) ? uniform_value(pp->spec_stat) : nullptr;   // (development counters: with STEREO_HIP_TRWS_TIMELINE only)
+  const int window = uniform_value(pp->window);
+  int *abort_word = (int *)wr_lds + kWrAbortInt;
   const int lane = threadIdx.x & (kWave - 1), wv = __builtin_amdgcn_readfirstlane(wv_);
   if (window <= 4) wr_messages_g<BACKWARD, 1>(a, wr_lds, lane, wv, abort_word);
   else wr_messages_g<BACKWARD, 2>(a, wr_lds, lane, wv, abort_word);
@@ -281,11 +189,11 @@ __device__ __attribute__((noinline)) void wr_messages(const DevParams *pp, int w
 
 // ---- wave 4: the labels of the primal pass (minimize.cpp:223-264, as the primal wave of a visit computes them) ------
 template <bool BACKWARD>
-__device__ __attribute__((noinline)) void wr_labels(const DevParams *pp_, int abort_off_) {
+__device__ __attribute__((noinline)) void wr_labels(const DevParams *pp_) {
   extern __shared__ __attribute__((aligned(16))) double wr_lds[];
-  const DevParams p = wr_params(pp_);
+  const DevParams p = uniform_params(pp_);
   double *rb = wr_lds;
-  int *abort_word = (int *)(wr_lds + __builtin_amdgcn_readfirstlane(abort_off_));
+  int *abort_word = (int *)wr_lds + kWrAbortInt;
   const int lane = threadIdx.x & (kWave - 1);
   const int c0 = p.spec_c0[BACKWARD ? 1 : 0], c1 = p.spec_c1[BACKWARD ? 1 : 0];
   const double inf = __builtin_huge_val();
@@ -301,13 +209,13 @@ __device__ __attribute__((noinline)) void wr_labels(const DevParams *pp_, int ab
     const double *sl = rb + ((i - c0) % kWrSlots) * kWrSlotDoubles;
     {
       const long long t0_ = (p.timeline && p.spec_stat) ? (long long)wall_clock64() : 0;
-      if (!wr_wait_i((const int *)(sl + kWrSc) + kWsTag, i + 1, abort_word, p.abort_flag, p.spin_ticks)) return;
+      if (!run_wait_i<false>((const int *)(sl + kWrSc) + kRsTag, i + 1, abort_word, p.abort_flag, p.spin_ticks)) return;
       if (p.timeline && p.spec_stat && lane == 0) atomicAdd(p.spec_stat + 18, (unsigned long long)((long long)wall_clock64() - t0_));
     }
     const int sw = ((const int *)(sl + kWrSc))[lane & 15];
     const double sd = sl[kWrSc + 8 + (lane & 7)];
-    const int nout = __builtin_amdgcn_readlane(sw, kWsNout), nin = __builtin_amdgcn_readlane(sw, kWsNin), md = __builtin_amdgcn_readlane(sw, kWsMd),
-              cut = __builtin_amdgcn_readlane(sw, kWsCut);
+    const int nout = __builtin_amdgcn_readlane(sw, kRsNout), nin = __builtin_amdgcn_readlane(sw, kRsNin), md = __builtin_amdgcn_readlane(sw, kRsMd),
+              cut = __builtin_amdgcn_readlane(sw, kRsCut);
     double db[4], o[4][4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -316,11 +224,11 @@ __device__ __attribute__((noinline)) void wr_labels(const DevParams *pp_, int ab
       for (int j = 0; j < 4; ++j) o[j][c] = sl[kWrRowOUT + j * kWrK + c * kWave + lane];
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane == 0) wr_store(rw + kWwConsP, i + 1 - c0);
+    if (lane == 0) lds_store(rw + kSwConsP, i + 1 - c0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (j < nin) {
-        const int src = __builtin_amdgcn_readlane(sw, kWsSrc + j);
+        const int src = __builtin_amdgcn_readlane(sw, kRsSrc + j);
         const int ks = src < 0 ? xprev : src;
         const double pks = rb[kWrPos + ks];
         const double aj = readlane_f64(sd, 3 + j);
@@ -352,21 +260,21 @@ __device__ __attribute__((noinline)) void wr_labels(const DevParams *pp_, int ab
     xprev = bi;
     if (cut) {
       const int ps = cut & 1;
-      if (!wr_wait(rw + kWwFree, cut - 2, abort_word, p.abort_flag, p.spin_ticks)) return;
-      if (lane == 0) { rw[kWwLabel + ps] = xprev; rw[kWwNode + ps] = __builtin_amdgcn_readlane(sw, kWsNode); }
-      WR_RELEASE();
-      if (lane == 0) wr_store(rw + kWwPubP + ps, cut);
+      if (!run_wait(rw + kSwFree, cut - 2, abort_word, p.abort_flag, p.spin_ticks)) return;
+      if (lane == 0) { rw[kSwLabel + ps] = xprev; rw[kSwNode + ps] = __builtin_amdgcn_readlane(sw, kRsNode); }
+      SPEC_RELEASE();
+      if (lane == 0) lds_store(rw + kSwPubP + ps, cut);
     }
   }
 }
 
 // ---- waves 5-10: staging -------------------------------------------------------------------------------------------------
 template <bool BACKWARD, bool PRIMAL, bool UPDATE>
-__device__ __attribute__((noinline)) void wr_loader(const DevParams *pp_, int epoch_, int abort_off_, int lw_) {
+__device__ __attribute__((noinline)) void wr_loader(const DevParams *pp_, int epoch_, int lw_) {
   extern __shared__ __attribute__((aligned(16))) double wr_lds[];
-  const DevParams p = wr_params(pp_);
+  const DevParams p = uniform_params(pp_);
   double *rb = wr_lds;
-  int *abort_word = (int *)(wr_lds + __builtin_amdgcn_readfirstlane(abort_off_));
+  int *abort_word = (int *)wr_lds + kWrAbortInt;
   const int lane = threadIdx.x & (kWave - 1);
   const int epoch = __builtin_amdgcn_readfirstlane(epoch_), lw = __builtin_amdgcn_readfirstlane(lw_);
   constexpr int D = BACKWARD ? 1 : 0;
@@ -470,7 +378,7 @@ __device__ __attribute__((noinline)) void wr_loader(const DevParams *pp_, int ep
     }
     // foreign dependencies (everything but the node in front), then their rows and labels
     if (ndep > 0) wait_for_dependencies_w(p, ndep, __shfl(w, 20 + (lane & 3), kWave), WRLI(w, 1), epoch, lane, abort_word);
-    if (wr_load(abort_word)) return;
+    if (lds_load(abort_word)) return;
     int src = -1;   // lane k < nin: the label the k-th incoming row's pairwise term takes (-1: the node in front)
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -486,8 +394,8 @@ __device__ __attribute__((noinline)) void wr_loader(const DevParams *pp_, int ep
     // the ring slot: all recurrences have taken the node that had it into their registers
     const int need = i - c0 - kWrSlots + 1;
     const long long tl1_ = (p.timeline && p.spec_stat && lw == 0) ? (long long)wall_clock64() : 0;
-    if (UPDATE && need > 0 && !wr_wait4(rw + kWwConsM, need, abort_word, p.abort_flag, p.spin_ticks)) return;
-    if (PRIMAL && need > 0 && !wr_wait_i(rw + kWwConsP, need, abort_word, p.abort_flag, p.spin_ticks)) return;
+    if (UPDATE && need > 0 && !run_wait_n<4>(rw + kWwConsM, need, abort_word, p.abort_flag, p.spin_ticks)) return;
+    if (PRIMAL && need > 0 && !run_wait_i<false>(rw + kSwConsP, need, abort_word, p.abort_flag, p.spin_ticks)) return;
     const long long tl2_ = (p.timeline && p.spec_stat && lw == 0) ? (long long)wall_clock64() : 0;
     // (a row picked by a uniform index: one scalar branch tree per row instead of a select per candidate and chunk)
 #define WR_GET(KSEL, DST)                                                                         \
@@ -554,18 +462,18 @@ __device__ __attribute__((noinline)) void wr_loader(const DevParams *pp_, int ep
 #undef WR_GET
     {
       int word = 0;
-      word = lane == kWsNt ? nt : lane == kWsKinds ? (kinds | (nt << 16)) : lane == kWsNmsg ? nmsg : lane == kWsCut ? cut
-           : lane == kWsPubKinds ? pubkinds : lane == kWsNout ? nout : lane == kWsNin ? nin : lane == kWsMd ? (md >> nout) : lane == kWsNode ? WRLI(w, 0) : 0;
-      const int srck = __shfl(src, lane - kWsSrc, kWave);
-      if (lane >= kWsSrc && lane < kWsSrc + 4) word = srck;
-      if (lane < kWsTag) ((int *)(sl + kWrSc))[lane] = word;
+      word = lane == kRsNt ? nt : lane == kRsKinds ? (kinds | (nt << 16)) : lane == kRsNmsg ? nmsg : lane == kRsCut ? cut
+           : lane == kRsPubKinds ? pubkinds : lane == kRsNout ? nout : lane == kRsNin ? nin : lane == kRsMd ? (md >> nout) : lane == kRsNode ? WRLI(w, 0) : 0;
+      const int srck = __shfl(src, lane - kRsSrc, kWave);
+      if (lane >= kRsSrc && lane < kRsSrc + 4) word = srck;
+      if (lane < kRsTag) ((int *)(sl + kWrSc))[lane] = word;
       const double a0 = readlane_f64(av, s0 < 0 ? 0 : s0), a1 = readlane_f64(av, s1 < 0 ? (s0 < 0 ? 0 : s0) : s1);
       const double ain = __shfl(av, nout + (lane - 3 < 0 ? 0 : lane - 3), kWave);
       const double g = (double)1 / (double)(nout > nin ? nout : nin > 0 ? nin : 1);
       if (lane < 8) sl[kWrSc + 8 + lane] = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? g : ain;
     }
-    WR_RELEASE();
-    if (lane == 0) wr_store((int *)(sl + kWrSc) + kWsTag, i + 1);
+    SPEC_RELEASE();
+    if (lane == 0) lds_store((int *)(sl + kWrSc) + kRsTag, i + 1);
     if (p.timeline && p.spec_stat && lw == 0 && lane == 0) {
       const long long tl3_ = (long long)wall_clock64();
       atomicAdd(p.spec_stat + 21 + D, (unsigned long long)(tl1_ - tl0_)); atomicAdd(p.spec_stat + 19 + D, (unsigned long long)(tl2_ - tl1_));
@@ -575,87 +483,23 @@ __device__ __attribute__((noinline)) void wr_loader(const DevParams *pp_, int ep
 #undef WR_REQUEST_OWN
 }
 
-// ---- wave 11: what a segment starts from, to global memory ------------------------------------------------------------
-template <bool PRIMAL, bool UPDATE>
-__device__ __attribute__((noinline)) void wr_publisher(const DevParams *pp_, int epoch_, int abort_off_) {
-  extern __shared__ __attribute__((aligned(16))) double wr_lds[];
-  const DevParams p = wr_params(pp_);
-  double *rb = wr_lds;
-  int *abort_word = (int *)(wr_lds + __builtin_amdgcn_readfirstlane(abort_off_));
-  const int lane = threadIdx.x & (kWave - 1);
-  const int epoch = __builtin_amdgcn_readfirstlane(epoch_);
-  const int K = p.K;
-  int *rw = (int *)(rb + kWrWords);
-  for (int s = 1; s < p.spec_nseg; ++s) {
-    const int ps = s & 1;
-    if (UPDATE) {
-      if (!wr_wait4(rw + kWwPubM + 4 * ps, s, abort_word, p.abort_flag, p.spin_ticks)) return;
-      const double *pb = rb + kWrPub + ps * 2 * kWrK;
-      const int kinds = wr_load(rw + kWwKinds + ps);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int kk = c * kWave + lane;
-        if (kk < K) {
-          double a0 = pb[kk], a1 = pb[kWrK + kk];
-          if ((p.debug & 16384) && s % 3 == 1 && kk == 0) a0 = __longlong_as_double(__double_as_longlong(a0) ^ 1ll);   // (development: a wrong row)
-          if ((p.debug & 65536) && s % 3 == 1 && (kk & 1)) a0 += 0.375;                                                // (development: a VERY wrong row)
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const int kd = (kinds >> (4 * k)) & 15;
-            if (kd) st_sc1(p.spec_rows + ((size_t)s * 8 + k) * K + kk, kd == 8 ? a0 : a1);
-          }
-        }
-      }
-    }
-    if (PRIMAL) {
-      if (!wr_wait(rw + kWwPubP + ps, s, abort_word, p.abort_flag, p.spin_ticks)) return;
-      int label = wr_load(rw + kWwLabel + ps);
-      if ((p.debug & 32768) && s % 5 == 2) label = label > 0 ? label - 1 : (K > 1 ? 1 : 0);                          // (development: a wrong label)
-      if (lane == 0) st_sc1(p.spec_x + s, label);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) { st_sc1(p.done + p.N + s, epoch); wr_store(rw + kWwFree, s); }
+// the wide runner's layout and roles for chain_runner (trws_spec.h): waves 0-3 messages, wave 4 labels, waves 5-10
+// loaders, wave 11 publisher; the positions go to LDS first
+struct WideRunner {
+  static constexpr int C = 4, kBase = 0, kAbortInt = kWrAbortInt, kSlots = kWrSlots, kSlotDoubles = kWrSlotDoubles, kSc = kWrSc,
+                       kTab = kWrTab, kTabs = 2, kPub = kWrPub, kWords = kWrWords, kMsgWaves = kWrMsg, kLoaders = kWrLoaders;
+  static constexpr bool kOverlay = true;
+  static __device__ __forceinline__ void prepare(const DevParams &p, double *rb, int tid) {
+    for (int k = tid; k < kWrK; k += (int)blockDim.x) rb[kWrPos + k] = k < p.K ? p.pos[k] : 0.0;
   }
-}
-
-// (noinline, parameters through a pointer to their copy in global memory: nothing of this routine leaks into the kernel
-//  it is called from; called at kernel entry, where only the kernel arguments are live)
-template <bool BACKWARD, bool PRIMAL, bool UPDATE>
-__device__ __attribute__((noinline)) void wide_chain_runner(const DevParams *pp_, int epoch_) {
-  extern __shared__ __attribute__((aligned(16))) double wr_lds[];
-  const DevParams &p = *pp_;
-  const int epoch = epoch_;
-  double *rb = wr_lds;
-  constexpr int abort_off = kWrWords + 31;   // (the last double of the words: [0] abort)
-  int *abort_word = (int *)(wr_lds + abort_off);
-  constexpr int D = BACKWARD ? 1 : 0;
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-  const int c0 = p.spec_c0[D], c1 = p.spec_c1[D];
-  int *rw = (int *)(rb + kWrWords);
-  if (tid < 64) rw[tid] = 0;
-  if (tid < kWrSlots) ((int *)(rb + tid * kWrSlotDoubles + kWrSc))[kWsTag] = 0;   // (no node staged)
-  if (tid < 64) {   // +inf on both sides of both tables
-    const int t = tid >> 5, e = tid & 31;
-    rb[kWrTab + t * kWrTabDoubles + (e < 16 ? e : kWrK + e)] = __builtin_huge_val();
-  }
-  for (int k = tid; k < kWrK; k += (int)blockDim.x) rb[kWrPos + k] = k < p.K ? p.pos[k] : 0.0;
-  if (p.timeline && tid == 0) p.timeline[((size_t)2 * p.tl_stride + D) * 2] = wall_clock64();
-  __syncthreads();
-  const unsigned long long trole0 = wall_clock64();
-  if (wave < kWrMsg) { if (UPDATE) { __builtin_amdgcn_s_setprio(3); wr_messages<BACKWARD>(pp_, wave, abort_off); __builtin_amdgcn_s_setprio(0); } }
-  else if (wave == kWrMsg) { if (PRIMAL) { __builtin_amdgcn_s_setprio(3); wr_labels<BACKWARD>(pp_, abort_off); __builtin_amdgcn_s_setprio(0); } }
-  else if (wave < kWrMsg + 1 + kWrLoaders) wr_loader<BACKWARD, PRIMAL, UPDATE>(pp_, epoch, abort_off, wave - kWrMsg - 1);
-  else wr_publisher<PRIMAL, UPDATE>(pp_, epoch, abort_off);
-  // (development: when each role was done, 100 MHz ticks since the roles started -- messages, labels, last loader, publisher)
-  if (p.timeline && p.spec_stat && (tid & (kWave - 1)) == 0 && (wave == 0 || wave == kWrMsg || wave == kWrMsg + kWrLoaders || wave == kWrMsg + 1 + kWrLoaders))
-    p.spec_stat[8 + 4 * D + (wave == 0 ? 0 : wave == kWrMsg ? 1 : wave == kWrMsg + kWrLoaders ? 2 : 3)] = wall_clock64() - trole0;
-  __syncthreads();
-  if (wr_load(abort_word) && tid == 0) st_sc1(p.abort_flag, 1);
-  if (p.timeline && tid == 0) p.timeline[((size_t)2 * p.tl_stride + D) * 2 + 1] = wall_clock64();
-  if (p.spec_stat && tid == 0) atomicAdd(p.spec_stat + 2, (unsigned long long)(c1 - c0));
-  __syncthreads();
-}
+  template <bool BACKWARD>
+  static __device__ __forceinline__ void messages(const DevParams *pp, int wave) { wr_messages<BACKWARD>(pp, wave); }
+  template <bool BACKWARD>
+  static __device__ __forceinline__ void labels(const DevParams *pp) { wr_labels<BACKWARD>(pp); }
+  template <bool BACKWARD, bool PRIMAL, bool UPDATE>
+  static __device__ __forceinline__ void loader(const DevParams *pp, int epoch, int lw) { wr_loader<BACKWARD, PRIMAL, UPDATE>(pp, epoch, lw); }
+};
+static_assert(kWrTabDoubles == kWrK + 32, "chain_runner's table stride");
 
 }  // namespace
 }  // namespace stereo
