@@ -82,6 +82,17 @@ int stereo_trws(int kernel, const double *unary, const uint32_t *conn, const dou
                 double *energy, double *lower_bound, double *iterations, char *err,
                 size_t errcap);
 void stereo_trws_cache_clear(void);
+/* Same solve, plus each node's min-marginals and confidence (definition: stereo_trws_plan_keep_min_marginals).
+ * No reference counterpart (trws_mex returns four outputs; mex/trws_minmarginals_mex.cpp is the six-output gateway).
+ * min_marginals K x N, confidence N; either may be NULL.  Labels, energy, bound and iterations are stereo_trws's bits.
+ * Always ONE plan, also with STEREO_HIP_GPUS >= 2 (strips give the same bits; per-strip beliefs are not supported):
+ * cached strips of the same problem are replaced by a single plan.  The flag is a runtime setting of the cached plan:
+ * a later plain stereo_trws call on it runs with the flag off and pays nothing.  Extra device memory 8 K N bytes. */
+int stereo_trws_min_marginals(int kernel, const double *unary, const uint32_t *conn, const double *q,
+                              const double *qprim, const double *alphas, double tol, double maxiter,
+                              double max_relgap, int K, int64_t N, int64_t E, double *labelling,
+                              double *energy, double *lower_bound, double *iterations,
+                              double *min_marginals, double *confidence, char *err, size_t errcap);
 
 
 /* Device-resident form of the same solver: graph analysis (SetAutomaticOrdering,
@@ -191,6 +202,31 @@ int stereo_trws_messages(int kernel, int K, int64_t M, const double *Di, const d
  * 5 large-label kernel (512 < K <= 4096, shared strictly ascending positions, any graph, both modes).
  * All give identical results.  Negative on a NULL plan. */
 int stereo_trws_plan_path(stereo_trws_plan *plan);
+
+/* ---- node beliefs: min-marginals, confidence, argmin ------------------------------ *
+ * No reference counterpart as an output.  After a run whose last finished iteration is t (the iterations
+ * reported), the belief of node i is the Di that MRFEnergy's forward pass of iteration t + 1 forms at i
+ * (minimize.cpp:38-46): D_i + the messages of firstForward(i) + those of firstBackward(i), in list order --
+ * the vector the plan's fused launch used to send i's forward messages.  One message state at rest never
+ * holds all of them (each edge stores one message and its direction flips every sweep), so with the flag on
+ * every iteration runs one extra kernel between the backward sweep and the fused forward sweep
+ * (P_i = D_i + firstForward messages; 8 K N bytes of device memory, about 8 K (2 N + E) bytes of traffic),
+ * and the read adds the firstBackward messages.  Bit-identical to t iterations of minimize.cpp plus one forward
+ * pass on the CPU.  Flag off (the default): no extra launch, no extra memory.  Strip plans refuse it.
+ * on = 0 frees the buffer.  Fails cleanly if the buffer cannot be allocated. */
+int stereo_trws_plan_keep_min_marginals(stereo_trws_plan *plan, int on, char *err, size_t errcap);
+/* Outputs of the last run, node-id order: min_marginals K x N (label fastest) = Di - min Di; confidence N = the
+ * second-smallest entry of that vector (+Inf when K = 1); argmin N = the first minimum, 0-based (the primal's tie
+ * rule).  Any of the three may be NULL.  Fails if no iteration has run with the flag on since it was set, after a
+ * reset, upload or bind (they start a new minimisation), and on strip plans.  Reading twice without iterating
+ * gives the same bits.  Host arrays: */
+int stereo_trws_plan_min_marginals(stereo_trws_plan *plan, double *min_marginals, double *confidence,
+                                   int32_t *argmin, char *err, size_t errcap);
+/* ... or device arrays of the caller (e.g. torch tensors), written on `stream` (hipStream_t, NULL = default)
+ * without waiting for it. */
+int stereo_trws_plan_min_marginals_device(stereo_trws_plan *plan, double *d_min_marginals,
+                                          double *d_confidence, int32_t *d_argmin, void *stream,
+                                          char *err, size_t errcap);
 
 /* ---- row strips: one image tiled across the GPUs of a node ------------------------------ *
  * No reference counterpart (the reference is one serial sweep, minimize.cpp:36-95); what is
@@ -498,6 +534,14 @@ int stereo_fusion_simultaneous_planes(stereo_fusion *ctx, const double *planes, 
 int stereo_fusion_simultaneous(stereo_fusion *ctx, const double *proposals, int K, double maxiter,
                                double max_relgap, double *energy, double *trws_energy,
                                double *lower_bound, double *iterations, char *err, size_t errcap);
+/* Node beliefs of the simultaneous fusion's TRW-S run (stereo_trws_plan_keep_min_marginals; no reference
+ * counterpart).  keep: applies to the plan the context creates for stereo_fusion_simultaneous / _planes from the
+ * next call on.  Read after such a call: min_marginals (K+1) x N, confidence N, argmin N (0-based), any may be
+ * NULL; rows in the label order TRW-S saw: the proposals in order, then the current assignment
+ * (dispmap_super.m:158-160). */
+int stereo_fusion_keep_min_marginals(stereo_fusion *ctx, int on, char *err, size_t errcap);
+int stereo_fusion_trws_min_marginals(stereo_fusion *ctx, double *min_marginals, double *confidence,
+                                     int32_t *argmin, char *err, size_t errcap);
 
 /* ---- SegPln proposals (dispmap_globalstereo.m:60-201) -------------------------------------
  * The winner-takes-all disparity map by window matching (:72-113): for every image and every disparity of

@@ -1006,6 +1006,7 @@ struct stereo_fusion {
   stereo_rd_plan *rd = nullptr;
   stereo_trws_plan *trws = nullptr;  // simultaneous fusion: plan of the last label count
   int trws_K = 0;
+  bool trws_mm = false;              // its node beliefs are kept (stereo_fusion_keep_min_marginals)
   DevBuf<double> props, unaryK, qK, qpK;
   DevBuf<int32_t> labels;
   std::vector<uint32_t> h_conn;
@@ -1364,7 +1365,8 @@ static int fusion_simultaneous_impl(stereo_fusion *F, const double *proposals, c
     const double t1 = now();
     if (stereo_trws_plan_bind_device(F->trws, F->unaryK.p, F->qK.p, F->qpK.p, nullptr, F->weights.p, F->tol, e2,
                                      sizeof(e2)) != 0 ||
-        stereo_trws_plan_reset(F->trws, e2, sizeof(e2)) != 0)
+        stereo_trws_plan_reset(F->trws, e2, sizeof(e2)) != 0 ||
+        stereo_trws_plan_keep_min_marginals(F->trws, F->trws_mm ? 1 : 0, e2, sizeof(e2)) != 0)
       throw std::runtime_error(e2);
     const double t2 = now();
     // Minimize_TRW_S runs at least one iteration and stops at iter >= iterMax (minimize.cpp:100-112)
@@ -1401,6 +1403,21 @@ int stereo_fusion_simultaneous(stereo_fusion *F, const double *proposals, int K,
   if (!F->have_assignment) return fail("stereo_fusion: no assignment set", err, errcap);
   return fusion_simultaneous_impl(F, proposals, nullptr, K, maxiter, max_relgap, energy, trws_energy, lower_bound,
                                   iterations, err, errcap);
+}
+
+int stereo_fusion_keep_min_marginals(stereo_fusion *F, int on, char *err, size_t errcap) {
+  if (!F) return fail("stereo_fusion_keep_min_marginals: NULL context", err, errcap);
+  F->trws_mm = on != 0;
+  return 0;
+}
+
+int stereo_fusion_trws_min_marginals(stereo_fusion *F, double *min_marginals, double *confidence, int32_t *argmin, char *err,
+                                     size_t errcap) {
+  if (!F) return fail("stereo_fusion_trws_min_marginals: NULL context", err, errcap);
+  if (!F->trws || !F->trws_mm)
+    return fail("stereo_fusion_trws_min_marginals: no simultaneous fusion has run with stereo_fusion_keep_min_marginals on",
+                err, errcap);
+  return stereo_trws_plan_min_marginals(F->trws, min_marginals, confidence, argmin, err, errcap);
 }
 
 int stereo_fusion_simultaneous_planes(stereo_fusion *F, const double *planes, int K, double maxiter, double max_relgap,

@@ -35,5 +35,13 @@ void wide_set_attributes();
 void launch_wide(int kernel, int what, int blocks, hipStream_t s, const DevParams &p, int epoch);
 void launch_wide_group(int kernel, int what, int blocks, hipStream_t s, const GroupArgs &ga, int epoch);
 
+// node beliefs after a run (trws_beliefs.hip): phase 1 between the backward sweep and the fused forward
+// sweep of an iteration, phase 2 on request after the run; K x N label-fastest rows in node-id order
+void launch_beliefs_accum(const double *unary, const double *msg, const int32_t *order, const int32_t *fptr,
+                          const int32_t *fidx, int K, int64_t N, double *out, hipStream_t s);
+void launch_beliefs_finish(const double *part, const double *msg, const int32_t *order, const int32_t *bptr,
+                           const int32_t *bidx, int K, int64_t N, double *mm, double *conf, int32_t *argmin,
+                           hipStream_t s);
+
 
 }  // namespace stereo

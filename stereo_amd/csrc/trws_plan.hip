@@ -237,6 +237,10 @@ struct stereo_trws_plan {
   bool self_sent = false;
   bool spec_allowed = false;   // the graph has such a run in both directions and STEREO_HIP_TRWS_SPEC is not 0
   bool spec_window = false;    // the positions are uniformly spaced over the window rounded up to four (finish_inputs)
+  // node beliefs (stereo_trws_plan_keep_min_marginals): phase 1's partial sums D_i + firstForward
+  // messages, K x N in node-id order; allocated only while the flag is on.  mm_ready: phase 1 ran in the last iteration
+  bool keep_mm = false, mm_ready = false;
+  DevBuf<double> d_belief;
   ~stereo_trws_plan() {
     for (int w = 0; w < 2; ++w)
       for (int k = 0; k < 3; ++k)
@@ -366,9 +370,13 @@ void persistent_iteration(stereo_trws_plan *P, const DevParams &p, hipStream_t s
                                   P->copy_stream));
   STEREO_HIP_CHECK(hipEventRecord(P->ev_lb, P->copy_stream));
   P->lb_in_flight = true;
+  // node beliefs, phase 1: every firstForward edge holds this iteration's backward message into its tail now
+  if (P->keep_mm)
+    launch_beliefs_accum(P->unary, P->d_msg.p, P->d_order.p, P->d_fptr.p, P->d_fidx.p, P->K, P->N, P->d_belief.p, s);
   // forward sweep of the NEXT iteration fused with this iteration's primal
   launch_persistent(P, p, 2, s);
   P->fwd_pending = true;
+  P->mm_ready = P->keep_mm;
   if (P->time_sweeps) STEREO_HIP_CHECK(hipEventRecord(P->ev1, s));
 }
 
@@ -391,7 +399,7 @@ void reset_state(stereo_trws_plan *P) {
   STEREO_HIP_CHECK(hipMemset(P->d_ctl.p, 0, sizeof(int32_t) * kCtlWords));
   STEREO_HIP_CHECK(hipDeviceSynchronize());
   P->iterations = 0; P->energy = 0; P->lb = 0; P->epoch = 0; P->fwd_pending = false;
-  P->lb_in_flight = false; P->issued = false;
+  P->lb_in_flight = false; P->issued = false; P->mm_ready = false;
 }
 
 // The order in which the reference's gateway hands EQUAL positions to the message code.
@@ -1127,7 +1135,7 @@ int stereo_trws_plan_iterate(stereo_trws_plan *P, int iters, double max_relgap, 
     for (int it = 0; it < iters; ++it) {
       issue_iteration(P, p, s);
       double lb = 0, en = 0;
-      if (!collect_iteration(P, s, &lb, &en)) return fail(gave_up_text(P), err, errcap);
+      if (!collect_iteration(P, s, &lb, &en)) { P->mm_ready = false; return fail(gave_up_text(P), err, errcap); }
       P->lb = lb; P->energy = en; P->iterations += 1;
       if (done_iters) *done_iters += 1;
       const double rel_gap = (en - lb) / en;  // minimize.cpp:105
@@ -1480,6 +1488,74 @@ int stereo_trws_plan_path(stereo_trws_plan *P) {
   return P->large ? 5 : P->wide ? 3 : P->fast2 ? 4 : P->fast ? 2 : 1;
 }
 
+int stereo_trws_plan_keep_min_marginals(stereo_trws_plan *P, int on, char *err, size_t errcap) {
+  DeviceScope device_scope_(P ? P->device : -1);
+  if (!P) return fail("stereo_trws_plan_keep_min_marginals: NULL plan", err, errcap);
+  if (P->nstrips > 1)
+    return fail("stereo_trws_plan_keep_min_marginals: a row strip has no min-marginals (per-strip beliefs are not "
+                "supported; solve on one plan)", err, errcap);
+  if (!on) {
+    P->keep_mm = false; P->mm_ready = false;
+    P->d_belief.release();
+    return 0;
+  }
+  if (P->keep_mm) return 0;
+  try {
+    P->d_belief.alloc((size_t)P->N * P->K);
+  } catch (const HipError &e) {
+    P->d_belief.release();
+    return fail("stereo_trws_plan_keep_min_marginals: cannot allocate the " + std::to_string(8 * (size_t)P->N * P->K) +
+                "-byte belief buffer (" + e.msg + ")", err, errcap);
+  }
+  P->keep_mm = true; P->mm_ready = false;
+  return 0;
+}
+
+static int min_marginals_impl(stereo_trws_plan *P, const char *who, double *mm, double *conf, int32_t *argmin, bool device,
+                              hipStream_t s, char *err, size_t errcap) {
+  if (!P) return fail(std::string(who) + ": NULL plan", err, errcap);
+  if (P->nstrips > 1)
+    return fail(std::string(who) + ": a row strip has no min-marginals (per-strip beliefs are not supported; solve on one plan)",
+                err, errcap);
+  if (!P->keep_mm || !P->mm_ready)
+    return fail(std::string(who) + ": no min-marginals to read: turn them on with stereo_trws_plan_keep_min_marginals and "
+                "iterate first (an upload, bind or reset discards them)", err, errcap);
+  try {
+    const size_t KN = (size_t)P->N * P->K;
+    if (device) {
+      launch_beliefs_finish(P->d_belief.p, P->d_msg.p, P->d_order.p, P->d_bptr.p, P->d_bidx.p, P->K, P->N, mm, conf, argmin, s);
+      return 0;
+    }
+    DevBuf<double> d_mm, d_conf;
+    DevBuf<int32_t> d_arg;
+    if (mm) d_mm.alloc(KN);
+    if (conf) d_conf.alloc(P->N);
+    if (argmin) d_arg.alloc(P->N);
+    launch_beliefs_finish(P->d_belief.p, P->d_msg.p, P->d_order.p, P->d_bptr.p, P->d_bidx.p, P->K, P->N, d_mm.p, d_conf.p,
+                          d_arg.p, nullptr);
+    if (mm) STEREO_HIP_CHECK(hipMemcpy(mm, d_mm.p, sizeof(double) * KN, hipMemcpyDeviceToHost));
+    if (conf) STEREO_HIP_CHECK(hipMemcpy(conf, d_conf.p, sizeof(double) * P->N, hipMemcpyDeviceToHost));
+    if (argmin) STEREO_HIP_CHECK(hipMemcpy(argmin, d_arg.p, sizeof(int32_t) * P->N, hipMemcpyDeviceToHost));
+    STEREO_HIP_CHECK(hipDeviceSynchronize());
+    return 0;
+  } catch (const HipError &e) {
+    return fail(e.msg, err, errcap);
+  }
+}
+
+int stereo_trws_plan_min_marginals(stereo_trws_plan *P, double *min_marginals, double *confidence, int32_t *argmin, char *err,
+                                   size_t errcap) {
+  DeviceScope device_scope_(P ? P->device : -1);
+  return min_marginals_impl(P, "stereo_trws_plan_min_marginals", min_marginals, confidence, argmin, false, nullptr, err, errcap);
+}
+
+int stereo_trws_plan_min_marginals_device(stereo_trws_plan *P, double *d_min_marginals, double *d_confidence,
+                                          int32_t *d_argmin, void *stream, char *err, size_t errcap) {
+  DeviceScope device_scope_(P ? P->device : -1);
+  return min_marginals_impl(P, "stereo_trws_plan_min_marginals_device", d_min_marginals, d_confidence, d_argmin, true,
+                            (hipStream_t)stream, err, errcap);
+}
+
 }  // extern "C"
 
 // ---- the gateway entry: what trws_mex reaches ------------------------------------------------------------
@@ -1511,6 +1587,7 @@ struct TrwsPlanCache {
   std::mutex mu;
   stereo_trws_plan *plan = nullptr;
   TrwsStripSet *strips = nullptr;   // ... or the row strips of the problem (STEREO_HIP_GPUS)
+  bool single_for_beliefs = false;  // the plan stands in for strips: stereo_trws_min_marginals solves on one plan
   std::string env;
   int kernel = 0, K = 0, mode = 0, device = -1;
   int64_t N = 0, E = 0;
@@ -1547,10 +1624,17 @@ bool columns_are_one_vector(const double *q, const double *qprim, int K, int64_t
   return true;
 }
 
+// beliefs: run with the plan's belief flag on and read min-marginals (K x N) / confidence (N), either may be NULL;
+// otherwise the flag is off (a plan the min-marginal entry used before pays nothing)
 int trws_solve_on(stereo_trws_plan *P, const double *unary, const double *q, const double *qprim, const double *alphas,
                   double tol, double maxiter, double max_relgap, bool look_for_shared, double *labelling, double *energy,
-                  double *lower_bound, double *iterations, char *err, size_t errcap) {
+                  double *lower_bound, double *iterations, char *err, size_t errcap, bool beliefs = false,
+                  double *min_marginals = nullptr, double *confidence = nullptr) {
   int rc;
+  if (beliefs || P->keep_mm) {
+    rc = stereo_trws_plan_keep_min_marginals(P, beliefs ? 1 : 0, err, errcap);
+    if (rc) return rc;
+  }
   if (look_for_shared && columns_are_one_vector(q, qprim, P->K, P->E))
     rc = stereo_trws_plan_upload(P, unary, nullptr, nullptr, q, alphas, tol, err, errcap);
   else
@@ -1561,7 +1645,9 @@ int trws_solve_on(stereo_trws_plan *P, const double *unary, const double *q, con
   if (itmax < 1) itmax = 1;
   rc = stereo_trws_plan_iterate(P, itmax, max_relgap, nullptr, nullptr, nullptr, err, errcap);
   if (rc) return rc;
-  return stereo_trws_plan_result(P, labelling, energy, lower_bound, iterations, err, errcap);
+  rc = stereo_trws_plan_result(P, labelling, energy, lower_bound, iterations, err, errcap);
+  if (rc || !beliefs || (!min_marginals && !confidence)) return rc;
+  return stereo_trws_plan_min_marginals(P, min_marginals, confidence, nullptr, err, errcap);
 }
 
 // ---- the gateway on several devices (STEREO_HIP_GPUS = G): row strips of the image grid ---------------------------
@@ -1707,24 +1793,12 @@ int gateway_strips(int K, int64_t N, int64_t E, const uint32_t *conn, const doub
   return G;
 }
 
-}  // namespace
-
-extern "C" {
-
-int stereo_trws_gateway_strips(void) { return g_last_gateway_strips; }
-
-void stereo_trws_cache_clear(void) {
-  TrwsPlanCache &C = trws_plan_cache();
-  std::lock_guard<std::mutex> lock(C.mu);
-  if (C.plan) { stereo_trws_plan_destroy(C.plan); C.plan = nullptr; }
-  if (C.strips) { delete C.strips; C.strips = nullptr; }
-  C.conn.clear(); C.conn.shrink_to_fit();
-}
-
-int stereo_trws(int kernel, const double *unary, const uint32_t *conn, const double *q,
-                const double *qprim, const double *alphas, double tol, double maxiter,
-                double max_relgap, int K, int64_t N, int64_t E, double *labelling, double *energy,
-                double *lower_bound, double *iterations, char *err, size_t errcap) {
+// The gateway behind stereo_trws and stereo_trws_min_marginals.  beliefs: always ONE plan (per-strip beliefs are not
+// supported; strips give the same bits), cached strips of the same problem are replaced by a single plan.
+int trws_gateway(int kernel, const double *unary, const uint32_t *conn, const double *q, const double *qprim, const double *alphas,
+                 double tol, double maxiter, double max_relgap, int K, int64_t N, int64_t E, double *labelling, double *energy,
+                 double *lower_bound, double *iterations, bool beliefs, double *min_marginals, double *confidence, char *err,
+                 size_t errcap) {
   if (kernel != 1 && kernel != 2) return fail("Unsupported kernel", err, errcap);  // trws_mex.cpp:162
   if (!unary || !conn || !q || !qprim || !alphas || !labelling || !energy || !lower_bound || !iterations)
     return fail("stereo_trws: NULL argument", err, errcap);
@@ -1734,7 +1808,7 @@ int stereo_trws(int kernel, const double *unary, const uint32_t *conn, const dou
   const char *ce = std::getenv("STEREO_HIP_TRWS_CACHE");
   const bool cached = (!ce || std::atoi(ce) != 0) && E > 0 && N > 0;
   int64_t gridH = 0;
-  const int G = (E > 0 && N > 0) ? gateway_strips(K, N, E, conn, q, qprim, mode, &gridH) : 1;
+  const int G = (E > 0 && N > 0 && !beliefs) ? gateway_strips(K, N, E, conn, q, qprim, mode, &gridH) : 1;
   g_last_gateway_strips = G;
   if (G > 1 && !cached) {
     TrwsStripSet S;
@@ -1748,7 +1822,7 @@ int stereo_trws(int kernel, const double *unary, const uint32_t *conn, const dou
     if (rc) return rc;
     // (above 512 labels only the shared positions vector is taken: look for it there)
     rc = trws_solve_on(P, unary, q, qprim, alphas, tol, maxiter, max_relgap, K > kGenericMaxK, labelling, energy, lower_bound,
-                       iterations, err, errcap);
+                       iterations, err, errcap, beliefs, min_marginals, confidence);
     stereo_trws_plan_destroy(P);
     return rc;
   }
@@ -1757,7 +1831,9 @@ int stereo_trws(int kernel, const double *unary, const uint32_t *conn, const dou
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return fail("stereo_trws: no HIP device available (the HIP path has no CPU fallback)", err, errcap);
   const std::string env = trws_env_key();
-  const bool hit = (C.plan || C.strips) && C.kernel == kernel && C.K == K && C.N == N && C.E == E && C.mode == mode && C.device == dev && C.env == env &&
+  // (a single plan left by the min-marginal entry does not stand in for the strips a plain call asks for)
+  const bool hit = (beliefs ? C.plan != nullptr : (C.plan || C.strips) && !(G > 1 && C.plan && C.single_for_beliefs)) && C.kernel == kernel && C.K == K &&
+                   C.N == N && C.E == E && C.mode == mode && C.device == dev && C.env == env &&
                    std::memcmp(C.conn.data(), conn, sizeof(uint32_t) * 2 * (size_t)E) == 0;
   if (!hit) {
     if (C.plan) { stereo_trws_plan_destroy(C.plan); C.plan = nullptr; }
@@ -1781,11 +1857,43 @@ int stereo_trws(int kernel, const double *unary, const uint32_t *conn, const dou
     if (rc) return rc;
     C.plan = P; C.kernel = kernel; C.K = K; C.N = N; C.E = E; C.mode = mode; C.device = dev; C.env = env;
     C.conn.assign(conn, conn + 2 * (size_t)E);
+    C.single_for_beliefs = beliefs && gateway_strips(K, N, E, conn, q, qprim, mode, &gridH) > 1;
   }
   const int rc = trws_solve_on(C.plan, unary, q, qprim, alphas, tol, maxiter, max_relgap, true, labelling, energy, lower_bound,
-                               iterations, err, errcap);
+                               iterations, err, errcap, beliefs, min_marginals, confidence);
   if (rc) { stereo_trws_plan_destroy(C.plan); C.plan = nullptr; }   // never keep a plan an error went through
   return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int stereo_trws_gateway_strips(void) { return g_last_gateway_strips; }
+
+void stereo_trws_cache_clear(void) {
+  TrwsPlanCache &C = trws_plan_cache();
+  std::lock_guard<std::mutex> lock(C.mu);
+  if (C.plan) { stereo_trws_plan_destroy(C.plan); C.plan = nullptr; }
+  if (C.strips) { delete C.strips; C.strips = nullptr; }
+  C.conn.clear(); C.conn.shrink_to_fit();
+}
+
+int stereo_trws(int kernel, const double *unary, const uint32_t *conn, const double *q,
+                const double *qprim, const double *alphas, double tol, double maxiter,
+                double max_relgap, int K, int64_t N, int64_t E, double *labelling, double *energy,
+                double *lower_bound, double *iterations, char *err, size_t errcap) {
+  return trws_gateway(kernel, unary, conn, q, qprim, alphas, tol, maxiter, max_relgap, K, N, E, labelling, energy, lower_bound,
+                      iterations, false, nullptr, nullptr, err, errcap);
+}
+
+int stereo_trws_min_marginals(int kernel, const double *unary, const uint32_t *conn, const double *q,
+                              const double *qprim, const double *alphas, double tol, double maxiter,
+                              double max_relgap, int K, int64_t N, int64_t E, double *labelling, double *energy,
+                              double *lower_bound, double *iterations, double *min_marginals, double *confidence,
+                              char *err, size_t errcap) {
+  return trws_gateway(kernel, unary, conn, q, qprim, alphas, tol, maxiter, max_relgap, K, N, E, labelling, energy, lower_bound,
+                      iterations, true, min_marginals, confidence, err, errcap);
 }
 
 }  // extern "C"

@@ -268,8 +268,10 @@ class dispmap_super:
         self.fusion_energies = [float(e) for e in E]
         return len(E)
 
-    def simultaneous_fusion(self, proposal_cell):
-        """dispmap_super.m:153-198"""
+    def simultaneous_fusion(self, proposal_cell, confidence=False):
+        """dispmap_super.m:153-198.  confidence=True also sets self.min_marginals ((K+1) x N: the proposals in order,
+        then the current assignment) and self.confidence (H x W, the reshape of current_dispmap) from the TRW-S run's
+        node beliefs; the device-resident and the stateless path give the same values."""
         if not isinstance(proposal_cell, (list, tuple)):
             raise StereoHipError("Input proposals should be given in cell array.")
         ctx = self._context()
@@ -287,25 +289,34 @@ class dispmap_super:
             if not self._ctx_has_assignment:
                 ctx.set_assignment(self._assignment)
                 self._ctx_has_assignment = True
+            ctx.keep_min_marginals(confidence)
             if single:   # K planes instead of K x 4 x N doubles
                 tab = np.concatenate([p.planes for p in proposal_cell], axis=1)
                 self.stored_energy, e, lb, iterations = ctx.simultaneous_planes(tab, self.maxiter, self._max_relgap)
-                self._host_stale = True
-                return e, lb, iterations
-            self.stored_energy, e, lb, iterations = ctx.simultaneous(proposal_cell, self.maxiter, self._max_relgap)
+            else:
+                self.stored_energy, e, lb, iterations = ctx.simultaneous(proposal_cell, self.maxiter, self._max_relgap)
             self._host_stale = True
+            if confidence:
+                mm, conf, _ = ctx.trws_min_marginals()
+                self._set_confidence(mm, conf)
             return e, lb, iterations
         props = [np.asfortranarray(p, dtype=np.float64) for p in proposal_cell] + [self.assignment]
         unary = np.stack([self.unary_cost(p) for p in props], axis=0)             # K x N
         q, qprim = T.trws_positions(self.neighborhood, self.points, props, self.d_min, self.d_step)
-        L, e, lb, iterations = trws(np.int32(self._kernel), unary, self.neighborhood + 1, q, qprim,
-                                    self.smooth_weights.reshape(-1), self.tol,
-                                    {"maxiter": self.maxiter, "max_relgap": self._max_relgap})
+        out = trws(np.int32(self._kernel), unary, self.neighborhood + 1, q, qprim, self.smooth_weights.reshape(-1),
+                   self.tol, {"maxiter": self.maxiter, "max_relgap": self._max_relgap}, min_marginals=confidence)
+        L, e, lb, iterations = out[:4]
+        if confidence:
+            self._set_confidence(out[4], out[5])
         a = np.zeros_like(props[0])
         for i, p in enumerate(props):
             a[:, L == i + 1] = p[:, L == i + 1]
         self.assignment = a
         return e, lb, iterations
+
+    def _set_confidence(self, mm, conf):
+        self.min_marginals = mm
+        self.confidence = np.asarray(conf).reshape(self.sz[1], self.sz[0]).T
 
     def current_dispmap(self):
         return self.disparitymap_from_assignment(self.assignment).reshape(self.sz[1], self.sz[0]).T

@@ -136,15 +136,30 @@ class FusionContext:
     def simultaneous_planes(self, planes, maxiter=1000, max_relgap=0.0):
         """simultaneous() with K single-plane proposals (4 x K) built on the device."""
         planes = np.asfortranarray(np.asarray(planes, np.float64).reshape(4, -1))
+        self._trws_labels = planes.shape[1] + 1
         e, te, lb, it = C.c_double(), C.c_double(), C.c_double(), C.c_double()
         self._call(_lib.lib().stereo_fusion_simultaneous_planes, _p(planes), C.c_int(planes.shape[1]), C.c_double(maxiter),
                    C.c_double(max_relgap), C.byref(e), C.byref(te), C.byref(lb), C.byref(it))
         return e.value, te.value, lb.value, it.value
 
+    def keep_min_marginals(self, on=True):
+        """Keep the node beliefs of the simultaneous fusions' TRW-S runs (stereo_fusion_keep_min_marginals)."""
+        self._call(_lib.lib().stereo_fusion_keep_min_marginals, C.c_int(int(bool(on))))
+
+    def trws_min_marginals(self):
+        """After simultaneous() / simultaneous_planes() with keep_min_marginals on: (min_marginals (K+1) x N, confidence N,
+        argmin N one based); rows: the proposals in order, then the current assignment (dispmap_super.m:158-160)."""
+        mm = np.zeros((getattr(self, "_trws_labels", 0), self.N), order="F")
+        conf = np.zeros(self.N)
+        arg = np.zeros(self.N, np.int32)
+        self._call(_lib.lib().stereo_fusion_trws_min_marginals, _p(mm) if mm.size else None, _p(conf), _p(arg, C.c_int32))
+        return mm, conf, arg.astype(np.float64) + 1
+
     def simultaneous(self, proposals, maxiter=1000, max_relgap=0.0):
         """proposals: list of 4 x N plane arrays (the current assignment is appended on the device).
         -> (stored energy afterwards, trws energy, lower bound, iterations)"""
         stack = np.asfortranarray(np.stack([np.asarray(P, np.float64) for P in proposals], axis=2))  # 4 x N x K
+        self._trws_labels = len(proposals) + 1
         e, te, lb, it = C.c_double(), C.c_double(), C.c_double(), C.c_double()
         self._call(_lib.lib().stereo_fusion_simultaneous, _p(stack), C.c_int(len(proposals)), C.c_double(maxiter),
                    C.c_double(max_relgap), C.byref(e), C.byref(te), C.byref(lb), C.byref(it))

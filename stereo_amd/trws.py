@@ -6,7 +6,9 @@ argument meaning of trws.m:2-33: ``unary`` is K x N, ``connectivity`` 2 x E and
 ONE based (the wrapper subtracts 1 like trws.m:33), ``q`` / ``qprim`` K x E,
 ``alphas`` E x 1, ``options`` a dict with ``maxiter`` (default 1000) and
 ``max_relgap`` (default 0) as in trws_mex.cpp:40-41.  Returns
-``(solution, energy, lower_bound, iterations)`` with 1-based labels.
+``(solution, energy, lower_bound, iterations)`` with 1-based labels; with
+``min_marginals=True`` also each node's min-marginals (K x N) and confidence (N)
+(stereo_trws_min_marginals).
 """
 import ctypes as C
 
@@ -38,7 +40,7 @@ def _ptr(a, t=C.c_double):
     return a.ctypes.data_as(C.POINTER(t))
 
 
-def trws(kernel, unary, connectivity, q, qprim, alphas, tol, options=None):
+def trws(kernel, unary, connectivity, q, qprim, alphas, tol, options=None, min_marginals=False):
     options = dict(options or {})
     maxiter = float(options.pop("maxiter", 1000))
     max_relgap = float(options.pop("max_relgap", 0))
@@ -66,13 +68,18 @@ def trws(kernel, unary, connectivity, q, qprim, alphas, tol, options=None):
     lab = np.zeros(N)
     en, lb, it = C.c_double(), C.c_double(), C.c_double()
     err = _lib.errbuf()
-    rc = _lib.lib().stereo_trws(C.c_int(kernel), _ptr(unary), _ptr(conn, C.c_uint32), _ptr(q),
-                                _ptr(qprim), _ptr(alphas), C.c_double(float(np.reshape(tol, -1)[0])),
-                                C.c_double(maxiter), C.c_double(max_relgap), C.c_int(K),
-                                C.c_int64(N), C.c_int64(E), _ptr(lab), C.byref(en), C.byref(lb),
-                                C.byref(it), err, C.c_size_t(len(err)))
+    args = (C.c_int(kernel), _ptr(unary), _ptr(conn, C.c_uint32), _ptr(q), _ptr(qprim), _ptr(alphas),
+            C.c_double(float(np.reshape(tol, -1)[0])), C.c_double(maxiter), C.c_double(max_relgap),
+            C.c_int(K), C.c_int64(N), C.c_int64(E), _ptr(lab), C.byref(en), C.byref(lb), C.byref(it))
+    if not min_marginals:
+        rc = _lib.lib().stereo_trws(*args, err, C.c_size_t(len(err)))
+        _lib.check(rc, err)
+        return lab, en.value, lb.value, it.value
+    mm = np.zeros((K, N), order="F")
+    conf = np.zeros(N)
+    rc = _lib.lib().stereo_trws_min_marginals(*args, _ptr(mm), _ptr(conf), err, C.c_size_t(len(err)))
     _lib.check(rc, err)
-    return lab, en.value, lb.value, it.value
+    return lab, en.value, lb.value, it.value, mm, conf
 
 
 class TrwsPlan:
@@ -160,6 +167,37 @@ class TrwsPlan:
                                                 C.c_size_t(len(err)))
         _lib.check(rc, err)
         return lab, en.value, lb.value, it.value
+
+    def keep_min_marginals(self, on=True):
+        """Keep node beliefs during the following iterations (stereo_trws_plan_keep_min_marginals):
+        one extra kernel per iteration and 8 K N bytes of device memory while on."""
+        err = _lib.errbuf()
+        rc = _lib.lib().stereo_trws_plan_keep_min_marginals(self._h, C.c_int(int(bool(on))), err,
+                                                            C.c_size_t(len(err)))
+        _lib.check(rc, err)
+
+    def min_marginals(self):
+        """(min_marginals K x N, confidence N, argmin N) of the last run; argmin one based
+        like result()'s labels."""
+        mm = np.zeros((self.K, self.N), order="F")
+        conf = np.zeros(self.N)
+        arg = np.zeros(self.N, np.int32)
+        err = _lib.errbuf()
+        rc = _lib.lib().stereo_trws_plan_min_marginals(self._h, _ptr(mm), _ptr(conf), _ptr(arg, C.c_int32),
+                                                       err, C.c_size_t(len(err)))
+        _lib.check(rc, err)
+        return mm, conf, arg.astype(np.float64) + 1
+
+    def min_marginals_device(self, d_min_marginals=None, d_confidence=None, d_argmin=None, stream=None):
+        """Same into device memory of the caller (ints, e.g. tensor.data_ptr(); any may be None):
+        K x N float64 label fastest (a contiguous (N, K) tensor), N float64, N int32 ZERO based.
+        Written on `stream` without waiting for it."""
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        err = _lib.errbuf()
+        rc = _lib.lib().stereo_trws_plan_min_marginals_device(self._h, vp(d_min_marginals), vp(d_confidence),
+                                                              vp(d_argmin), vp(stream), err,
+                                                              C.c_size_t(len(err)))
+        _lib.check(rc, err)
 
     def info(self):
         rank = np.zeros(self.N, np.int64)
