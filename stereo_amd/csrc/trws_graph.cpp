@@ -308,6 +308,7 @@ bool build_trws_graph(int64_t N, int64_t E, const uint32_t *conn, TrwsGraph &g,
   }
   if (g.fast_ok) {
     constexpr int W = TrwsGraph::kDescWords;
+    bool protocol_ok[2] = {true, true};
     // the two sweep directions are independent of each other: one host thread each
     auto build_direction = [&](int d) {
       auto tick_ = std::chrono::steady_clock::now();
@@ -528,6 +529,96 @@ bool build_trws_graph(int64_t N, int64_t E, const uint32_t *conn, TrwsGraph &g,
         for (auto &th : pool) th.join();
       }
       DTICK("dir0 descriptors");
+      // ---- does the loader protocol terminate on this schedule?  (trws.py: simulate_look_ahead and
+      // simulate_spec_schedule state the rules and DESIGN.md 4.1 the kernel lines behind them; this is the same
+      // fixed point, by a work list instead of rounds: linear time.)
+      // The visit that computes position i of a run ends at a workgroup barrier the loader reaches only once the
+      // foreign dependencies of position i + 1 are visible -- and those of position i + 2 where bit 12 lets it wait
+      // two visits ahead --, and the storer raises node i's completion flag behind that barrier.  (Only
+      // trws_wide_kernel's loader B waits two visits ahead; the rule is applied whatever kernel a plan will pick --
+      // a superset of the constraints of trws_pipe_kernel and trws_pipe2_kernel, so what terminates under it
+      // terminates there, at the price of refusing a few graphs those two could take.)  Every run gets a workgroup of
+      // its own here (the ticket order with fewer workgroups is look_ahead_ok's); granules only ever make a row
+      // visible EARLIER.  On the image grid the chain builder never lets two runs wait for each other this way; on
+      // other graphs it can (two runs whose second nodes each hang on the other's first node), and such a graph must
+      // not reach the descriptor-driven kernels.
+      // The speculative schedule (sp != nullptr) makes rows visible LATER: a node of the cut run is visible to
+      // everybody else only when its SEGMENT commits (the storer holds a segment's flags back, spec_commit raises
+      // them), segment q commits behind segment q - 1, starts behind the runner's cut q, and the runner walks the
+      // cut run waiting for every node's foreign dependencies.  A one-node run that hangs on a node of a segment and
+      // feeds a later node of the SAME segment then stops that segment for good -- the host's `fine` test only looks
+      // at dependencies inside the cut run.  Ordinary runs keep the loader coupling above.
+      // wgs > 0: only wgs workgroups are resident; they draw the tickets in order, a finished task frees its workgroup
+      // for the next ticket (every task is monotone, so which tasks ever finish does not depend on timing).
+      auto protocol_terminates = [&](const TrwsGraph::Sweep::Spec *sp, int64_t wgs) -> bool {
+        const std::vector<int32_t> &rptr = sp ? sp->run_ptr : S.chain_run_ptr;
+        const int64_t T = (int64_t)rptr.size() - 1;
+        const int64_t nseg = sp ? sp->nseg : 0, L = sp ? sp->seg_len : 1;
+        // what a task can wait for: [0, N) a node's flag, N + q the runner's cut q, N + nseg + q segment q's commit
+        std::vector<uint8_t> fired(N + 2 * nseg, 0);
+        std::vector<int32_t> wait_head(N + 2 * nseg, -1), wait_next(T + 1, -1), ended(T + 1, 0), work;
+        auto blocked_on = [&](int64_t pos) -> int32_t {   // first dependency of the node at `pos` nobody can see yet
+          for (int32_t x : deps[S.chain_rank[pos]])
+            if (!fired[x]) return x;
+          return -1;
+        };
+        auto wait = [&](int64_t key, int32_t t) { wait_next[t] = wait_head[key]; wait_head[key] = t; };   // (one key at a time)
+        auto fire = [&](int64_t key) {
+          fired[key] = 1;
+          for (int32_t w = wait_head[key]; w >= 0; w = wait_next[w]) work.push_back(w);
+          wait_head[key] = -1;
+        };
+        if (sp) fired[N] = 1;
+        const int64_t ntickets = T + (sp ? 1 : 0);   // task T: the runner
+        int64_t finished = 0, started = 0;
+        auto start_more = [&]() {
+          for (; started < ntickets && (wgs <= 0 || started < wgs + finished); ++started) {
+            const int32_t k = sp ? sp->run_order[started] : S.chain_run_order.empty() ? (int32_t)started : S.chain_run_order[started];
+            work.push_back(k < 0 ? (int32_t)T : k);
+          }
+        };
+        start_more();
+        while (!work.empty() || (start_more(), !work.empty())) {
+          const int32_t k = work.back();
+          work.pop_back();
+          if (k == T) {   // the runner: ended = nodes walked
+            for (;;) {
+              const int64_t cur = sp->c0 + ended[k];
+              if (cur >= sp->c1) { ++finished; break; }
+              const int32_t x = blocked_on(cur);
+              if (x >= 0) { wait(x, k); break; }
+              const int64_t off = ++ended[k];
+              if (sp->c0 + off < sp->c1 && off % L == 0 && off / L < nseg) fire(N + off / L);
+            }
+            continue;
+          }
+          const int64_t a = rptr[k], b = rptr[k + 1];
+          const int64_t seg = sp ? (int64_t)sp->kind[k] - 1 : -1;
+          if (seg >= 0) {   // a segment: ended = nodes walked; nothing is visible before the commit
+            if (!fired[N + seg]) { wait(N + seg, k); continue; }
+            int32_t x = -1;
+            while (a + ended[k] < b && (x = blocked_on(a + ended[k])) < 0) ++ended[k];
+            if (x >= 0) { wait(x, k); continue; }
+            if (seg > 0 && !fired[N + nseg + seg - 1]) { wait(N + nseg + seg - 1, k); continue; }
+            for (int64_t pos = a; pos < b; ++pos) fire(S.chain_rank[pos]);
+            fire(N + nseg + seg);
+            ++finished;
+            continue;
+          }
+          for (;;) {   // an ordinary run: ended = visits ended (the lead-in visit first)
+            if (ended[k] == b - a + 1) { ++finished; break; }
+            const int64_t i = a + ended[k] - 1;   // computed by the visit about to end (a - 1: the lead-in visit)
+            int32_t x = i + 1 < b ? blocked_on(i + 1) : -1;
+            if (x < 0 && i + 2 < b && ((S.desc[(size_t)(i + 2) * W + 2] >> 12) & 1)) x = blocked_on(i + 2);
+            if (x >= 0) { wait(x, k); break; }
+            ++ended[k];
+            if (i >= a) fire(S.chain_rank[i]);
+          }
+        }
+        return finished == T + (sp ? 1 : 0);
+      };
+      protocol_ok[d] = protocol_terminates(nullptr, 0);
+      DTICK("dir0 protocol check");
       // Completion flags are raised either in the middle of the next visit (costs a store
       // drain on that run's critical path, but the dependent run can follow closely) or
       // lazily at its end (free).  A run is "lazy" if nobody else reads its flags before it
@@ -605,7 +696,11 @@ bool build_trws_graph(int64_t N, int64_t E, const uint32_t *conn, TrwsGraph &g,
             else sp.run_order.push_back(k < best ? k : k + sp.nseg - 1);
           }
           sp.ok = true;
-          S.spec = std::move(sp);
+          // (never a schedule the host cannot show to terminate: such a graph keeps the plain chain schedule)
+          // (with every task resident, and -- where the tickets outnumber the workgroups certain to be resident -- with
+          //  that many workgroups drawing tickets in order: a segment holds its workgroup until it commits)
+          const int64_t Wres = resident > 0 && (int64_t)sp.run_order.size() > resident ? resident : 0;
+          if (protocol_terminates(&sp, 0) && (Wres == 0 || protocol_terminates(&sp, Wres))) S.spec = std::move(sp);
         }
       }
       // ---- tagged-granule hand-over (word 57, trws_graph.h): the rows a node fetches from another ordinary run that
@@ -655,6 +750,15 @@ bool build_trws_graph(int64_t N, int64_t E, const uint32_t *conn, TrwsGraph &g,
     std::thread backward([&] { build_direction(1); });
     build_direction(0);
     backward.join();
+    if (!protocol_ok[0] || !protocol_ok[1]) {
+      // a schedule the host cannot show to terminate is never launched: the generic kernel takes the graph
+      g.fast_ok = false;
+      for (int d = 0; d < 2; ++d) {
+        TrwsGraph::Sweep &S = g.sweep[d];
+        S.desc = std::vector<int32_t>(); S.chain_rank.clear(); S.chain_run_ptr.clear(); S.chain_run_order.clear();
+        S.chain_run_strip.clear(); S.spec = TrwsGraph::Sweep::Spec();
+      }
+    }
   }
   TICK("end");
   return true;

@@ -98,7 +98,8 @@ struct TrwsGraph {
     } spec;
   } sweep[2];
   static constexpr int kDescWords = 64;
-  // every node has <= 8 incident edges and <= 4 foreign dependencies per direction
+  // every node has <= 8 incident edges and <= 4 foreign dependencies per direction, and the loader protocol
+  // terminates on both chain schedules (trws_graph.cpp); false: the generic kernel takes the graph
   bool fast_ok = false;
   static constexpr int kMaxSlots = 8;
 };

@@ -664,7 +664,7 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
     P->Nl = N; P->El = E;
     if (nstrips > 1) {
       if (!g.fast_ok)
-        return fail("stereo_trws: row strips need a graph the pipelined kernels take (<= 8 edges per node)", err, errcap);
+        return fail("stereo_trws: row strips need a graph the pipelined kernels take (<= 8 edges per node, <= 4 dependencies in other runs, a chain schedule that provably terminates)", err, errcap);
       P->layout.reset(new StripLayout);
       if (!build_strip_layout(g, strip, *P->layout, gerr)) return fail(gerr, err, errcap);
       const StripLayout &L = *P->layout;
