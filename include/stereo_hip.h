@@ -317,6 +317,13 @@ int stereo_trws_plan_debug_flags(stereo_trws_plan *plan, int32_t *done, int32_t 
  * they lie in HBM (E x K doubles, edge-major).  No reference counterpart. */
 int stereo_trws_plan_debug_terms(stereo_trws_plan *plan, double *lb_terms, int64_t cap, int64_t *n_lb);
 int stereo_trws_plan_debug_messages(stereo_trws_plan *plan, double *out, int64_t count);
+/* Development aid, host only (no device): the rule that picks a plan's sweep kernel family.  Facts of the
+ * plan: kernel, K, message_mode, fast_ok (the graph suits the pipelined kernels), fast_switch (STEREO_HIP_TRWS_FAST is
+ * not 0), strips (the plan is a row strip).  Facts of its inputs: positions = 0 q / qprim per edge, 1 one shared vector
+ * that is not finite and strictly ascending, 2 one that is, -1 no inputs yet; lambda.  Returns what stereo_trws_plan_path
+ * would, or 0 with the refusal the plan gives in err. */
+int stereo_trws_family_rule(int kernel, int K, int message_mode, int fast_ok, int fast_switch, int strips,
+                            int positions, double lambda, char *err, size_t errcap);
 /* The gateway on several devices.  With STEREO_HIP_GPUS=G (2 .. 16) in the environment stereo_trws -- what trws_mex
  * reaches, cpp/trws_mex.cpp:149-164 -- cuts the problem into G row strips when the graph is the image grid of
  * dispmap_super.m:279-302 (nodes col * H + row, 4-neighbourhood, H >= 2 G; K <= 128, or <= 256 with one positions vector

@@ -357,3 +357,28 @@ def test_the_gateway_shards_over_strips(G, hip, monkeypatch):
     q = rng.uniform(0, 8, (5, n)); qp = rng.uniform(0, 8, (5, n))
     hip.trws(1, rng.uniform(0, 9, (5, n)), conn, q, qp, np.ones(n), 2.0, dict(maxiter=3))
     assert strips_used() == 1
+
+
+def test_the_gateway_cache_remembers_how_many_strips_it_holds(hip, monkeypatch):
+    """128 < K <= 256 with STEREO_HIP_GPUS=2: one positions vector in every column of q / qprim runs on two strips,
+    positions per edge on one plan.  The same grid asks for both in turn, the cache is not cleared in between: every
+    call succeeds and equals the same call without the switch, and stereo_trws_gateway_strips tells what ran.  (Before
+    the strip count was part of the cache key the second call ran the cached strips and returned their refusal.)"""
+    from stereo_amd import _lib
+    from helpers import trws_problem
+    strips_used = lambda: int(_lib.lib().stereo_trws_gateway_strips())
+    calls = []
+    for kind in ("fronto", "general", "fronto"):
+        p = trws_problem(44, 16, 12, 130, kind=kind)
+        calls.append((1, p["unary"].T, p["conn"].T + 1, p["q"].T, p["qprim"].T, p["alphas"], 20.0, dict(maxiter=5, max_relgap=0.0)))
+    assert np.array_equal(calls[0][2], calls[1][2])
+    monkeypatch.delenv("STEREO_HIP_GPUS", raising=False)
+    expected = []
+    for args in calls:
+        expected.append(hip.trws(*args))
+        assert strips_used() == 1
+    monkeypatch.setenv("STEREO_HIP_GPUS", "2")
+    for args, (lab0, en0, lb0, it0), G in zip(calls, expected, (2, 1, 2)):
+        lab, en, lb, it = hip.trws(*args)
+        assert strips_used() == G
+        assert it == it0 and np.array_equal(lab, lab0) and en == en0 and lb == lb0
