@@ -527,31 +527,17 @@ size_t generic_lds_bytes(int Kp) {
   return sizeof(double) * (size_t)(Kp + 8 + kMaxSlots * Kp + Kp + kWavesPerBlock * (kWaveVecs * Kp + 8));
 }
 
-void generic_set_attributes(int lds) {
-#define SET_PLDS(KER, BW, MD, PR, UP)                                                              \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)trws_persistent_kernel<KER, BW, MD, PR, UP>,  \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-#define SET_PLDS4(KER, MD)                                                                         \
-  SET_PLDS(KER, false, MD, false, true); SET_PLDS(KER, true, MD, false, true);                    \
-  SET_PLDS(KER, false, MD, true, true); SET_PLDS(KER, false, MD, true, false)
-  SET_PLDS4(1, 0); SET_PLDS4(1, 1); SET_PLDS4(2, 0); SET_PLDS4(2, 1);
-#undef SET_PLDS4
-#undef SET_PLDS
-}
+// rows: [smoothness kernel 1 | 2][message mode 0 | 1]
+#define GENERIC_ENTRY(BW, PR, UP, KER, MD) (const void *)trws_persistent_kernel<KER, BW, MD, PR, UP>,
+#define GENERIC_ROW(KER, MD) {TRWS_SWEEP_VARIANTS(GENERIC_ENTRY, KER, MD)}
+static const SweepRow kGenericKernels[4] = {GENERIC_ROW(1, 0), GENERIC_ROW(1, 1), GENERIC_ROW(2, 0), GENERIC_ROW(2, 1)};
+#undef GENERIC_ROW
+#undef GENERIC_ENTRY
+
+void generic_set_attributes(int lds) { set_max_dynamic_lds(kGenericKernels, 4, lds); }
 
 void launch_generic(int kernel, int mode, int what, int blocks, size_t lds, hipStream_t s, const DevParams &p, int epoch) {
-  const dim3 grid(blocks), block(kBlock);
-#define GEN(KER, MD)                                                                                                          \
-  switch (what) {                                                                                                             \
-    case 0: hipLaunchKernelGGL((trws_persistent_kernel<KER, false, MD, false, true>), grid, block, lds, s, p, epoch); break;  \
-    case 1: hipLaunchKernelGGL((trws_persistent_kernel<KER, true, MD, false, true>), grid, block, lds, s, p, epoch); break;   \
-    case 2: hipLaunchKernelGGL((trws_persistent_kernel<KER, false, MD, true, true>), grid, block, lds, s, p, epoch); break;   \
-    default: hipLaunchKernelGGL((trws_persistent_kernel<KER, false, MD, true, false>), grid, block, lds, s, p, epoch); break; \
-  }
-  if (kernel == 1) { if (mode == 0) { GEN(1, 0) } else { GEN(1, 1) } }
-  else { if (mode == 0) { GEN(2, 0) } else { GEN(2, 1) } }
-#undef GEN
-  STEREO_HIP_CHECK(hipGetLastError());
+  launch_sweep(kGenericKernels[(kernel == 1 ? 0 : 1) * 2 + (mode == 0 ? 0 : 1)], what, blocks, kBlock, lds, s, p, epoch);
 }
 
 }  // namespace stereo

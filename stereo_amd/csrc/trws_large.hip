@@ -396,31 +396,17 @@ size_t large_lds_bytes(int Kp) {
 
 size_t large_scratch_doubles(int Kp) { return 3 * (size_t)(Kp + 2); }
 
-void large_set_attributes(int lds) {
-#define SET_LLDS(KER, BW, MD, PR, UP)                                                          \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)trws_large_kernel<KER, BW, MD, PR, UP>,  \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-#define SET_LLDS4(KER, MD)                                                                     \
-  SET_LLDS(KER, false, MD, false, true); SET_LLDS(KER, true, MD, false, true);                \
-  SET_LLDS(KER, false, MD, true, true); SET_LLDS(KER, false, MD, true, false)
-  SET_LLDS4(1, 0); SET_LLDS4(1, 1); SET_LLDS4(2, 0); SET_LLDS4(2, 1);
-#undef SET_LLDS4
-#undef SET_LLDS
-}
+// rows: [smoothness kernel 1 | 2][message mode 0 | 1]
+#define LARGE_ENTRY(BW, PR, UP, KER, MD) (const void *)trws_large_kernel<KER, BW, MD, PR, UP>,
+#define LARGE_ROW(KER, MD) {TRWS_SWEEP_VARIANTS(LARGE_ENTRY, KER, MD)}
+static const SweepRow kLargeKernels[4] = {LARGE_ROW(1, 0), LARGE_ROW(1, 1), LARGE_ROW(2, 0), LARGE_ROW(2, 1)};
+#undef LARGE_ROW
+#undef LARGE_ENTRY
+
+void large_set_attributes(int lds) { set_max_dynamic_lds(kLargeKernels, 4, lds); }
 
 void launch_large(int kernel, int mode, int what, int blocks, size_t lds, hipStream_t s, const DevParams &p, int epoch) {
-  const dim3 grid(blocks), block(kLBlock);
-#define LRG(KER, MD)                                                                                                     \
-  switch (what) {                                                                                                        \
-    case 0: hipLaunchKernelGGL((trws_large_kernel<KER, false, MD, false, true>), grid, block, lds, s, p, epoch); break;  \
-    case 1: hipLaunchKernelGGL((trws_large_kernel<KER, true, MD, false, true>), grid, block, lds, s, p, epoch); break;   \
-    case 2: hipLaunchKernelGGL((trws_large_kernel<KER, false, MD, true, true>), grid, block, lds, s, p, epoch); break;   \
-    default: hipLaunchKernelGGL((trws_large_kernel<KER, false, MD, true, false>), grid, block, lds, s, p, epoch); break; \
-  }
-  if (kernel == 1) { if (mode == 0) { LRG(1, 0) } else { LRG(1, 1) } }
-  else { if (mode == 0) { LRG(2, 0) } else { LRG(2, 1) } }
-#undef LRG
-  STEREO_HIP_CHECK(hipGetLastError());
+  launch_sweep(kLargeKernels[(kernel == 1 ? 0 : 1) * 2 + (mode == 0 ? 0 : 1)], what, blocks, kLBlock, lds, s, p, epoch);
 }
 
 }  // namespace stereo

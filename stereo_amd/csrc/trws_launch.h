@@ -6,9 +6,32 @@
 
 #include <cstddef>
 
+#include "common.h"
 #include "trws_dev.h"
 
 namespace stereo {
+
+// The four sweep variants (BACKWARD, PRIMAL, UPDATE) in `what` order: X(BW, PR, UP, ...) once per variant.  A family
+// file builds its table of kernel addresses from this list exactly once -- one row of four per (smoothness kernel,
+// shared positions or message mode, plain / group / speculative entry) --, its *_set_attributes walks the table and its
+// launch_* index it, so the kernels that are launched and the kernels that got their LDS size are the same by
+// construction.
+#define TRWS_SWEEP_VARIANTS(X, ...) \
+  X(false, false, true, __VA_ARGS__) X(true, false, true, __VA_ARGS__) X(false, true, true, __VA_ARGS__) X(false, true, false, __VA_ARGS__)
+typedef const void *SweepRow[4];
+
+// every kernel of `rows` may use `bytes` of dynamic LDS (above 64 KB a kernel without this fails at launch)
+inline void set_max_dynamic_lds(const SweepRow *rows, int nrows, int bytes) {
+  for (int r = 0; r < nrows; ++r)
+    for (const void *k : rows[r]) STEREO_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+}
+// launches row[what] with (arg, epoch); arg: DevParams, or GroupArgs for the group kernels
+template <class Arg>
+inline void launch_sweep(const SweepRow &row, int what, int blocks, int threads, size_t lds, hipStream_t s, const Arg &arg, int epoch) {
+  void *args[] = {(void *)&arg, (void *)&epoch};
+  STEREO_HIP_CHECK(hipLaunchKernel(row[what >= 0 && what < 3 ? what : 3], dim3(blocks), dim3(threads), args, lds, s));
+  STEREO_HIP_CHECK(hipGetLastError());
+}
 
 size_t generic_lds_bytes(int Kp);
 void generic_set_attributes(int lds);

@@ -1,5 +1,5 @@
 // TRW-S pipelined sweep kernel for K <= 64 (both smoothness kernels): role-specialised waves, one
-// barrier per visit.  Part of libstereo_hip.so; overview in trws_plan.hip.
+// barrier per visit.  Part of libstereo_hip.so; overview in DESIGN.md 4.1, the run and visit frame in trws_visit.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -9,6 +9,7 @@
 #include "trws_dev.h"
 #include "trws_launch.h"
 #include "trws_spec.h"
+#include "trws_visit.h"
 
 namespace stereo {
 namespace {
@@ -125,32 +126,23 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
 
   for (;;) {
     // (ctl[3]: the workgroup walks the speculative segment it holds a second time -- no new ticket)
-    if (tid == 0 && !(SPEC && (ctl[3] || have_ticket))) { const int t_ = atomicAdd(p.ticket, 1); ctl[0] = t_ < p.ntickets[D] ? (p.run_order[D] ? p.run_order[D][t_] : t_) : p.nruns[D]; }
+    TRWS_DRAW_TICKET(ctl, SPEC && (ctl[3] || have_ticket))
     have_ticket = false;
-    __syncthreads();
-    const int run = __builtin_amdgcn_readfirstlane(ctl[0]);
-    const int second_walk = SPEC ? __builtin_amdgcn_readfirstlane(ctl[3]) : 0;
     // (the helpers' exchange flags show schedule positions: a second walk of a speculative segment visits the SAME
     //  positions again, and a flag left by the first walk would pass for the helper's word of the second -- the
-    //  finishing wave would merge the first walk's partial minima, which are those of almost the same message.
-    //  Every wave is behind the last visit's barrier here: nothing is being published or collected.)
-    if (tid < kPipeCompute && !(p.debug & 131072)) xflag[tid] = 0;   // (development switch 131072: flags left as they are)
-    __syncthreads();
-    if (SPEC && tid == 0) ctl[3] = 0;
-    if (run >= p.nruns[D]) break;
-    if (SPEC && run < 0) continue;   // (the runner's ticket is ticket 0: drawn and served above)
-    const int p0 = p.run_ptr[D][run], p1 = p.run_ptr[D][run + 1];
-    // a segment of the speculative schedule (trws_graph.h: Sweep::Spec): its first visit takes what the node in front
-    // hands over from the runner's rows, its completion flags wait for the commit below the visit loops
-    const int seg = (SPEC && p.spec_kind[D]) ? __builtin_amdgcn_readfirstlane(p.spec_kind[D][run]) - 1 : -1;
+    //  finishing wave would merge the first walk's partial minima, which are those of almost the same message.)
+    //  (development switch 131072: flags left as they are)
+    TRWS_RUN_ENTER(SPEC, ctl, if (tid < kPipeCompute && !(p.debug & 131072)) xflag[tid] = 0;)
+    TRWS_SPEC_SEGMENT
     unsigned long long busy = 0;
 #ifdef STEREO_HIP_VISIT_PROFILE
     unsigned long long vacc[6] = {0, 0, 0, 0, 0, 0}, macc[5] = {0, 0, 0, 0, 0}, lacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define VSTAMP(i) do { const long long n_ = (long long)__builtin_readcyclecounter(); vacc[i] += (unsigned long long)(n_ - vmark); vmark = n_; } while (0)
+#define PIPE_VISIT_MARK long long vmark = (long long)__builtin_readcyclecounter();
 #else
 #define VSTAMP(i) do { } while (0)
+#define PIPE_VISIT_MARK
 #endif
-    const bool spec_in = SPEC && seg > 0 && !second_walk;
     int xprev = 0, xprev2 = 0;  // primal wave: labels of the previous two nodes of the run
     int wnext = 0;              // loader: raw descriptor word of the node after next (prefetched)
     if (wave == kPipeCompute) wnext = desc[(size_t)p0 * DW + lane];
@@ -182,34 +174,14 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
     }
     if (p.timeline && tid == 0) p.timeline[((size_t)D * p.tl_stride + run) * 2] = wall_clock64();
 
-    // Every role walks the run in its own loop -- the same visits, the same barrier at the end of each: the hardware
-    // barrier counts arrivals, whichever s_barrier instruction a wave arrives at -- so that what one role keeps across
-    // visits (the loaders' parked requests and descriptor words, the primal wave's labels) and the kernel parameters it
-    // uses are live in ITS loop only: in one loop for all roles the function sat at the scalar-register limit, ~300
-    // scalars spilled into VGPR lanes, and every edit anywhere moved spill code onto the compute waves' path.
+    // every role walks the run in its own loop (trws_visit.h): four ring slots, the abort word looked at before the barrier
+#define PIPE_VISITS_BEGIN \
+    TRWS_VISITS_BEGIN(TRWS_BUSY_OPEN PIPE_VISIT_MARK, stage0, kStageDoubles, TRWS_RING4(hand, kWave), scal, TRWS_ABORT_LOOK(ctl) TRWS_OPAQUE_K)
+#define PIPE_VISITS_END \
+    TRWS_VISITS_END(TRWS_BUSY_CLOSE VSTAMP(4);, TRWS_ABORT_LEAVE(aborted_, ), __syncthreads(), VSTAMP(5);)
     if (wave < kPipeCompute) {
     // ---- compute
-    for (int pos = p0 - 1; pos <= p1; ++pos) {
-      const long long tstart = p.prof ? (long long)__builtin_readcyclecounter() : 0;
-#ifdef STEREO_HIP_VISIT_PROFILE
-      long long vmark = (long long)__builtin_readcyclecounter();
-#endif
-      double *st = stage0 + (pos & 1) * kStageDoubles;          // node `pos`
-      double *stn = stage0 + ((pos + 1) & 1) * kStageDoubles;   // node `pos + 1`
-      double *hcur = hand + (pos & 3) * 8 * kWave, *hprev = hand + ((pos - 1) & 3) * 8 * kWave;
-      double *sc = scal + (pos & 1) * kScalDoubles;
-      const bool have_node = pos >= p0 && pos < p1;
-      // (the workgroup's abort word -- a loader's wait gave up during the PREVIOUS visit -- is requested here and
-      //  looked at in front of the barrier that ends this visit: read behind that barrier, as it used to be, its
-      //  LDS round trip was the first thing on every wave's path into the next visit)
-      const int aborted = __hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      // (opaque copies, renewed every visit: what is derived from them -- per-lane row bases, the label-count
-      //  tests of the envelope code, ... -- is recomputed where it is used, one instruction each; left visible as
-      //  loop invariants, the compiler hoists dozens of such values out of the visit loop and keeps them in
-      //  spilled registers, scalar ones in VGPR lanes, vector ones in scratch memory)
-      int Kv = K;
-      asm volatile("" : "+s"(Kv));
-      const int lkv = lane < Kv ? lane : Kv - 1;
+    PIPE_VISITS_BEGIN
       {
         // ------------------------------------------------------------ compute
         if (UPDATE && have_node) {
@@ -305,35 +277,10 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
           }
         }
       }
-      if (p.prof) busy += (unsigned long long)((long long)__builtin_readcyclecounter() - tstart);
-      VSTAMP(4);
-      if (aborted) return;  // a dependency wait gave up (bounded spin); host reports it
-      __syncthreads();
-      VSTAMP(5);
-    }
+    PIPE_VISITS_END
     } else if (wave == kPipeCompute) {
     // ---- loader: stage node pos + 1
-    for (int pos = p0 - 1; pos <= p1; ++pos) {
-      const long long tstart = p.prof ? (long long)__builtin_readcyclecounter() : 0;
-#ifdef STEREO_HIP_VISIT_PROFILE
-      long long vmark = (long long)__builtin_readcyclecounter();
-#endif
-      double *st = stage0 + (pos & 1) * kStageDoubles;          // node `pos`
-      double *stn = stage0 + ((pos + 1) & 1) * kStageDoubles;   // node `pos + 1`
-      double *hcur = hand + (pos & 3) * 8 * kWave, *hprev = hand + ((pos - 1) & 3) * 8 * kWave;
-      double *sc = scal + (pos & 1) * kScalDoubles;
-      const bool have_node = pos >= p0 && pos < p1;
-      // (the workgroup's abort word -- a loader's wait gave up during the PREVIOUS visit -- is requested here and
-      //  looked at in front of the barrier that ends this visit: read behind that barrier, as it used to be, its
-      //  LDS round trip was the first thing on every wave's path into the next visit)
-      const int aborted = __hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      // (opaque copies, renewed every visit: what is derived from them -- per-lane row bases, the label-count
-      //  tests of the envelope code, ... -- is recomputed where it is used, one instruction each; left visible as
-      //  loop invariants, the compiler hoists dozens of such values out of the visit loop and keeps them in
-      //  spilled registers, scalar ones in VGPR lanes, vector ones in scratch memory)
-      int Kv = K;
-      asm volatile("" : "+s"(Kv));
-      const int lkv = lane < Kv ? lane : Kv - 1;
+    PIPE_VISITS_BEGIN
       {
         // ------------------------------------------------------------ loader: stage node pos + 1
         if (pos + 1 >= p0 && pos + 1 < p1) {
@@ -477,35 +424,10 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
 #endif
         }
       }
-      if (p.prof) busy += (unsigned long long)((long long)__builtin_readcyclecounter() - tstart);
-      VSTAMP(4);
-      if (aborted) return;  // a dependency wait gave up (bounded spin); host reports it
-      __syncthreads();
-      VSTAMP(5);
-    }
+    PIPE_VISITS_END
     } else if (wave == kPipeCompute + 2) {
     // ---- loader A: own data of node pos + 1
-    for (int pos = p0 - 1; pos <= p1; ++pos) {
-      const long long tstart = p.prof ? (long long)__builtin_readcyclecounter() : 0;
-#ifdef STEREO_HIP_VISIT_PROFILE
-      long long vmark = (long long)__builtin_readcyclecounter();
-#endif
-      double *st = stage0 + (pos & 1) * kStageDoubles;          // node `pos`
-      double *stn = stage0 + ((pos + 1) & 1) * kStageDoubles;   // node `pos + 1`
-      double *hcur = hand + (pos & 3) * 8 * kWave, *hprev = hand + ((pos - 1) & 3) * 8 * kWave;
-      double *sc = scal + (pos & 1) * kScalDoubles;
-      const bool have_node = pos >= p0 && pos < p1;
-      // (the workgroup's abort word -- a loader's wait gave up during the PREVIOUS visit -- is requested here and
-      //  looked at in front of the barrier that ends this visit: read behind that barrier, as it used to be, its
-      //  LDS round trip was the first thing on every wave's path into the next visit)
-      const int aborted = __hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      // (opaque copies, renewed every visit: what is derived from them -- per-lane row bases, the label-count
-      //  tests of the envelope code, ... -- is recomputed where it is used, one instruction each; left visible as
-      //  loop invariants, the compiler hoists dozens of such values out of the visit loop and keeps them in
-      //  spilled registers, scalar ones in VGPR lanes, vector ones in scratch memory)
-      int Kv = K;
-      asm volatile("" : "+s"(Kv));
-      const int lkv = lane < Kv ? lane : Kv - 1;
+    PIPE_VISITS_BEGIN
       {
         // ------------------------------------------------------------ loader A: own data of node pos + 1
         // The registers hold what was requested during visit pos - 1 (its HBM latency lies behind a
@@ -557,35 +479,10 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
           if (pos + 2 < p1) PIPE_REQUEST_OWN(wa1);
         }
       }
-      if (p.prof) busy += (unsigned long long)((long long)__builtin_readcyclecounter() - tstart);
-      VSTAMP(4);
-      if (aborted) return;  // a dependency wait gave up (bounded spin); host reports it
-      __syncthreads();
-      VSTAMP(5);
-    }
+    PIPE_VISITS_END
     } else if (wave == kPipeCompute + 1) {
     // ---- storer: node pos - 1
-    for (int pos = p0 - 1; pos <= p1; ++pos) {
-      const long long tstart = p.prof ? (long long)__builtin_readcyclecounter() : 0;
-#ifdef STEREO_HIP_VISIT_PROFILE
-      long long vmark = (long long)__builtin_readcyclecounter();
-#endif
-      double *st = stage0 + (pos & 1) * kStageDoubles;          // node `pos`
-      double *stn = stage0 + ((pos + 1) & 1) * kStageDoubles;   // node `pos + 1`
-      double *hcur = hand + (pos & 3) * 8 * kWave, *hprev = hand + ((pos - 1) & 3) * 8 * kWave;
-      double *sc = scal + (pos & 1) * kScalDoubles;
-      const bool have_node = pos >= p0 && pos < p1;
-      // (the workgroup's abort word -- a loader's wait gave up during the PREVIOUS visit -- is requested here and
-      //  looked at in front of the barrier that ends this visit: read behind that barrier, as it used to be, its
-      //  LDS round trip was the first thing on every wave's path into the next visit)
-      const int aborted = __hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      // (opaque copies, renewed every visit: what is derived from them -- per-lane row bases, the label-count
-      //  tests of the envelope code, ... -- is recomputed where it is used, one instruction each; left visible as
-      //  loop invariants, the compiler hoists dozens of such values out of the visit loop and keeps them in
-      //  spilled registers, scalar ones in VGPR lanes, vector ones in scratch memory)
-      int Kv = K;
-      asm volatile("" : "+s"(Kv));
-      const int lkv = lane < Kv ? lane : Kv - 1;
+    PIPE_VISITS_BEGIN
       {
         // ------------------------------------------------------------ storer: node pos - 1
         // The node's descriptor word is in a register since the previous visit (below) and nothing but the
@@ -646,35 +543,10 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
           sw = dring[(pos % 3) * kWave + lane];
         }
       }
-      if (p.prof) busy += (unsigned long long)((long long)__builtin_readcyclecounter() - tstart);
-      VSTAMP(4);
-      if (aborted) return;  // a dependency wait gave up (bounded spin); host reports it
-      __syncthreads();
-      VSTAMP(5);
-    }
+    PIPE_VISITS_END
     } else {
     // ---- primal of node pos
-    for (int pos = p0 - 1; pos <= p1; ++pos) {
-      const long long tstart = p.prof ? (long long)__builtin_readcyclecounter() : 0;
-#ifdef STEREO_HIP_VISIT_PROFILE
-      long long vmark = (long long)__builtin_readcyclecounter();
-#endif
-      double *st = stage0 + (pos & 1) * kStageDoubles;          // node `pos`
-      double *stn = stage0 + ((pos + 1) & 1) * kStageDoubles;   // node `pos + 1`
-      double *hcur = hand + (pos & 3) * 8 * kWave, *hprev = hand + ((pos - 1) & 3) * 8 * kWave;
-      double *sc = scal + (pos & 1) * kScalDoubles;
-      const bool have_node = pos >= p0 && pos < p1;
-      // (the workgroup's abort word -- a loader's wait gave up during the PREVIOUS visit -- is requested here and
-      //  looked at in front of the barrier that ends this visit: read behind that barrier, as it used to be, its
-      //  LDS round trip was the first thing on every wave's path into the next visit)
-      const int aborted = __hip_atomic_load(ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      // (opaque copies, renewed every visit: what is derived from them -- per-lane row bases, the label-count
-      //  tests of the envelope code, ... -- is recomputed where it is used, one instruction each; left visible as
-      //  loop invariants, the compiler hoists dozens of such values out of the visit loop and keeps them in
-      //  spilled registers, scalar ones in VGPR lanes, vector ones in scratch memory)
-      int Kv = K;
-      asm volatile("" : "+s"(Kv));
-      const int lkv = lane < Kv ? lane : Kv - 1;
+    PIPE_VISITS_BEGIN
       {
         // ------------------------------------------------------------ primal of node pos
         if (PRIMAL && have_node) {
@@ -719,13 +591,10 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
           }
         }
       }
-      if (p.prof) busy += (unsigned long long)((long long)__builtin_readcyclecounter() - tstart);
-      VSTAMP(4);
-      if (aborted) return;  // a dependency wait gave up (bounded spin); host reports it
-      __syncthreads();
-      VSTAMP(5);
+    PIPE_VISITS_END
     }
-    }
+#undef PIPE_VISITS_BEGIN
+#undef PIPE_VISITS_END
     if (SPEC && seg >= 0) {
       const int verdict = spec_commit<1, kPipeWaves, 2, BACKWARD, PRIMAL, UPDATE>(p.self, epoch, p0, p1, seg, spec_in ? 1 : 0, 2 * kPipeCtlOff);
       if (verdict == 2) return;
@@ -766,6 +635,7 @@ __global__ __launch_bounds__(kPipeThreads) void trws_pipe_group_kernel(GroupArgs
 #undef PIPE_REQUEST_OWN
 #undef PIPE_LOAD8
 #undef VSTAMP
+#undef PIPE_VISIT_MARK
 #undef PIPE_ROW
 #undef RLI
 
@@ -779,62 +649,32 @@ size_t pipe_lds_bytes() {
 size_t pipe_spec_lds_bytes() { return sizeof(double) * (kRunBase + kRunDoubles + kRunDummy); }   // ... with the runner's ring behind
 int pipe_threads() { return kPipeThreads; }
 
-void pipe_set_attributes() {
-  const int lds = (int)pipe_lds_bytes(), slds = (int)pipe_spec_lds_bytes();
-#define SET_S(BW, PR, UP) STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)trws_pipe_spec_kernel<BW, PR, UP>, hipFuncAttributeMaxDynamicSharedMemorySize, slds))
-  SET_S(false, false, true); SET_S(true, false, true); SET_S(false, true, true); SET_S(false, true, false);
-#undef SET_S
-#define SET_P(KER, BW, PR, UP)                                                                                                          \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)trws_pipe_kernel<KER, BW, PR, UP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));        \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)trws_pipe_kernel<KER, BW, PR, UP, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));       \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)trws_pipe_group_kernel<KER, BW, PR, UP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));  \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)trws_pipe_group_kernel<KER, BW, PR, UP, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-  SET_P(1, false, false, true); SET_P(1, true, false, true); SET_P(1, false, true, true); SET_P(1, false, true, false);
-  SET_P(2, false, false, true); SET_P(2, true, false, true); SET_P(2, false, true, true); SET_P(2, false, true, false);
-#undef SET_P
-}
+// rows: [smoothness kernel 1 | 2][per-edge | shared positions][plain | group], then the speculative schedule's kernel
+#define PIPE_ENTRY(BW, PR, UP, NAME, KER, SH) (const void *)NAME<KER, BW, PR, UP, SH>,
+#define PIPE_SPEC_ENTRY(BW, PR, UP, ...) (const void *)trws_pipe_spec_kernel<BW, PR, UP>,
+#define PIPE_ROWS(KER, SH) {TRWS_SWEEP_VARIANTS(PIPE_ENTRY, trws_pipe_kernel, KER, SH)}, {TRWS_SWEEP_VARIANTS(PIPE_ENTRY, trws_pipe_group_kernel, KER, SH)}
+constexpr int kPipeSpecRow = 8;
+static const SweepRow kPipeKernels[kPipeSpecRow + 1] = {PIPE_ROWS(1, false), PIPE_ROWS(1, true), PIPE_ROWS(2, false), PIPE_ROWS(2, true),
+                                                        {TRWS_SWEEP_VARIANTS(PIPE_SPEC_ENTRY)}};
+#undef PIPE_ROWS
+#undef PIPE_SPEC_ENTRY
+#undef PIPE_ENTRY
+static int pipe_row(int kernel, bool shared, bool group) { return ((kernel == 1 ? 0 : 1) * 2 + (shared ? 1 : 0)) * 2 + (group ? 1 : 0); }
 
-#define PIPE_SWITCH(NAME, ARG)                                                                                          \
-  const size_t plds = pipe_lds_bytes();                                                                                 \
-  const dim3 grid(blocks), block(kPipeThreads);                                                                         \
-  _Pragma("clang diagnostic push")                                                                                      \
-  if (kernel == 1) { PIPE4(NAME, 1, ARG) } else { PIPE4(NAME, 2, ARG) }                                                 \
-  _Pragma("clang diagnostic pop")                                                                                       \
-  STEREO_HIP_CHECK(hipGetLastError());
-#define PIPE1(NAME, KER, BW, PR, UP, ARG)                                                                               \
-  do {                                                                                                                  \
-    if (shared) hipLaunchKernelGGL((NAME<KER, BW, PR, UP, true>), grid, block, plds, s, ARG, epoch);                     \
-    else hipLaunchKernelGGL((NAME<KER, BW, PR, UP, false>), grid, block, plds, s, ARG, epoch);                           \
-  } while (0)
-#define PIPE4(NAME, KER, ARG)                                                                                           \
-  switch (what) {                                                                                                       \
-    case 0: PIPE1(NAME, KER, false, false, true, ARG); break;                                                           \
-    case 1: PIPE1(NAME, KER, true, false, true, ARG); break;                                                            \
-    case 2: PIPE1(NAME, KER, false, true, true, ARG); break;                                                            \
-    default: PIPE1(NAME, KER, false, true, false, ARG); break;                                                          \
-  }
+void pipe_set_attributes() {
+  set_max_dynamic_lds(kPipeKernels, kPipeSpecRow, (int)pipe_lds_bytes());
+  set_max_dynamic_lds(kPipeKernels + kPipeSpecRow, 1, (int)pipe_spec_lds_bytes());
+}
 
 void launch_pipe(int kernel, bool shared, int what, int blocks, hipStream_t s, const DevParams &p, int epoch) {
-  if (p.spec_kind[0] != nullptr && p.spec_kind[1] != nullptr && kernel == 1 && shared) {
-    // the speculative schedule's kernel (the runner's LDS lies behind the visits')
-    const size_t slds = pipe_spec_lds_bytes();
-    const dim3 grid(blocks), block(kPipeThreads);
-    switch (what) {
-      case 0: hipLaunchKernelGGL((trws_pipe_spec_kernel<false, false, true>), grid, block, slds, s, p, epoch); break;
-      case 1: hipLaunchKernelGGL((trws_pipe_spec_kernel<true, false, true>), grid, block, slds, s, p, epoch); break;
-      case 2: hipLaunchKernelGGL((trws_pipe_spec_kernel<false, true, true>), grid, block, slds, s, p, epoch); break;
-      default: hipLaunchKernelGGL((trws_pipe_spec_kernel<false, true, false>), grid, block, slds, s, p, epoch); break;
-    }
-    STEREO_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  PIPE_SWITCH(trws_pipe_kernel, p)
+  // the speculative schedule's kernel (the runner's LDS lies behind the visits')
+  if (p.spec_kind[0] != nullptr && p.spec_kind[1] != nullptr && kernel == 1 && shared)
+    return launch_sweep(kPipeKernels[kPipeSpecRow], what, blocks, kPipeThreads, pipe_spec_lds_bytes(), s, p, epoch);
+  launch_sweep(kPipeKernels[pipe_row(kernel, shared, false)], what, blocks, kPipeThreads, pipe_lds_bytes(), s, p, epoch);
 }
 void launch_pipe_group(int kernel, bool shared, int what, int blocks, hipStream_t s, const GroupArgs &ga, int epoch) {
-  PIPE_SWITCH(trws_pipe_group_kernel, ga)   // (strips keep the plain chain schedule)
+  // (strips keep the plain chain schedule)
+  launch_sweep(kPipeKernels[pipe_row(kernel, shared, true)], what, blocks, kPipeThreads, pipe_lds_bytes(), s, ga, epoch);
 }
-#undef PIPE4
-#undef PIPE1
-#undef PIPE_SWITCH
 
 }  // namespace stereo

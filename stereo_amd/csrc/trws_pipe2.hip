@@ -1,5 +1,6 @@
 // TRW-S pipelined sweep kernel for 64 < K <= 128 with per-edge positions (two labels per lane), both smoothness
-// kernels (the quadratic one since round 5).  Part of libstereo_hip.so; overview in trws_plan.hip.
+// kernels (the quadratic one since round 5).  Part of libstereo_hip.so; overview in DESIGN.md 4.1, the run and visit
+// frame in trws_visit.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -8,6 +9,7 @@
 #include "common.h"
 #include "trws_dev.h"
 #include "trws_launch.h"
+#include "trws_visit.h"
 
 namespace stereo {
 namespace {
@@ -54,28 +56,21 @@ __device__ __forceinline__ void pipe2_body(DevParams p, int epoch) {
   if (tid == 0) ctl[1] = 0;
 
   for (;;) {
-    if (tid == 0) { const int t_ = atomicAdd(p.ticket, 1); ctl[0] = t_ < p.ntickets[D] ? (p.run_order[D] ? p.run_order[D][t_] : t_) : p.nruns[D]; }
-    __syncthreads();
-    const int run = __builtin_amdgcn_readfirstlane(ctl[0]);
-    __syncthreads();
-    if (run >= p.nruns[D]) break;
-    const int p0 = p.run_ptr[D][run], p1 = p.run_ptr[D][run + 1];
+    TRWS_DRAW_TICKET(ctl, false)
+    TRWS_RUN_ENTER(false, ctl, )
     int xprev = 0, xprev2 = 0;
     int wnext = 0;
     if (wave == kPipeCompute) wnext = desc[(size_t)p0 * DW + lane];
     if (p.timeline && tid == 0) p.timeline[((size_t)D * p.tl_stride + run) * 2] = wall_clock64();
 
     unsigned long long busy = 0;  // development profile (STEREO_HIP_TRWS_PROF): cycles from barrier to barrier arrival
-    // (every role walks the run in its own loop, as in trws_pipe.hip: the same visits, the same barrier, registers per role)
+    // (every role walks the run in its own loop, trws_visit.h; the abort word is still read BEHIND the visit's barrier here)
+#define PIPE2_VISITS_BEGIN TRWS_VISITS_BEGIN(TRWS_BUSY_OPEN, stage0, k2Stage, TRWS_RING4(hand, k2W), scal, )
+#define PIPE2_VISITS_END \
+    TRWS_VISITS_END(TRWS_BUSY_CLOSE, , __syncthreads(), TRWS_ABORT_LEAVE(ctl[1], if (tid == 0) st_sc1(p.abort_flag, 1);))
     if (wave < kPipeCompute) {
     // ---- compute
-    for (int pos = p0 - 1; pos <= p1; ++pos) {
-      const long long tstart = p.prof ? (long long)__builtin_readcyclecounter() : 0;
-      double *st = stage0 + (pos & 1) * k2Stage;
-      double *stn = stage0 + ((pos + 1) & 1) * k2Stage;
-      double *hcur = hand + (pos & 3) * 8 * k2W, *hprev = hand + ((pos - 1) & 3) * 8 * k2W;
-      double *sc = scal + (pos & 1) * kScalDoubles;
-      const bool have_node = pos >= p0 && pos < p1;
+    PIPE2_VISITS_BEGIN
       {
         // ------------------------------------------------------------ compute
         if (UPDATE && have_node) {
@@ -290,22 +285,10 @@ __device__ __forceinline__ void pipe2_body(DevParams p, int epoch) {
           }
         }
       }
-      if (p.prof) busy += (unsigned long long)((long long)__builtin_readcyclecounter() - tstart);
-      __syncthreads();
-      if (ctl[1]) {
-        if (tid == 0) st_sc1(p.abort_flag, 1);
-        return;
-      }
-    }
+    PIPE2_VISITS_END
     } else if (wave == kPipeCompute) {
     // ---- loader: stage node pos + 1
-    for (int pos = p0 - 1; pos <= p1; ++pos) {
-      const long long tstart = p.prof ? (long long)__builtin_readcyclecounter() : 0;
-      double *st = stage0 + (pos & 1) * k2Stage;
-      double *stn = stage0 + ((pos + 1) & 1) * k2Stage;
-      double *hcur = hand + (pos & 3) * 8 * k2W, *hprev = hand + ((pos - 1) & 3) * 8 * k2W;
-      double *sc = scal + (pos & 1) * kScalDoubles;
-      const bool have_node = pos >= p0 && pos < p1;
+    PIPE2_VISITS_BEGIN
       {
         // ------------------------------------------------------------ loader: stage node pos + 1
         if (pos + 1 >= p0 && pos + 1 < p1) {
@@ -377,22 +360,10 @@ __device__ __forceinline__ void pipe2_body(DevParams p, int epoch) {
           if (lane < 8) { stn[k2StA + lane] = av; stni[64 + lane] = pxv; }
         }
       }
-      if (p.prof) busy += (unsigned long long)((long long)__builtin_readcyclecounter() - tstart);
-      __syncthreads();
-      if (ctl[1]) {
-        if (tid == 0) st_sc1(p.abort_flag, 1);
-        return;
-      }
-    }
+    PIPE2_VISITS_END
     } else if (wave == kPipeCompute + 1) {
     // ---- storer: node pos - 1
-    for (int pos = p0 - 1; pos <= p1; ++pos) {
-      const long long tstart = p.prof ? (long long)__builtin_readcyclecounter() : 0;
-      double *st = stage0 + (pos & 1) * k2Stage;
-      double *stn = stage0 + ((pos + 1) & 1) * k2Stage;
-      double *hcur = hand + (pos & 3) * 8 * k2W, *hprev = hand + ((pos - 1) & 3) * 8 * k2W;
-      double *sc = scal + (pos & 1) * kScalDoubles;
-      const bool have_node = pos >= p0 && pos < p1;
+    PIPE2_VISITS_BEGIN
       {
         // ------------------------------------------------------------ storer: node pos - 1
         if (pos - 1 >= p0) {
@@ -427,22 +398,10 @@ __device__ __forceinline__ void pipe2_body(DevParams p, int epoch) {
           }
         }
       }
-      if (p.prof) busy += (unsigned long long)((long long)__builtin_readcyclecounter() - tstart);
-      __syncthreads();
-      if (ctl[1]) {
-        if (tid == 0) st_sc1(p.abort_flag, 1);
-        return;
-      }
-    }
+    PIPE2_VISITS_END
     } else if (wave == kPipeCompute + 3) {
     // ---- primal of node pos
-    for (int pos = p0 - 1; pos <= p1; ++pos) {
-      const long long tstart = p.prof ? (long long)__builtin_readcyclecounter() : 0;
-      double *st = stage0 + (pos & 1) * k2Stage;
-      double *stn = stage0 + ((pos + 1) & 1) * k2Stage;
-      double *hcur = hand + (pos & 3) * 8 * k2W, *hprev = hand + ((pos - 1) & 3) * 8 * k2W;
-      double *sc = scal + (pos & 1) * kScalDoubles;
-      const bool have_node = pos >= p0 && pos < p1;
+    PIPE2_VISITS_BEGIN
       {
         // ------------------------------------------------------------ primal of node pos
         if (PRIMAL && have_node) {
@@ -494,33 +453,14 @@ __device__ __forceinline__ void pipe2_body(DevParams p, int epoch) {
           if (lane == 0) { sc[9] = eb; ((int *)(sc + 10))[0] = bi; }
         }
       }
-      if (p.prof) busy += (unsigned long long)((long long)__builtin_readcyclecounter() - tstart);
-      __syncthreads();
-      if (ctl[1]) {
-        if (tid == 0) st_sc1(p.abort_flag, 1);
-        return;
-      }
-    }
+    PIPE2_VISITS_END
     } else {
     // ---- (idle wave)
-    for (int pos = p0 - 1; pos <= p1; ++pos) {
-      const long long tstart = p.prof ? (long long)__builtin_readcyclecounter() : 0;
-      double *st = stage0 + (pos & 1) * k2Stage;
-      double *stn = stage0 + ((pos + 1) & 1) * k2Stage;
-      double *hcur = hand + (pos & 3) * 8 * k2W, *hprev = hand + ((pos - 1) & 3) * 8 * k2W;
-      double *sc = scal + (pos & 1) * kScalDoubles;
-      const bool have_node = pos >= p0 && pos < p1;
-      {
-        (void)0;
-      }
-      if (p.prof) busy += (unsigned long long)((long long)__builtin_readcyclecounter() - tstart);
-      __syncthreads();
-      if (ctl[1]) {
-        if (tid == 0) st_sc1(p.abort_flag, 1);
-        return;
-      }
+    PIPE2_VISITS_BEGIN
+    PIPE2_VISITS_END
     }
-    }
+#undef PIPE2_VISITS_BEGIN
+#undef PIPE2_VISITS_END
     if (p.timeline && tid == 0) p.timeline[((size_t)D * p.tl_stride + run) * 2 + 1] = wall_clock64();
     if (p.prof && lane == 0 && (p.prof_run < 0 || run == p.prof_run)) {
       atomicAdd(p.prof + 32 + wave, busy);
@@ -544,46 +484,21 @@ __global__ __launch_bounds__(kPipeThreads) void trws_pipe2_group_kernel(GroupArg
 
 size_t pipe2_lds_bytes() { return sizeof(double) * k2LdsDoubles; }
 
-void pipe2_set_attributes() {
-  const int lds2 = (int)pipe2_lds_bytes();
-#define SET_LDS2(NAME, KER, SH)                                                                                                            \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<KER, false, false, true, SH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2)); \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<KER, true, false, true, SH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));  \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<KER, false, true, true, SH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2));  \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<KER, false, true, false, SH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2))
-  SET_LDS2(trws_pipe2_kernel, 1, true); SET_LDS2(trws_pipe2_kernel, 1, false);
-  SET_LDS2(trws_pipe2_group_kernel, 1, true); SET_LDS2(trws_pipe2_group_kernel, 1, false);
-  SET_LDS2(trws_pipe2_kernel, 2, true); SET_LDS2(trws_pipe2_kernel, 2, false);
-  SET_LDS2(trws_pipe2_group_kernel, 2, true); SET_LDS2(trws_pipe2_group_kernel, 2, false);
-#undef SET_LDS2
-}
+// rows: [smoothness kernel 1 | 2][per-edge | shared positions][plain | group]
+#define PIPE2_ENTRY(BW, PR, UP, NAME, KER, SH) (const void *)NAME<KER, BW, PR, UP, SH>,
+#define PIPE2_ROWS(KER, SH) {TRWS_SWEEP_VARIANTS(PIPE2_ENTRY, trws_pipe2_kernel, KER, SH)}, {TRWS_SWEEP_VARIANTS(PIPE2_ENTRY, trws_pipe2_group_kernel, KER, SH)}
+static const SweepRow kPipe2Kernels[8] = {PIPE2_ROWS(1, false), PIPE2_ROWS(1, true), PIPE2_ROWS(2, false), PIPE2_ROWS(2, true)};
+#undef PIPE2_ROWS
+#undef PIPE2_ENTRY
+static int pipe2_row(int kernel, bool shared, bool group) { return ((kernel == 1 ? 0 : 1) * 2 + (shared ? 1 : 0)) * 2 + (group ? 1 : 0); }
 
-#define PIPE2_SWITCH(NAME, ARG)                                                                   \
-  const size_t lds2 = pipe2_lds_bytes();                                                          \
-  const dim3 grid2(blocks), block2(kPipeThreads);                                                 \
-  if (kernel == 1) { PIPE2_4(NAME, 1, ARG) } else { PIPE2_4(NAME, 2, ARG) }                       \
-  STEREO_HIP_CHECK(hipGetLastError());
-#define PIPE2_4(NAME, KER, ARG)                                                                   \
-  switch (what) {                                                                                 \
-    case 0: PIPE2(NAME, KER, false, false, true, ARG); break;                                     \
-    case 1: PIPE2(NAME, KER, true, false, true, ARG); break;                                      \
-    case 2: PIPE2(NAME, KER, false, true, true, ARG); break;                                      \
-    default: PIPE2(NAME, KER, false, true, false, ARG); break;                                    \
-  }
-#define PIPE2(NAME, KER, BW, PR, UP, ARG)                                                         \
-  do {                                                                                            \
-    if (shared) hipLaunchKernelGGL((NAME<KER, BW, PR, UP, true>), grid2, block2, lds2, s, ARG, epoch);  \
-    else hipLaunchKernelGGL((NAME<KER, BW, PR, UP, false>), grid2, block2, lds2, s, ARG, epoch);        \
-  } while (0)
+void pipe2_set_attributes() { set_max_dynamic_lds(kPipe2Kernels, 8, (int)pipe2_lds_bytes()); }
 
 void launch_pipe2(int kernel, bool shared, int what, int blocks, hipStream_t s, const DevParams &p, int epoch) {
-  PIPE2_SWITCH(trws_pipe2_kernel, p)
+  launch_sweep(kPipe2Kernels[pipe2_row(kernel, shared, false)], what, blocks, kPipeThreads, pipe2_lds_bytes(), s, p, epoch);
 }
 void launch_pipe2_group(int kernel, bool shared, int what, int blocks, hipStream_t s, const GroupArgs &ga, int epoch) {
-  PIPE2_SWITCH(trws_pipe2_group_kernel, ga)
+  launch_sweep(kPipe2Kernels[pipe2_row(kernel, shared, true)], what, blocks, kPipeThreads, pipe2_lds_bytes(), s, ga, epoch);
 }
-#undef PIPE2_4
-#undef PIPE2
-#undef PIPE2_SWITCH
 
 }  // namespace stereo

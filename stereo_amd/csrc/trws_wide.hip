@@ -1,5 +1,6 @@
 // TRW-S pipelined sweep kernel for 64 < K <= 256 on shared strictly ascending positions (the large
-// grids), linear kernel.  Part of libstereo_hip.so; overview in trws_plan.hip.
+// grids), linear kernel.  Part of libstereo_hip.so; overview in DESIGN.md 4.1 and 4.3, the run and visit frame in
+// trws_visit.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -8,6 +9,7 @@
 #include "common.h"
 #include "trws_dev.h"
 #include "trws_launch.h"
+#include "trws_visit.h"
 #include "trws_wspec.h"
 
 namespace stereo {
@@ -284,55 +286,32 @@ __device__ __forceinline__ void wide_body(DevParams p, int epoch) {
 
   for (;;) {
     // (ctl[3]: the workgroup walks the speculative segment it holds a second time -- no new ticket)
-    if (tid == 0 && !(SPEC && (L.ctl[3] || have_ticket))) { const int t_ = atomicAdd(p.ticket, 1); L.ctl[0] = t_ < p.ntickets[D] ? (p.run_order[D] ? p.run_order[D][t_] : t_) : p.nruns[D]; }
+    TRWS_DRAW_TICKET(L.ctl, SPEC && (L.ctl[3] || have_ticket))
     have_ticket = false;
-    __syncthreads();
-    const int run = __builtin_amdgcn_readfirstlane(L.ctl[0]);
-    const int second_walk = SPEC ? __builtin_amdgcn_readfirstlane(L.ctl[3]) : 0;
     // (the twins' exchange flags show schedule positions: a second walk visits the same positions, see trws_pipe.hip)
-    if (SPEC && tid < kWideCompute) L.xflag[tid] = 0;
-    __syncthreads();
-    if (SPEC && tid == 0) L.ctl[3] = 0;
-    if (run >= p.nruns[D]) break;
-    if (SPEC && run < 0) continue;   // (the runner's ticket is ticket 0: drawn and served above)
-    const int p0 = p.run_ptr[D][run], p1 = p.run_ptr[D][run + 1];
-    // a segment of the speculative schedule: its first visit takes what the node in front hands over from the runner's
-    // rows, its completion flags wait for the commit below the visit loops
-    const int seg = (SPEC && p.spec_kind[D]) ? __builtin_amdgcn_readfirstlane(p.spec_kind[D][run]) - 1 : -1;
-    const bool spec_in = SPEC && seg > 0 && !second_walk;
-    (void)spec_in;
+    TRWS_RUN_ENTER(SPEC, L.ctl, if (SPEC && tid < kWideCompute) L.xflag[tid] = 0;)
+    TRWS_SPEC_SEGMENT
     const bool wprof = WIDE_PROF(p) && (p.prof_run < 0 || run == p.prof_run);  // STEREO_HIP_TRWS_PROF_RUN: one run only
     (void)wprof;
     if (p.timeline && tid == 0) p.timeline[((size_t)D * p.tl_stride + run) * 2] = wall_clock64();
 
-    // One visit loop per role (not one loop with a role switch inside): state carried from visit
-    // to visit -- the loader's parked registers -- then occupies registers in that role only.
-#define WIDE_VISITS_BEGIN     for (int pos = p0 - 1; pos <= p1; ++pos) { \
-      double *st = L.stage0 + (pos & 1) * kWStage; \
-      double *stn = L.stage0 + ((pos + 1) & 1) * kWStage; \
-      const int hb = ((pos % 3) + 3) % 3, hb1 = (((pos - 1) % 3) + 3) % 3, hb2 = (((pos - 2) % 3) + 3) % 3; \
-      double *hcur = L.hand + hb * 8 * kWS, *hprev = L.hand + hb1 * 8 * kWS, *hprev2 = L.hand + hb2 * 8 * kWS; \
-      double *sc = L.scal + (pos & 1) * kScalDoubles; \
-      const bool have_node = pos >= p0 && pos < p1; \
-      const int aborted_ = __hip_atomic_load(L.ctl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); /* a loader's wait gave up during the previous visit */ \
+    // One visit loop per role (trws_visit.h): three ring slots, the abort word looked at before the barrier.
+#define WIDE_VISIT_MARK \
       long long tmark = wprof ? (long long)__builtin_readcyclecounter() : 0; \
       const long long tvisit = tmark; \
-      (void)st; (void)stn; (void)hcur; (void)hprev; (void)hprev2; (void)sc; (void)have_node; (void)tvisit;
-#define WIDE_VISITS_END_(BARRIER)       if (wprof) { \
+      (void)tvisit;
+#define WIDE_VISIT_CLOSE \
+      if (wprof) { \
         const long long now_ = (long long)__builtin_readcyclecounter(); \
         if (wave == 0) pvis += have_node ? 1 : 0; \
         pbusy += (unsigned long long)(now_ - tvisit); \
         if (now_ - tvisit > 8000) plate += 1; \
         tmark = now_; \
-      } \
-      if (aborted_) { /* (looked at in front of the barrier: behind it the LDS round trip was every wave's first step into the next visit) */ \
-        if (tid == 0) st_sc1(p.abort_flag, 1); \
-        return; \
-      } \
-      BARRIER; \
-      if (wprof && wave == 0) pwait += (unsigned long long)((long long)__builtin_readcyclecounter() - tmark); \
-    }
-#define WIDE_VISITS_END WIDE_VISITS_END_(__syncthreads())
+      }
+#define WIDE_VISITS_BEGIN TRWS_VISITS_BEGIN(, L.stage0, kWStage, TRWS_RING3(L.hand, kWS), L.scal, TRWS_ABORT_LOOK(L.ctl) WIDE_VISIT_MARK)
+#define WIDE_VISITS_END \
+    TRWS_VISITS_END(WIDE_VISIT_CLOSE, TRWS_ABORT_LEAVE(aborted_, if (tid == 0) st_sc1(p.abort_flag, 1);), __syncthreads(), \
+                    if (wprof && wave == 0) pwait += (unsigned long long)((long long)__builtin_readcyclecounter() - tmark);)
     if (wave < kWideCompute) {
       WIDE_VISITS_BEGIN
         // ======================================================== compute waves
@@ -1291,7 +1270,8 @@ __device__ __forceinline__ void wide_body(DevParams p, int epoch) {
     }
 #undef WIDE_VISITS_BEGIN
 #undef WIDE_VISITS_END
-#undef WIDE_VISITS_END_
+#undef WIDE_VISIT_MARK
+#undef WIDE_VISIT_CLOSE
     if (SPEC && seg >= 0) {
       // (verdict word: ctl[4], the first twin exchange flag, idle between visits)
       const int verdict = spec_commit<4, kWideWaves, 4, BACKWARD, PRIMAL, UPDATE>(p.self, epoch, p0, p1, seg, spec_in ? 1 : 0, (int)(L.ctl - (int *)lds));
@@ -1335,67 +1315,30 @@ size_t wide_lds_bytes() { return sizeof(double) * kWideLdsDoubles; }
 static_assert(kWrDoubles * 8 <= 160 * 1024, "wide runner LDS");
 size_t wide_spec_lds_bytes() { return sizeof(double) * (size_t)(kWideLdsDoubles > kWrDoubles ? kWideLdsDoubles : kWrDoubles); }
 
-void wide_set_attributes() {
-  const int wlds = (int)wide_lds_bytes();
-  {
-    const int slds = (int)wide_spec_lds_bytes();
-#define SET_S(BW, PR, UP) STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)trws_wide_spec_kernel<BW, PR, UP>, hipFuncAttributeMaxDynamicSharedMemorySize, slds))
-    SET_S(false, false, true); SET_S(true, false, true); SET_S(false, true, true); SET_S(false, true, false);
-#undef SET_S
-  }
-#define SET_W(NAME)                                                                                                             \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<1, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wlds)); \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<1, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wlds));  \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<1, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wlds));  \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<1, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, wlds))
-  SET_W(trws_wide_kernel); SET_W(trws_wide_group_kernel);
-#undef SET_W
-#define SET_W(NAME)                                                                                                             \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<2, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wlds)); \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<2, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wlds));  \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<2, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, wlds));  \
-  STEREO_HIP_CHECK(hipFuncSetAttribute((const void *)NAME<2, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, wlds))
-  SET_W(trws_wide_kernel); SET_W(trws_wide_group_kernel);
-#undef SET_W
-}
+// rows: [smoothness kernel 1 | 2][plain | group], then the speculative schedule's kernel
+#define WIDE_ENTRY(BW, PR, UP, NAME, KER) (const void *)NAME<KER, BW, PR, UP>,
+#define WIDE_SPEC_ENTRY(BW, PR, UP, ...) (const void *)trws_wide_spec_kernel<BW, PR, UP>,
+#define WIDE_ROWS(KER) {TRWS_SWEEP_VARIANTS(WIDE_ENTRY, trws_wide_kernel, KER)}, {TRWS_SWEEP_VARIANTS(WIDE_ENTRY, trws_wide_group_kernel, KER)}
+constexpr int kWideSpecRow = 4;
+static const SweepRow kWideKernels[kWideSpecRow + 1] = {WIDE_ROWS(1), WIDE_ROWS(2), {TRWS_SWEEP_VARIANTS(WIDE_SPEC_ENTRY)}};
+#undef WIDE_ROWS
+#undef WIDE_SPEC_ENTRY
+#undef WIDE_ENTRY
+static int wide_row(int kernel, bool group) { return (kernel == 2 ? 1 : 0) * 2 + (group ? 1 : 0); }
 
-#define WIDE_SWITCH(NAME, ARG)                                                                                     \
-  const size_t wlds = wide_lds_bytes();                                                                            \
-  const dim3 wgrid(blocks), wblock(kWideThreads);                                                                  \
-  if (kernel == 2) {                                                                                               \
-    switch (what) {                                                                                                \
-      case 0: hipLaunchKernelGGL((NAME<2, false, false, true>), wgrid, wblock, wlds, s, ARG, epoch); break;        \
-      case 1: hipLaunchKernelGGL((NAME<2, true, false, true>), wgrid, wblock, wlds, s, ARG, epoch); break;         \
-      case 2: hipLaunchKernelGGL((NAME<2, false, true, true>), wgrid, wblock, wlds, s, ARG, epoch); break;         \
-      default: hipLaunchKernelGGL((NAME<2, false, true, false>), wgrid, wblock, wlds, s, ARG, epoch); break;       \
-    }                                                                                                              \
-  } else {                                                                                                         \
-    switch (what) {                                                                                                \
-      case 0: hipLaunchKernelGGL((NAME<1, false, false, true>), wgrid, wblock, wlds, s, ARG, epoch); break;        \
-      case 1: hipLaunchKernelGGL((NAME<1, true, false, true>), wgrid, wblock, wlds, s, ARG, epoch); break;         \
-      case 2: hipLaunchKernelGGL((NAME<1, false, true, true>), wgrid, wblock, wlds, s, ARG, epoch); break;         \
-      default: hipLaunchKernelGGL((NAME<1, false, true, false>), wgrid, wblock, wlds, s, ARG, epoch); break;       \
-    }                                                                                                              \
-  }                                                                                                                \
-  STEREO_HIP_CHECK(hipGetLastError());
+void wide_set_attributes() {
+  set_max_dynamic_lds(kWideKernels, kWideSpecRow, (int)wide_lds_bytes());
+  set_max_dynamic_lds(kWideKernels + kWideSpecRow, 1, (int)wide_spec_lds_bytes());
+}
 
 void launch_wide(int kernel, int what, int blocks, hipStream_t s, const DevParams &p, int epoch) {
-  if (p.spec_kind[0] != nullptr && p.spec_kind[1] != nullptr && kernel == 1) {
-    // the speculative schedule's kernel
-    const size_t slds = wide_spec_lds_bytes();
-    const dim3 grid(blocks), block(kWideThreads);
-    switch (what) {
-      case 0: hipLaunchKernelGGL((trws_wide_spec_kernel<false, false, true>), grid, block, slds, s, p, epoch); break;
-      case 1: hipLaunchKernelGGL((trws_wide_spec_kernel<true, false, true>), grid, block, slds, s, p, epoch); break;
-      case 2: hipLaunchKernelGGL((trws_wide_spec_kernel<false, true, true>), grid, block, slds, s, p, epoch); break;
-      default: hipLaunchKernelGGL((trws_wide_spec_kernel<false, true, false>), grid, block, slds, s, p, epoch); break;
-    }
-    STEREO_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  WIDE_SWITCH(trws_wide_kernel, p)
+  // the speculative schedule's kernel
+  if (p.spec_kind[0] != nullptr && p.spec_kind[1] != nullptr && kernel == 1)
+    return launch_sweep(kWideKernels[kWideSpecRow], what, blocks, kWideThreads, wide_spec_lds_bytes(), s, p, epoch);
+  launch_sweep(kWideKernels[wide_row(kernel, false)], what, blocks, kWideThreads, wide_lds_bytes(), s, p, epoch);
 }
-void launch_wide_group(int kernel, int what, int blocks, hipStream_t s, const GroupArgs &ga, int epoch) { WIDE_SWITCH(trws_wide_group_kernel, ga) }
-#undef WIDE_SWITCH
+void launch_wide_group(int kernel, int what, int blocks, hipStream_t s, const GroupArgs &ga, int epoch) {
+  launch_sweep(kWideKernels[wide_row(kernel, true)], what, blocks, kWideThreads, wide_lds_bytes(), s, ga, epoch);
+}
 
 }  // namespace stereo
