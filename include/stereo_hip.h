@@ -27,8 +27,9 @@ extern "C" {
  * entry points select their plan's device, wall-clock bound on cross-workgroup waits.  4: stereo_fusion_fit_planes,
  * stereo_fusion_fuse_until_convergence.  5: stereo_segpln_wta, stereo_segpln_planes.  6: stereo_segment_* (the segmenters
  * behind dispmap_globalstereo), stereo_trws_plan_debug_terms / _messages, stereo_segpln_planes_batch.  7: TRW-S takes
- * up to 4096 labels with one shared strictly ascending positions vector (stereo_trws_plan_path 5). */
-#define STEREO_HIP_ABI_VERSION 7
+ * up to 4096 labels with one shared strictly ascending positions vector (stereo_trws_plan_path 5).  8: stereo_trws_batch_*
+ * (independent plans that share one launch per sweep). */
+#define STEREO_HIP_ABI_VERSION 8
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -284,6 +285,55 @@ int stereo_trws_plan_collect(stereo_trws_plan *plan, double *lower_bound_part, d
                              char *err, size_t errcap);
 int stereo_trws_plan_commit(stereo_trws_plan *plan, double lower_bound, double energy, char *err,
                             size_t errcap);
+/* ---- batches: independent problems that share one launch per sweep ----
+ * A sweep of one problem is bound by the dependency chain of its node order and leaves most of the device idle; a batch
+ * runs the sweeps of n <= 16 plans in one launch each, so that the idle compute units work on the other problems.
+ * Members are ordinary plans and stay the caller's: each keeps its own inputs, messages, labels, energy, bound and
+ * iteration count, results come from stereo_trws_plan_result per member, and every member computes bit for bit what
+ * stereo_trws_plan_iterate computes for it alone (its bound and energy are summed per member, in the single plan's
+ * order).  A member may be iterated alone between batch calls; it must outlive the batch's last call.
+ *
+ * create accepts plans that are whole problems (not strips) with inputs uploaded or bound, all on one device, all in
+ * one pipelined kernel family (stereo_trws_plan_path 2, 3 or 4), with the same smoothness kernel, message mode and kind
+ * of positions (one shared vector, or q / qprim per edge): one launch runs one sweep kernel.  K, the graph and its size
+ * may differ.  Everything else -- the generic or large family, mixed instantiations, a strip, a member without inputs
+ * or on another device, the same plan twice, n < 1 or n > 16 -- is refused with a message that names the offending
+ * member ("member <index> ...") and the reason; the plans are left as they were.  The rule is applied again by every
+ * iterate (an upload can move a plan to another family).
+ *
+ * K <= 64 (path 2): the launch's workgroups start on one member each and move on to the next member that has runs
+ * left when theirs has none, so members of unequal size share the device.  Paths 3 and 4 run one workgroup per compute
+ * unit: the launch's grid is divided statically, and a batch whose shares do not fit the device together is split into
+ * consecutive launches.  Shared launches keep the plain chain schedule: the speculative border-chain schedule of a
+ * single plan (stereo_trws_plan_spec_stats) is OFF inside them, like in a strip group; results do not depend on it.
+ * Where a shared launch is measured to lose against the plans iterated in turn -- one active member; fewer than 8
+ * members on path 2 that each have more runs than the device keeps workgroups resident -- iterate gives
+ * every member its own launches, one after the other, exactly as stereo_trws_plan_iterate does: same bits, same
+ * contract, and out[1] of stereo_trws_batch_stats does not count them.
+ * Node beliefs: a member with stereo_trws_plan_keep_min_marginals on gets its phase-1 launch in every batch iteration,
+ * between the backward and the fused launch as in stereo_trws_plan_iterate, and stereo_trws_plan_min_marginals after a
+ * batch iteration returns what it returns after the same iterations alone.
+ * A batch runs on the default (NULL) stream: the members' inputs must be complete there (bound arrays written on
+ * another stream need a synchronisation first).  Sweep timing (stereo_trws_plan_stats) is not defined for batch
+ * iterations: the launches belong to all members at once. */
+typedef struct stereo_trws_batch stereo_trws_batch;
+int stereo_trws_batch_create(stereo_trws_plan *const *plans, int n, stereo_trws_batch **out, char *err, size_t errcap);
+/* Frees the batch; the members are not touched. */
+void stereo_trws_batch_destroy(stereo_trws_batch *batch);
+/* Up to `iters` iterations of every member.  max_relgap applies PER MEMBER exactly as in stereo_trws_plan_iterate: a
+ * member whose (E - LB) / E falls below it stops and keeps its state, the others go on, the launches that follow leave
+ * it out, and it stays out of this batch's later calls until stereo_trws_batch_reset.  done_iters[i] (n entries, may be
+ * NULL): iterations member i ran in this call.  If a member's sweep gives up waiting, every member's iteration is
+ * collected first and the error names the member. */
+int stereo_trws_batch_iterate(stereo_trws_batch *batch, int iters, double max_relgap, int32_t *done_iters, char *err,
+                              size_t errcap);
+/* stereo_trws_plan_reset of every member; stopped members take part again; the batch's counters restart. */
+int stereo_trws_batch_reset(stereo_trws_batch *batch, char *err, size_t errcap);
+/* Diagnostics since creation / the last reset: out[0] workgroups that held runs of more than one member (read from the
+ * batch's control words on the device; 0 on paths 3 and 4), out[1] sweep launches issued (a split batch counts each
+ * part), out[2] 1 if the speculative schedule runs inside this batch (always 0), out[3] workgroups one launch keeps
+ * resident together. */
+int stereo_trws_batch_stats(stereo_trws_batch *batch, int64_t out[4]);
 /* What a strip stores.  nodes (n_nodes entries): global id of local node i -- the n_own own nodes
  * in ascending order, then the halo; edges (n_edges): global id of local edge e, ascending.  Any
  * output may be NULL (ask for the counts first).  A plan of the whole problem reports identity. */

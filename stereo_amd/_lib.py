@@ -15,7 +15,7 @@ _dp = C.POINTER(C.c_double)
 _u32p = C.POINTER(C.c_uint32)
 _i64p = C.POINTER(C.c_int64)
 
-ABI_VERSION = 7   # include/stereo_hip.h: STEREO_HIP_ABI_VERSION
+ABI_VERSION = 8   # include/stereo_hip.h: STEREO_HIP_ABI_VERSION
 
 _lib = None
 
@@ -44,6 +44,7 @@ def lib():
                                  "stereo_amd/csrc/build.sh" % (LIB_PATH, L.stereo_hip_abi_version(), ABI_VERSION))
         L.stereo_hip_last_error.restype = C.c_char_p
         L.stereo_trws_plan_destroy.restype = None
+        L.stereo_trws_batch_destroy.restype = None
         L.stereo_rd_plan_destroy.restype = None
         L.stereo_fusion_destroy.restype = None
         for name in ("stereo_trws_cache_clear", "stereo_rd_cache_clear"):

@@ -98,6 +98,16 @@ struct GroupArgs {
   int first[kMaxGroup + 1];
 };
 
+// Independent problems in ONE launch (stereo_trws_batch_*): a group whose members have nothing to do
+// with each other.  first[] is where a workgroup STARTS; a workgroup of trws_pipe_batch_kernel that finds its member's
+// tickets used up moves on to the next member.  ctl: the batch's own control words -- [0] workgroups that held runs of
+// more than one member (summed over the launches since the last reset).
+constexpr int kBatchCtlWords = 4;
+struct BatchArgs {
+  GroupArgs g;
+  unsigned long long *ctl;
+};
+
 namespace {
 
 constexpr int kWave = 64;

@@ -47,6 +47,10 @@ int pipe_threads();
 void pipe_set_attributes();
 void launch_pipe(int kernel, bool shared, int what, int blocks, hipStream_t s, const DevParams &p, int epoch);
 void launch_pipe_group(int kernel, bool shared, int what, int blocks, hipStream_t s, const GroupArgs &ga, int epoch);
+// independent problems in one launch, workgroups that move between them (stereo_trws_batch_*); how many of its
+// workgroups a compute unit holds at once
+void launch_pipe_batch(int kernel, bool shared, int what, int blocks, hipStream_t s, const BatchArgs &ba, int epoch);
+int pipe_batch_resident_per_cu(int kernel, bool shared);
 
 size_t pipe2_lds_bytes();
 void pipe2_set_attributes();

@@ -67,9 +67,12 @@ __device__ __forceinline__ void granule_delay(const DevParams &p, int node) {
 // own, launched only when a plan's sweeps use it: everything it adds (the runner's ticket, a segment's first visit,
 // the held-back flags, the rows kept for a second walk, the commit) costs the visit loops registers, and the plain
 // schedule's kernels stay what they were.
-template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED, bool SPEC = false>
+// BATCH: the body as trws_pipe_batch_kernel calls it, once per member of a batch (below): the one thing it adds is a mark
+// in ctl[2] -- the speculative kernel's verdict word, unused here -- once the workgroup holds a run of this member.
+template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED, bool SPEC = false, bool BATCH = false>
 __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
   static_assert(!SPEC || (SHARED && KERNEL == 1), "the speculative schedule exists for shared positions and the linear kernel");
+  static_assert(!(SPEC && BATCH), "batches keep the plain chain schedule");
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double *stage0 = lds;                                   // 2 stages
   double *hand = lds + 2 * kStageDoubles;                 // ring of 4 x 8 x 64: the last visits' new messages
@@ -134,6 +137,7 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
     //  (development switch 131072: flags left as they are)
     TRWS_RUN_ENTER(SPEC, ctl, if (tid < kPipeCompute && !(p.debug & 131072)) xflag[tid] = 0;)
     TRWS_SPEC_SEGMENT
+    if (BATCH && tid == 0) ctl[2] = 1;
     unsigned long long busy = 0;
 #ifdef STEREO_HIP_VISIT_PROFILE
     unsigned long long vacc[6] = {0, 0, 0, 0, 0, 0}, macc[5] = {0, 0, 0, 0, 0}, lacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -632,6 +636,22 @@ __global__ __launch_bounds__(kPipeThreads) void trws_pipe_group_kernel(GroupArgs
   pipe_body<KERNEL, BACKWARD, PRIMAL, UPDATE, SHARED>(ga.pp[group_strip(ga)], epoch);
 }
 
+// Independent problems in one launch (stereo_trws_batch_*): the member frame of trws_visit.h around the
+// body.  A workgroup starts at the member its block index names (the host's shares, as for strips), walks that member's
+// runs until its tickets are used up, and moves on to the next member, round the table once.  Everything the body keeps
+// per problem -- the parameter block in scalar registers, positions and permutation per lane, the LDS tables -- is set
+// up again by the body itself at every call: a member is entered exactly as a launch of its own enters it.  A member
+// whose sweep gave up (ctl[1]) ends the workgroup: the host reports that member, and nothing is started behind a fault.
+template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED>
+__global__ __launch_bounds__(kPipeThreads) void trws_pipe_batch_kernel(BatchArgs ba, int epoch) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  int *ctl = (int *)(lds + kPipeCtlOff);
+  int *state = (int *)(lds + kPipeLdsDoubles);   // (behind the body's LDS: pipe_batch_lds_bytes)
+  TRWS_MEMBERS_BEGIN(ba, group_strip(ba.g), state)
+    pipe_body<KERNEL, BACKWARD, PRIMAL, UPDATE, SHARED, false, true>(ba.g.pp[member], epoch);
+  TRWS_MEMBERS_END(ba, ctl, state)
+}
+
 #undef PIPE_REQUEST_OWN
 #undef PIPE_LOAD8
 #undef VSTAMP
@@ -646,16 +666,20 @@ size_t pipe_lds_bytes() {
                                    kPipeCompute * kPipeXchg + kPipeCompute / 2, "LDS layout of pipe_body");
   return sizeof(double) * kPipeLdsDoubles;
 }
+static size_t pipe_batch_lds_bytes() { return sizeof(double) * (kPipeLdsDoubles + 2); }   // ... with the member frame's state behind
 size_t pipe_spec_lds_bytes() { return sizeof(double) * (kRunBase + kRunDoubles + kRunDummy); }   // ... with the runner's ring behind
 int pipe_threads() { return kPipeThreads; }
 
-// rows: [smoothness kernel 1 | 2][per-edge | shared positions][plain | group], then the speculative schedule's kernel
+// rows: [smoothness kernel 1 | 2][per-edge | shared positions][plain | group], then the speculative schedule's kernel;
+// the batch kernels in a table of their own: [smoothness kernel 1 | 2][per-edge | shared positions]
 #define PIPE_ENTRY(BW, PR, UP, NAME, KER, SH) (const void *)NAME<KER, BW, PR, UP, SH>,
 #define PIPE_SPEC_ENTRY(BW, PR, UP, ...) (const void *)trws_pipe_spec_kernel<BW, PR, UP>,
 #define PIPE_ROWS(KER, SH) {TRWS_SWEEP_VARIANTS(PIPE_ENTRY, trws_pipe_kernel, KER, SH)}, {TRWS_SWEEP_VARIANTS(PIPE_ENTRY, trws_pipe_group_kernel, KER, SH)}
 constexpr int kPipeSpecRow = 8;
 static const SweepRow kPipeKernels[kPipeSpecRow + 1] = {PIPE_ROWS(1, false), PIPE_ROWS(1, true), PIPE_ROWS(2, false), PIPE_ROWS(2, true),
                                                         {TRWS_SWEEP_VARIANTS(PIPE_SPEC_ENTRY)}};
+static const SweepRow kPipeBatchKernels[4] = {{TRWS_SWEEP_VARIANTS(PIPE_ENTRY, trws_pipe_batch_kernel, 1, false)}, {TRWS_SWEEP_VARIANTS(PIPE_ENTRY, trws_pipe_batch_kernel, 1, true)},
+                                              {TRWS_SWEEP_VARIANTS(PIPE_ENTRY, trws_pipe_batch_kernel, 2, false)}, {TRWS_SWEEP_VARIANTS(PIPE_ENTRY, trws_pipe_batch_kernel, 2, true)}};
 #undef PIPE_ROWS
 #undef PIPE_SPEC_ENTRY
 #undef PIPE_ENTRY
@@ -664,6 +688,7 @@ static int pipe_row(int kernel, bool shared, bool group) { return ((kernel == 1 
 void pipe_set_attributes() {
   set_max_dynamic_lds(kPipeKernels, kPipeSpecRow, (int)pipe_lds_bytes());
   set_max_dynamic_lds(kPipeKernels + kPipeSpecRow, 1, (int)pipe_spec_lds_bytes());
+  set_max_dynamic_lds(kPipeBatchKernels, 4, (int)pipe_batch_lds_bytes());
 }
 
 void launch_pipe(int kernel, bool shared, int what, int blocks, hipStream_t s, const DevParams &p, int epoch) {
@@ -675,6 +700,17 @@ void launch_pipe(int kernel, bool shared, int what, int blocks, hipStream_t s, c
 void launch_pipe_group(int kernel, bool shared, int what, int blocks, hipStream_t s, const GroupArgs &ga, int epoch) {
   // (strips keep the plain chain schedule)
   launch_sweep(kPipeKernels[pipe_row(kernel, shared, true)], what, blocks, kPipeThreads, pipe_lds_bytes(), s, ga, epoch);
+}
+void launch_pipe_batch(int kernel, bool shared, int what, int blocks, hipStream_t s, const BatchArgs &ba, int epoch) {
+  launch_sweep(kPipeBatchKernels[pipe_row(kernel, shared, false) / 2], what, blocks, kPipeThreads, pipe_batch_lds_bytes(), s, ba, epoch);
+}
+int pipe_batch_resident_per_cu(int kernel, bool shared) {
+  // (the backward sweep's kernel: the variants of a row differ by a few registers at most, and a share that is
+  //  not resident at once only starts later -- tickets are drawn by workgroups that run)
+  int per_cu = 0;
+  STEREO_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kPipeBatchKernels[pipe_row(kernel, shared, false) / 2][1], kPipeThreads,
+                                                                 pipe_batch_lds_bytes()));
+  return per_cu > 0 ? per_cu : 1;
 }
 
 }  // namespace stereo

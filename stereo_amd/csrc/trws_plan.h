@@ -11,6 +11,7 @@
 
 #include "../../include/stereo_hip.h"
 #include "common.h"
+#include "trws_batch.h"
 #include "trws_family.h"
 #include "trws_graph.h"
 #include "trws_dev.h"
@@ -138,6 +139,20 @@ struct stereo_trws_plan {
     if (ev_lb) (void)hipEventDestroy(ev_lb);
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
   }
+};
+
+// Independent plans that share the launches of a sweep (stereo_trws_batch_*).  The members stay the
+// caller's; the batch owns the table of their parameter blocks and its control words.
+struct stereo_trws_batch {
+  std::vector<stereo_trws_plan *> members;
+  std::vector<char> stopped;      // per member: met max_relgap in a batch iteration; stays out until stereo_trws_batch_reset
+  int device = 0;
+  int capacity = 0;               // workgroups of one launch that are resident together
+  // one region of kMaxGroup blocks per launch of an iteration (forward, backward, fused): the members of a launch, compacted
+  stereo::DevBuf<stereo::DevParams> d_table;
+  stereo::PinnedBuf<stereo::DevParams> h_table;
+  stereo::DevBuf<unsigned long long> d_ctl;   // kBatchCtlWords (BatchArgs::ctl)
+  int64_t launches = 0;           // sweep launches issued (a batch split for capacity counts each part)
 };
 
 namespace stereo {

@@ -152,39 +152,84 @@ void launch_persistent(stereo_trws_plan *P, const DevParams &p, int what, hipStr
   if (what != 3) P->sweep_launches += 1;
 }
 
-// One fused launch for the strips of a group (what: as in launch_persistent).
-void launch_group(stereo_trws_plan *const *G, int n, int what, hipStream_t s) {
+// One fused launch for the plans G[0 .. n) whose parameter blocks lie at `table` in that order: the strips of a group,
+// or -- B given -- members of a batch (what: as in launch_persistent).  Strips and the one-per-CU families divide the
+// grid statically; a batch on the K <= 64 kernel gets workgroups that move between its members, and a batch whose
+// static shares do not fit the device together is split into consecutive launches (trws_batch_partition).
+void launch_table(stereo_trws_plan *const *G, int n, const DevParams *table, int what, hipStream_t s, int epoch, stereo_trws_batch *B) {
   stereo_trws_plan *P0 = G[0];
-  GroupArgs ga{};
-  ga.pp = P0->d_group.p; ga.n = n;
-  int total = 0;
-  const int epoch = P0->epoch + 1;
   const bool one_per_cu = P0->family == TrwsFamily::Wide || P0->family == TrwsFamily::Pipe2;
+  int blocks[kMaxGroup];
   for (int i = 0; i < n; ++i) {
     stereo_trws_plan *P = G[i];
-    ++P->epoch;
     STEREO_HIP_CHECK(hipMemsetAsync(P->d_ctl.p, 0, sizeof(int32_t), s));  // ticket = 0
-    ga.first[i] = total;
-    total += one_per_cu ? std::min(P->grid_blocks, P->cus) : P->grid_blocks;
+    blocks[i] = one_per_cu ? std::min(P->grid_blocks, P->cus) : P->grid_blocks;
     if (what != 3) P->sweep_launches += 1;
   }
-  ga.first[n] = total;
-  switch (P0->family) {   // (stereo_trws_plans_issue lets the pipelined families through only)
-    case TrwsFamily::Wide: launch_wide_group(P0->kernel, what, total, s, ga, epoch); break;
-    case TrwsFamily::Pipe2: launch_pipe2_group(P0->kernel, P0->pos != nullptr, what, total, s, ga, epoch); break;
-    default: launch_pipe_group(P0->kernel, P0->pos != nullptr, what, total, s, ga, epoch);
+  const bool floating = B && !one_per_cu;
+  for (int at = 0; at < n;) {
+    BatchArgs ba{};
+    GroupArgs &ga = ba.g;
+    ga.pp = table + at;
+    if (B) {
+      ga.n = trws_batch_partition(blocks + at, n - at, B->capacity, floating, ga.first);
+    } else {   // strips wait for each other: all of them in this launch, shares one behind the other
+      ga.n = n;
+      for (int i = 0; i < n; ++i) ga.first[i + 1] = ga.first[i] + blocks[i];
+    }
+    const int total = ga.first[ga.n];
+    switch (P0->family) {   // (the callers let the pipelined families through only)
+      case TrwsFamily::Wide: launch_wide_group(P0->kernel, what, total, s, ga, epoch); break;
+      case TrwsFamily::Pipe2: launch_pipe2_group(P0->kernel, P0->pos != nullptr, what, total, s, ga, epoch); break;
+      default:
+        if (B) { ba.ctl = B->d_ctl.p; launch_pipe_batch(P0->kernel, P0->pos != nullptr, what, total, s, ba, epoch); }
+        else launch_pipe_group(P0->kernel, P0->pos != nullptr, what, total, s, ga, epoch);
+    }
+    if (B) B->launches += 1;
+    at += ga.n;
   }
   STEREO_HIP_CHECK(hipGetLastError());
 }
 
-// One iteration's launches and device-to-host copies for the plans of one launch (one plan, or the strips of a
-// group), without waiting for any of them.  launch(what) is the one thing that differs: the plan's own launch
-// (stereo_trws_plan_iterate; beliefs: with phase 1 of the node beliefs) or the group launch (the issue entries).
+// ... for the strips of a group: one state, one epoch
+void launch_group(stereo_trws_plan *const *G, int n, int what, hipStream_t s) {
+  const int epoch = G[0]->epoch + 1;
+  for (int i = 0; i < n; ++i) ++G[i]->epoch;
+  launch_table(G, n, G[0]->d_group.p, what, s, epoch, nullptr);
+}
+
+// ... for the members of a batch that take part in launch `what`: all of G, but in the forward sweep of a first
+// iteration (what 0) only those whose forward sweep has not run yet.  Members come with epochs of their own (one may
+// have iterated alone); an epoch only has to exceed every epoch its plan has seen -- flags are compared with <, granule
+// tags with == against values that are all older -- so the launch takes one above the highest and every member adopts it.
+void launch_batch(stereo_trws_batch *B, stereo_trws_plan *const *G, const DevParams *params, int n, int what, hipStream_t s) {
+  stereo_trws_plan *in[kMaxGroup];
+  DevParams *h = B->h_table.p + (size_t)what * kMaxGroup, *d = B->d_table.p + (size_t)what * kMaxGroup;
+  int m = 0, epoch = 0;
+  for (int i = 0; i < n; ++i) {
+    if (what == 0 && G[i]->fwd_pending) continue;
+    epoch = std::max(epoch, G[i]->epoch + 1);
+    h[m] = params[i];
+    in[m++] = G[i];
+  }
+  for (int i = 0; i < m; ++i) in[i]->epoch = epoch;
+  STEREO_HIP_CHECK(hipMemcpyAsync(d, h, sizeof(DevParams) * m, hipMemcpyHostToDevice, s));
+  launch_table(in, m, d, what, s, epoch, B);
+}
+
+// One iteration's launches and device-to-host copies for the plans of one launch (one plan, the strips of a
+// group, or the members of a batch), without waiting for any of them.  launch(what) is the one thing that differs: the
+// plan's own launch (stereo_trws_plan_iterate), the group launch (the issue entries) or the batch launch
+// (stereo_trws_batch_iterate); beliefs: with phase 1 of the node beliefs, for every plan that keeps them.
+// Strips are in one state; the members of a batch need not be: launch(0) is for the plans whose forward sweep has
+// not run yet, and the batch launch leaves the others out of it.
 template <class Launch>
 void issue_iteration(stereo_trws_plan *const *plans, int n, hipStream_t s, bool beliefs, Launch launch) {
   stereo_trws_plan *P0 = plans[0];
   if (P0->time_sweeps) STEREO_HIP_CHECK(hipEventRecord(P0->ev0, s));
-  if (!P0->fwd_pending) launch(0);
+  bool fwd_due = false;
+  for (int i = 0; i < n; ++i) fwd_due = fwd_due || !plans[i]->fwd_pending;
+  if (fwd_due) launch(0);
   launch(1);
   // the backward sweep's lower-bound terms travel while the next launch runs
   STEREO_HIP_CHECK(hipEventRecord(P0->ev_bwd, s));
@@ -196,10 +241,12 @@ void issue_iteration(stereo_trws_plan *const *plans, int n, hipStream_t s, bool 
     P->lb_in_flight = true;
   }
   // node beliefs, phase 1: every firstForward edge holds this iteration's backward message into its tail now
-  if (beliefs && P0->keep_mm)
-    launch_beliefs_accum(P0->unary, P0->d_msg.p, P0->d_order.p, P0->d_fptr.p, P0->d_fidx.p, P0->K, P0->N, P0->d_belief.p, s);
+  for (int i = 0; beliefs && i < n; ++i) {
+    stereo_trws_plan *P = plans[i];
+    if (P->keep_mm) launch_beliefs_accum(P->unary, P->d_msg.p, P->d_order.p, P->d_fptr.p, P->d_fidx.p, P->K, P->N, P->d_belief.p, s);
+  }
   launch(2);  // forward sweep of the NEXT iteration fused with this iteration's primal
-  if (beliefs) P0->mm_ready = P0->keep_mm;
+  for (int i = 0; beliefs && i < n; ++i) plans[i]->mm_ready = plans[i]->keep_mm;
   if (P0->time_sweeps) STEREO_HIP_CHECK(hipEventRecord(P0->ev1, s));
   for (int i = 0; i < n; ++i) {
     stereo_trws_plan *P = plans[i];
@@ -471,6 +518,18 @@ static int strip_ready(stereo_trws_plan *P, const char *who, char *err, size_t e
   return 0;
 }
 
+// The parameters of a plan's OWN launches (speculative schedule included), with the block once more in global memory:
+// chain_runner / spec_commit read their parameters there; sent when it changes.
+static DevParams own_params(stereo_trws_plan *P) {
+  const DevParams p = make_params(P);
+  if (!P->self_sent || std::memcmp(P->h_self.p, &p, sizeof(DevParams)) != 0) {
+    std::memcpy(P->h_self.p, &p, sizeof(DevParams));
+    STEREO_HIP_CHECK(hipMemcpy(P->d_self.p, P->h_self.p, sizeof(DevParams), hipMemcpyHostToDevice));
+    P->self_sent = true;
+  }
+  return p;
+}
+
 int stereo_trws_plan_iterate(stereo_trws_plan *P, int iters, double max_relgap, void *stream,
                              int *done_iters, int *stopped, char *err, size_t errcap) {
   DeviceScope device_scope_(P ? P->device : -1);
@@ -483,13 +542,7 @@ int stereo_trws_plan_iterate(stereo_trws_plan *P, int iters, double max_relgap, 
   if (stopped) *stopped = 0;
   hipStream_t s = (hipStream_t)stream;
   try {
-    const DevParams p = make_params(P);
-    // (the block once more in global memory: chain_runner / spec_commit read their parameters there; sent when it changes)
-    if (!P->self_sent || std::memcmp(P->h_self.p, &p, sizeof(DevParams)) != 0) {
-      std::memcpy(P->h_self.p, &p, sizeof(DevParams));
-      STEREO_HIP_CHECK(hipMemcpy(P->d_self.p, P->h_self.p, sizeof(DevParams), hipMemcpyHostToDevice));
-      P->self_sent = true;
-    }
+    const DevParams p = own_params(P);
     for (int it = 0; it < iters; ++it) {
       issue_iteration(&P, 1, s, true, [&](int what) { launch_persistent(P, p, what, s); });
       double lb = 0, en = 0;
@@ -560,6 +613,132 @@ int stereo_trws_plan_commit(stereo_trws_plan *P, double lower_bound, double ener
   DeviceScope device_scope_(P ? P->device : -1);
   if (!P) return fail("stereo_trws_plan_commit: NULL plan", err, errcap);
   P->lb = lower_bound; P->energy = energy; P->iterations += 1;
+  return 0;
+}
+
+// ---- batches: independent plans that share the launches of a sweep ----------------------------------
+
+// the admission rule (trws_batch.h) on the members as they are NOW: at creation, and again before every iteration --
+// an upload may have moved a member to another kernel family since
+static int batch_admit(const char *who, stereo_trws_plan *const *plans, int n, char *err, size_t errcap) {
+  TrwsBatchMember facts[kBatchMaxMembers];
+  for (int i = 0; plans && i < n && i < kBatchMaxMembers; ++i) {
+    const stereo_trws_plan *P = plans[i];
+    TrwsBatchMember &f = facts[i];
+    f.present = P != nullptr;
+    if (!P) continue;
+    for (int j = 0; j < i; ++j) f.repeated = f.repeated || plans[j] == P;
+    f.nstrips = P->nstrips; f.have_inputs = P->have_inputs; f.family = P->family; f.kernel = P->kernel;
+    f.exact = P->mode == STEREO_TRWS_MESSAGES_EXACT; f.shared = P->pos != nullptr; f.device = P->device;
+  }
+  std::string why;
+  if (trws_batch_admit(plans ? facts : nullptr, n, &why) >= 0) return fail(std::string(who) + ": " + why, err, errcap);
+  return 0;
+}
+
+int stereo_trws_batch_create(stereo_trws_plan *const *plans, int n, stereo_trws_batch **out, char *err, size_t errcap) {
+  if (!out) return fail("stereo_trws_batch_create: NULL argument", err, errcap);
+  *out = nullptr;
+  if (int rc = batch_admit("stereo_trws_batch_create", plans, n, err, errcap)) return rc;
+  DeviceScope device_scope_(plans[0]->device);
+  try {
+    std::unique_ptr<stereo_trws_batch> B(new stereo_trws_batch);
+    B->members.assign(plans, plans + n);
+    B->stopped.assign(n, 0);
+    B->device = plans[0]->device;
+    // what stays resident together: the K <= 64 kernel as often per compute unit as the device says, the others once
+    const stereo_trws_plan *P0 = plans[0];
+    B->capacity = P0->cus * (P0->family == TrwsFamily::Pipe ? pipe_batch_resident_per_cu(P0->kernel, P0->pos != nullptr) : 1);
+    // (development, as for a single plan's launch: fewer workgroups -- members then share them, and the K <= 64 kernel's float)
+    if (const char *be = std::getenv("STEREO_HIP_TRWS_BLOCKS"))
+      if (std::atoi(be) > 0) B->capacity = std::min(B->capacity, std::atoi(be));
+    B->d_table.alloc(3 * kMaxGroup); B->h_table.alloc(3 * kMaxGroup);
+    B->d_ctl.alloc(kBatchCtlWords);
+    STEREO_HIP_CHECK(hipMemset(B->d_ctl.p, 0, sizeof(unsigned long long) * kBatchCtlWords));
+    *out = B.release();
+    return 0;
+  } catch (const HipError &e) {
+    return fail(e.msg, err, errcap);
+  }
+}
+
+void stereo_trws_batch_destroy(stereo_trws_batch *B) {
+  DeviceScope device_scope_(B ? B->device : -1);
+  delete B;
+}
+
+int stereo_trws_batch_iterate(stereo_trws_batch *B, int iters, double max_relgap, int32_t *done_iters, char *err, size_t errcap) {
+  if (!B) return fail("stereo_trws_batch_iterate: NULL batch", err, errcap);
+  DeviceScope device_scope_(B->device);
+  const int n = (int)B->members.size();
+  for (int i = 0; done_iters && i < n; ++i) done_iters[i] = 0;
+  if (int rc = batch_admit("stereo_trws_batch_iterate", B->members.data(), n, err, errcap)) return rc;
+  for (int i = 0; i < n; ++i)
+    if (B->members[i]->issued)
+      return fail("stereo_trws_batch_iterate: member " + std::to_string(i) + " has an issued iteration that has not been collected", err, errcap);
+  hipStream_t s = nullptr;
+  try {
+    // (batches keep the plain chain schedule, like the strip groups)
+    DevParams all[kMaxGroup], own[kMaxGroup];
+    for (int i = 0; i < n; ++i) { all[i] = make_params(B->members[i], false); own[i] = own_params(B->members[i]); }
+    for (int it = 0; it < iters; ++it) {
+      stereo_trws_plan *G[kMaxGroup];
+      DevParams params[kMaxGroup];
+      int index[kMaxGroup], m = 0;
+      for (int i = 0; i < n; ++i)
+        if (!B->stopped[i]) { G[m] = B->members[i]; params[m] = all[i]; index[m++] = i; }
+      if (m == 0) break;
+      // Where the shared launch is known to lose (measured), the members take their own launches one after
+      // the other -- the single plan's path, speculative schedule included; same bits either way: a batch of one, and
+      // fewer than kBatchLargeMin members of the K <= 64 family that each fill the device alone (more runs than
+      // resident workgroups: nothing idles for the others to use).
+      bool own_launches = m == 1;
+      if (!own_launches && G[0]->family == TrwsFamily::Pipe && m < kBatchLargeMin) {
+        own_launches = true;
+        for (int j = 0; j < m; ++j) own_launches = own_launches && G[j]->grid_blocks >= B->capacity;
+      }
+      if (!own_launches) issue_iteration(G, m, s, true, [&](int what) { launch_batch(B, G, params, m, what, s); });
+      // every member commits its own sums, taken in the single plan's order; all are collected before any is reported
+      int gave_up = -1;
+      for (int j = 0; j < m; ++j) {
+        stereo_trws_plan *P = G[j];
+        if (own_launches) issue_iteration(&P, 1, s, true, [&](int what) { launch_persistent(P, own[index[j]], what, s); });
+        double lb = 0, en = 0;
+        if (!collect_iteration(P, s, &lb, &en)) { P->mm_ready = false; if (gave_up < 0) gave_up = j; continue; }
+        P->lb = lb; P->energy = en; P->iterations += 1;
+        if (done_iters) done_iters[index[j]] += 1;
+        const double rel_gap = (en - lb) / en;  // minimize.cpp:105
+        if (rel_gap < max_relgap) B->stopped[index[j]] = 1;
+      }
+      if (gave_up >= 0)
+        return fail("stereo_trws_batch_iterate: member " + std::to_string(index[gave_up]) + ": " + gave_up_text(G[gave_up]), err, errcap);
+    }
+    return 0;
+  } catch (const HipError &e) {
+    return fail(e.msg, err, errcap);
+  }
+}
+
+int stereo_trws_batch_reset(stereo_trws_batch *B, char *err, size_t errcap) {
+  if (!B) return fail("stereo_trws_batch_reset: NULL batch", err, errcap);
+  DeviceScope device_scope_(B->device);
+  try {
+    for (stereo_trws_plan *P : B->members) reset_state(P);
+    std::fill(B->stopped.begin(), B->stopped.end(), 0);
+    STEREO_HIP_CHECK(hipMemset(B->d_ctl.p, 0, sizeof(unsigned long long) * kBatchCtlWords));
+    B->launches = 0;
+    return 0;
+  } catch (const HipError &e) {
+    return fail(e.msg, err, errcap);
+  }
+}
+
+int stereo_trws_batch_stats(stereo_trws_batch *B, int64_t out[4]) {
+  if (!B || !out) return 1;
+  DeviceScope device_scope_(B->device);
+  unsigned long long v[kBatchCtlWords] = {0};
+  if (hipMemcpy(v, B->d_ctl.p, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return 1;
+  out[0] = (int64_t)v[0]; out[1] = B->launches; out[2] = 0; out[3] = B->capacity;
   return 0;
 }
 

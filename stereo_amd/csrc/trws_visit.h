@@ -42,6 +42,35 @@
     const bool spec_in = SPEC && seg > 0 && !second_walk; \
     (void)spec_in;
 
+// ---- the member frame: one level above the run frame (trws_pipe_batch_kernel; stereo_trws_batch_*) ------
+// A launch that serves several INDEPENDENT problems from one table of parameter blocks.  The ticket draw gets one more
+// level: a workgroup draws the tickets of the member HOME names until none is left (the run frame's own exit), then those
+// of the next member of the table, once round.  It enters a member only through that member's ticket counter, so inside
+// every member tickets are still handed out in schedule order to workgroups that run -- what every wait relies on.
+// Between BEGIN and END stands the call of the kernel body with the member's parameter block, `member` its index:
+// the body reads the block from the table and sets up everything it keeps per problem anew.  CTL: the body's control
+// words; [1] != 0: a wait gave up -- the workgroup ends, wave by wave, as it does in a launch of one problem (no barrier
+// behind a body that some waves have left early); [2]: the body held a run of this member.  BA.ctl[0] counts the
+// workgroups that held runs of more than one member.  STATE: three ints of LDS behind the body's own -- what the frame
+// keeps across a body lives there, not in registers the visit loops would have to spill.
+#define TRWS_MEMBERS_BEGIN(BA, HOME, STATE) \
+    if (threadIdx.x == 0) { (STATE)[0] = (HOME); (STATE)[1] = 0; (STATE)[2] = 0; }   /* member, members visited, members served */ \
+    __syncthreads(); \
+    for (;;) { \
+      const int member = __builtin_amdgcn_readfirstlane((STATE)[0]);
+#define TRWS_MEMBERS_END(BA, CTL, STATE) \
+      if (__hip_atomic_load((CTL) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return; \
+      __syncthreads(); \
+      if (threadIdx.x == 0) { \
+        (STATE)[2] += (CTL)[2]; \
+        (STATE)[1] += 1; \
+        (STATE)[0] = (STATE)[0] + 1 < (BA).g.n ? (STATE)[0] + 1 : 0; \
+      } \
+      __syncthreads(); \
+      if (__builtin_amdgcn_readfirstlane((STATE)[1]) >= (BA).g.n) break; \
+    } \
+    if (threadIdx.x == 0 && (STATE)[2] > 1) atomicAdd((BA).ctl, 1ull);
+
 // ---- the visit frame -------------------------------------------------------------------------------------------------
 // Every role walks the run in its own loop -- the same visits, the same barrier at the end of each: the hardware barrier
 // counts arrivals, whichever s_barrier instruction a wave arrives at -- so that what one role keeps across visits (the

@@ -232,6 +232,65 @@ class TrwsPlan:
         return ms.value, n.value
 
 
+class TrwsBatch:
+    """Independent TrwsPlan objects that share one launch per sweep (stereo_trws_batch_*).
+
+    The members stay ordinary plans: results come from each plan's ``result()``, and every member computes bit for
+    bit what ``TrwsPlan.iterate`` computes for it alone.  Accepted: whole problems with inputs, on one device, in one
+    pipelined kernel family (``path()`` 2, 3 or 4) with the same smoothness kernel, message mode and kind of positions;
+    everything else raises with the offending member's index in the message."""
+
+    MAX_MEMBERS = 16
+
+    def __init__(self, plans):
+        self.plans = list(plans)
+        self._h = C.c_void_p()
+        n = len(self.plans)
+        arr = (C.c_void_p * max(n, 1))(*[p._h for p in self.plans])
+        err = _lib.errbuf()
+        rc = _lib.lib().stereo_trws_batch_create(arr, C.c_int(n), C.byref(self._h), err, C.c_size_t(len(err)))
+        _lib.check(rc, err)
+
+    def close(self):
+        if self._h:
+            _lib.lib().stereo_trws_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def iterate(self, iters, max_relgap=0.0):
+        """Up to `iters` iterations of every member; max_relgap stops each member on its own (it then stays out until
+        reset()).  Returns the iterations each member ran in this call."""
+        done = (C.c_int32 * len(self.plans))()
+        err = _lib.errbuf()
+        rc = _lib.lib().stereo_trws_batch_iterate(self._h, C.c_int(int(iters)), C.c_double(float(max_relgap)), done, err,
+                                                  C.c_size_t(len(err)))
+        _lib.check(rc, err)
+        return [int(d) for d in done]
+
+    def reset(self):
+        err = _lib.errbuf()
+        _lib.check(_lib.lib().stereo_trws_batch_reset(self._h, err, C.c_size_t(len(err))), err)
+
+    def stats(self):
+        """dict(floated: workgroups that held runs of more than one member, launches, spec: the speculative schedule
+        runs inside the batch (never), capacity: workgroups one launch keeps resident)."""
+        out = (C.c_int64 * 4)()
+        _lib.lib().stereo_trws_batch_stats(self._h, out)
+        return dict(floated=int(out[0]), launches=int(out[1]), spec=bool(out[2]), capacity=int(out[3]))
+
+
 def analyze(N, connectivity0):
     """Host-only graph analysis (stereo_trws_analyze); connectivity zero based."""
     c = np.asarray(connectivity0)
