@@ -29,7 +29,7 @@ extern "C" {
  * behind dispmap_globalstereo), stereo_trws_plan_debug_terms / _messages, stereo_segpln_planes_batch.  7: TRW-S takes
  * up to 4096 labels with one shared strictly ascending positions vector (stereo_trws_plan_path 5).  8: stereo_trws_batch_*
  * (independent plans that share one launch per sweep). */
-#define STEREO_HIP_ABI_VERSION 8
+#define STEREO_HIP_ABI_VERSION 9
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -86,9 +86,12 @@ void stereo_trws_cache_clear(void);
 /* Same solve, plus each node's min-marginals and confidence (definition: stereo_trws_plan_keep_min_marginals).
  * No reference counterpart (trws_mex returns four outputs; mex/trws_minmarginals_mex.cpp is the six-output gateway).
  * min_marginals K x N, confidence N; either may be NULL.  Labels, energy, bound and iterations are stereo_trws's bits.
- * Always ONE plan, also with STEREO_HIP_GPUS >= 2 (strips give the same bits; per-strip beliefs are not supported):
- * cached strips of the same problem are replaced by a single plan.  The flag is a runtime setting of the cached plan:
- * a later plain stereo_trws call on it runs with the flag off and pays nothing.  Extra device memory 8 K N bytes. */
+ * ONE plan by default, also with STEREO_HIP_GPUS >= 2 (strips give the same bits): cached strips of the same problem
+ * are replaced by a single plan.  With STEREO_HIP_TRWS_BELIEFS_STRIPS=1 as well the call is sharded by stereo_trws's
+ * rule (stereo_trws_gateway_strips): every strip keeps the beliefs of its own nodes and the rows are put together at
+ * their node ids -- the same bits again, with messages and beliefs divided among the strips.  The flag is a runtime
+ * setting of the cached plan(s): a later plain stereo_trws call on them runs with the flag off and pays nothing.
+ * Extra device memory 8 K N bytes (over all strips). */
 int stereo_trws_min_marginals(int kernel, const double *unary, const uint32_t *conn, const double *q,
                               const double *qprim, const double *alphas, double tol, double maxiter,
                               double max_relgap, int K, int64_t N, int64_t E, double *labelling,
@@ -213,14 +216,16 @@ int stereo_trws_plan_path(stereo_trws_plan *plan);
  * every iteration runs one extra kernel between the backward sweep and the fused forward sweep
  * (P_i = D_i + firstForward messages; 8 K N bytes of device memory, about 8 K (2 N + E) bytes of traffic),
  * and the read adds the firstBackward messages.  Bit-identical to t iterations of minimize.cpp plus one forward
- * pass on the CPU.  Flag off (the default): no extra launch, no extra memory.  Strip plans refuse it.
- * on = 0 frees the buffer.  Fails cleanly if the buffer cannot be allocated. */
+ * pass on the CPU.  Flag off (the default): no extra launch, no extra memory.  A strip plan refuses this entry and
+ * takes stereo_trws_plan_strip_keep_min_marginals (below).  on = 0 frees the buffer.  Fails cleanly if the buffer
+ * cannot be allocated. */
 int stereo_trws_plan_keep_min_marginals(stereo_trws_plan *plan, int on, char *err, size_t errcap);
 /* Outputs of the last run, node-id order: min_marginals K x N (label fastest) = Di - min Di; confidence N = the
  * second-smallest entry of that vector (+Inf when K = 1); argmin N = the first minimum, 0-based (the primal's tie
  * rule).  Any of the three may be NULL.  Fails if no iteration has run with the flag on since it was set, after a
- * reset, upload or bind (they start a new minimisation), and on strip plans.  Reading twice without iterating
- * gives the same bits.  Host arrays: */
+ * reset, upload or bind (they start a new minimisation), while an issued iteration has not been collected, and on
+ * strip plans (their entry: stereo_trws_plan_strip_min_marginals).  Reading twice without iterating gives the same
+ * bits.  Host arrays: */
 int stereo_trws_plan_min_marginals(stereo_trws_plan *plan, double *min_marginals, double *confidence,
                                    int32_t *argmin, char *err, size_t errcap);
 /* ... or device arrays of the caller (e.g. torch tensors), written on `stream` (hipStream_t, NULL = default)
@@ -310,8 +315,8 @@ int stereo_trws_plan_commit(stereo_trws_plan *plan, double lower_bound, double e
  * members on path 2 that each have more runs than the device keeps workgroups resident -- iterate gives
  * every member its own launches, one after the other, exactly as stereo_trws_plan_iterate does: same bits, same
  * contract, and out[1] of stereo_trws_batch_stats does not count them.
- * Node beliefs: a member with stereo_trws_plan_keep_min_marginals on gets its phase-1 launch in every batch iteration,
- * between the backward and the fused launch as in stereo_trws_plan_iterate, and stereo_trws_plan_min_marginals after a
+ * Node beliefs: the members with stereo_trws_plan_keep_min_marginals on get their phase 1 in every batch iteration -- one
+ * launch for all of them -- between the backward and the fused launch as in stereo_trws_plan_iterate, and stereo_trws_plan_min_marginals after a
  * batch iteration returns what it returns after the same iterations alone.
  * A batch runs on the default (NULL) stream: the members' inputs must be complete there (bound arrays written on
  * another stream need a synchronisation first).  Sweep timing (stereo_trws_plan_stats) is not defined for batch
@@ -355,6 +360,33 @@ int stereo_trws_strip_layout_host(int64_t N, int64_t E, const uint32_t *conn, co
                                   int nstrips, int strip, int direction, int64_t *n_nodes,
                                   int64_t *n_own, int64_t *n_edges, int64_t *n_visits, int32_t *nodes,
                                   int32_t *edges, int32_t *desc, char *err, size_t errcap);
+/* Node beliefs on strips.  A strip keeps the beliefs of its OWN nodes: 8 K n_own bytes, one extra
+ * kernel per iteration between the strip's backward and its fused launch -- every message row the two phases read for
+ * an own node is in the strip's own copy when they read it, so the strips exchange nothing for this.  Strips that
+ * iterate through stereo_trws_plans_issue share one such launch per iteration, as do the members of a batch.
+ * On a plan of the whole problem the call is stereo_trws_plan_keep_min_marginals.  on = 0 frees the buffers.
+ * Turn it on on every strip between iterations (collective where the strips are processes). */
+int stereo_trws_plan_strip_keep_min_marginals(stereo_trws_plan *plan, int on, char *err, size_t errcap);
+/* The strip's own rows after its iteration was collected, host arrays: min_marginals K x n_own, confidence n_own,
+ * argmin n_own (0-based), own nodes in the order of stereo_trws_plan_strip_layout (row j belongs to node nodes[j]).
+ * Any output may be NULL.  Fails like stereo_trws_plan_min_marginals: flag off, no iteration since it was set or since
+ * a reset / upload / bind, an issued iteration not yet collected. */
+int stereo_trws_plan_strip_min_marginals(stereo_trws_plan *plan, double *min_marginals, double *confidence,
+                                         int32_t *argmin, char *err, size_t errcap);
+/* n <= 16 strips of one problem that share ONE device, read in one launch into device arrays of the WHOLE problem
+ * (d_min_marginals K x N, d_confidence N, d_argmin N, any may be NULL) on `stream`, without waiting for it: every own
+ * node's row is written at its global id; nodes of strips that are not named keep what the arrays held. */
+int stereo_trws_plans_min_marginals_device(stereo_trws_plan *const *plans, int n, double *d_min_marginals,
+                                           double *d_confidence, int32_t *d_argmin, void *stream, char *err,
+                                           size_t errcap);
+/* Host only (no device): the lists the belief kernels walk on strip `strip` -- own (n_own entries): its own nodes in
+ * rank order as strip-local ids; fptr / bptr (n_own + 1) and fidx / bidx (n_fwd / n_bwd): per such node the
+ * firstForward / firstBackward edges as strip-local ids, in the list order of stereo_trws_analyze.  Sizes first
+ * (arrays NULL), then the arrays.  nstrips == 1: the whole problem (owner may be NULL). */
+int stereo_trws_strip_belief_lists_host(int64_t N, int64_t E, const uint32_t *conn, const int32_t *owner,
+                                        int nstrips, int strip, int64_t *n_own, int64_t *n_fwd, int64_t *n_bwd,
+                                        int32_t *own, int32_t *fptr, int32_t *fidx, int32_t *bptr, int32_t *bidx,
+                                        char *err, size_t errcap);
 /* Diagnostics (any output may be NULL). */
 int stereo_trws_plan_strip_info(stereo_trws_plan *plan, int *nstrips, int *strip, int64_t *own_nodes,
                                 int64_t *runs_forward, int64_t *runs_backward, int *needs_previous,
@@ -379,8 +411,9 @@ int stereo_trws_family_rule(int kernel, int K, int message_mode, int fast_ok, in
  * dispmap_super.m:279-302 (nodes col * H + row, 4-neighbourhood, H >= 2 G; K <= 128, or <= 256 with one positions vector
  * in every column of q and qprim): strip g on device g when the process sees G devices (peer access over xGMI), all
  * strips on the current device otherwise (logical strips, one fused launch per sweep).  Same labels, energy, bound and
- * iteration count as on one device.  This call tells how many strips the calling thread's last stereo_trws ran on
- * (1: the single-device plan).  No reference counterpart. */
+ * iteration count as on one device.  stereo_trws_min_marginals follows the same rule only with
+ * STEREO_HIP_TRWS_BELIEFS_STRIPS=1 set as well.  This call tells how many strips the calling thread's last stereo_trws /
+ * stereo_trws_min_marginals ran on (1: the single-device plan).  No reference counterpart. */
 int stereo_trws_gateway_strips(void);
 
 /* Host only (no device): the speculative schedule of the graph's one long serial run, if it has one (DESIGN.md 4.5;

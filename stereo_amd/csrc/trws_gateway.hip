@@ -151,11 +151,49 @@ int strips_create(int kernel, int K, int64_t N, int64_t E, const uint32_t *conn,
   return rc;
 }
 
+// The strips' belief rows put together at their node ids.  Logical strips: one grouped launch into arrays of the whole
+// problem on the device; strips on devices of their own: each strip's own rows, scattered on the host.
+int strips_min_marginals(TrwsStripSet &S, double *min_marginals, double *confidence, char *err, size_t errcap) {
+  const int G = (int)S.plans.size();
+  const stereo_trws_plan *P0 = S.plans[0];
+  const size_t K = (size_t)P0->K;
+  try {
+    if (S.one_device) {
+      DevBuf<double> d_mm, d_conf;
+      if (min_marginals) d_mm.alloc((size_t)P0->N * K);
+      if (confidence) d_conf.alloc((size_t)P0->N);
+      if (int rc = stereo_trws_plans_min_marginals_device(S.plans.data(), G, d_mm.p, d_conf.p, nullptr, nullptr, err, errcap)) return rc;
+      if (min_marginals) STEREO_HIP_CHECK(hipMemcpy(min_marginals, d_mm.p, sizeof(double) * (size_t)P0->N * K, hipMemcpyDeviceToHost));
+      if (confidence) STEREO_HIP_CHECK(hipMemcpy(confidence, d_conf.p, sizeof(double) * (size_t)P0->N, hipMemcpyDeviceToHost));
+      return 0;
+    }
+  } catch (const HipError &e) {
+    return fail(e.msg, err, errcap);
+  }
+  std::vector<double> mm, conf;
+  for (int g = 0; g < G; ++g) {
+    const StripLayout &L = *S.plans[g]->layout;
+    if (min_marginals) mm.resize((size_t)L.n_own * K);
+    if (confidence) conf.resize((size_t)L.n_own);
+    if (int rc = stereo_trws_plan_strip_min_marginals(S.plans[g], min_marginals ? mm.data() : nullptr, confidence ? conf.data() : nullptr,
+                                                      nullptr, err, errcap)) return rc;
+    for (int64_t j = 0; j < L.n_own; ++j) {
+      if (min_marginals) std::memcpy(min_marginals + (size_t)L.nodes[j] * K, &mm[(size_t)j * K], sizeof(double) * K);
+      if (confidence) confidence[L.nodes[j]] = conf[j];
+    }
+  }
+  return 0;
+}
+
+// beliefs: as trws_solve_on -- every strip runs with its belief flag on and the rows are read afterwards
 int strips_solve(TrwsStripSet &S, const double *unary, const double *q, const double *qprim, const double *alphas, double tol,
                  double maxiter, double max_relgap, double *labelling, double *energy, double *lower_bound, double *iterations, char *err,
-                 size_t errcap) {
+                 size_t errcap, bool beliefs = false, double *min_marginals = nullptr, double *confidence = nullptr) {
   const int G = (int)S.plans.size();
   stereo_trws_plan *P0 = S.plans[0];
+  for (int g = 0; g < G; ++g)
+    if (beliefs || S.plans[g]->keep_mm)
+      if (int rc = stereo_trws_plan_strip_keep_min_marginals(S.plans[g], beliefs ? 1 : 0, err, errcap)) return rc;
   const bool shared = columns_are_one_vector(q, qprim, P0->K, P0->E);
   for (int g = 0; g < G; ++g) {
     const int rc = shared ? stereo_trws_plan_upload(S.plans[g], unary, nullptr, nullptr, q, alphas, tol, err, errcap)
@@ -195,7 +233,8 @@ int strips_solve(TrwsStripSet &S, const double *unary, const double *q, const do
       if (S.owner[i] == g) labelling[i] = part[i];
   }
   *energy = en; *lower_bound = lb; *iterations = (double)done;
-  return 0;
+  if (!beliefs || (!min_marginals && !confidence)) return 0;
+  return strips_min_marginals(S, min_marginals, confidence, err, errcap);
 }
 
 // how many strips the gateway should cut the problem into (1: the plain single-device plan)
@@ -255,8 +294,8 @@ int gateway_create(const TrwsCacheKey &k, int64_t gridH, stereo_trws_plan **P, T
 
 thread_local int g_last_gateway_strips = 0;   // what the last stereo_trws call of this thread ran on (stereo_trws_gateway_strips)
 
-// The gateway behind stereo_trws and stereo_trws_min_marginals.  beliefs: always ONE plan (per-strip beliefs are not
-// supported; strips give the same bits): the call asks for G = 1, and G is part of the cache key.
+// The gateway behind stereo_trws and stereo_trws_min_marginals.  beliefs: ONE plan (strips give the same bits) unless
+// STEREO_HIP_TRWS_BELIEFS_STRIPS=1 asks for the strips of stereo_trws's rule; G is part of the cache key.
 int trws_gateway(int kernel, const double *unary, const uint32_t *conn, const double *q, const double *qprim, const double *alphas,
                  double tol, double maxiter, double max_relgap, int K, int64_t N, int64_t E, double *labelling, double *energy,
                  double *lower_bound, double *iterations, bool beliefs, double *min_marginals, double *confidence, char *err,
@@ -272,10 +311,13 @@ int trws_gateway(int kernel, const double *unary, const uint32_t *conn, const do
   const char *ce = std::getenv("STEREO_HIP_TRWS_CACHE");
   const bool cached = (!ce || std::atoi(ce) != 0) && E > 0 && N > 0;
   int64_t gridH = 0;
-  key.G = (E > 0 && N > 0 && !beliefs) ? gateway_strips(kernel, K, N, E, conn, q, qprim, key.mode, &gridH) : 1;
+  bool shard = !beliefs;
+  if (const char *bs = trws_switch(kSwBeliefsStrips)) shard = shard || std::atoi(bs) == 1;
+  key.G = (E > 0 && N > 0 && shard) ? gateway_strips(kernel, K, N, E, conn, q, qprim, key.mode, &gridH) : 1;
   g_last_gateway_strips = key.G;
   auto solve = [&](stereo_trws_plan *P, TrwsStripSet *S, bool look_for_shared) {
-    if (S) return strips_solve(*S, unary, q, qprim, alphas, tol, maxiter, max_relgap, labelling, energy, lower_bound, iterations, err, errcap);
+    if (S) return strips_solve(*S, unary, q, qprim, alphas, tol, maxiter, max_relgap, labelling, energy, lower_bound, iterations, err, errcap,
+                               beliefs, min_marginals, confidence);
     return trws_solve_on(P, unary, q, qprim, alphas, tol, maxiter, max_relgap, look_for_shared, labelling, energy, lower_bound,
                          iterations, err, errcap, beliefs, min_marginals, confidence);
   };

@@ -833,6 +833,41 @@ bool build_strip_layout(const TrwsGraph &g, int strip, StripLayout &out, std::st
   return sound;
 }
 
+bool build_strip_belief_lists(const TrwsGraph &g, int strip, const std::vector<int32_t> &nodes, const std::vector<int32_t> &edges,
+                              StripBeliefLists &out, std::string &err) {
+  out = StripBeliefLists();
+  const bool whole = g.nstrips <= 1 || g.owner.empty();
+  std::vector<int32_t> node_l, edge_l;
+  if (!whole) {
+    node_l.assign((size_t)g.N, -1); edge_l.assign((size_t)g.E, -1);
+    for (size_t i = 0; i < nodes.size(); ++i) node_l[nodes[i]] = (int32_t)i;
+    for (size_t e = 0; e < edges.size(); ++e) edge_l[edges[e]] = (int32_t)e;
+  }
+  out.fptr.assign(1, 0); out.bptr.assign(1, 0);
+  bool sound = true;
+  for (int64_t r = 0; r < g.N; ++r) {
+    const int32_t node = g.order[r];
+    if (!whole && g.owner[node] != strip) continue;
+    const int32_t nl = whole ? node : node_l[node];
+    if (nl < 0) sound = false;
+    out.own.push_back(nl);
+    for (int32_t k = g.fptr[r]; k < g.fptr[r + 1]; ++k) {
+      const int32_t el = whole ? g.fidx[k] : edge_l[g.fidx[k]];
+      if (el < 0) sound = false;
+      out.fidx.push_back(el);
+    }
+    for (int32_t k = g.bptr[r]; k < g.bptr[r + 1]; ++k) {
+      const int32_t el = whole ? g.bidx[k] : edge_l[g.bidx[k]];
+      if (el < 0) sound = false;
+      out.bidx.push_back(el);
+    }
+    out.fptr.push_back((int32_t)out.fidx.size());
+    out.bptr.push_back((int32_t)out.bidx.size());
+  }
+  if (!sound) err = "stereo_trws: a strip's belief lists name a node or edge the strip does not store";
+  return sound;
+}
+
 }  // namespace stereo
 
 extern "C" int stereo_trws_analyze(int64_t N, int64_t E, const uint32_t *conn, int64_t *rank,
@@ -988,5 +1023,39 @@ extern "C" int stereo_trws_strip_layout_host(int64_t N, int64_t E, const uint32_
     return 0;
   } catch (const std::exception &e) {
     return stereo::fail(std::string("stereo_trws_strip_layout_host: ") + e.what(), err, errcap);
+  }
+}
+
+// Host-only view of the lists the belief kernels walk on one strip (build_strip_belief_lists): own (n_own entries,
+// strip-local node ids in rank order), fptr / bptr (n_own + 1), fidx / bidx (n_fwd / n_bwd strip-local edge ids).
+// nstrips == 1: the whole problem (owner may be NULL).
+extern "C" int stereo_trws_strip_belief_lists_host(int64_t N, int64_t E, const uint32_t *conn, const int32_t *owner,
+                                                   int nstrips, int strip, int64_t *n_own, int64_t *n_fwd, int64_t *n_bwd,
+                                                   int32_t *own, int32_t *fptr, int32_t *fidx, int32_t *bptr, int32_t *bidx,
+                                                   char *err, size_t errcap) {
+  if (!conn || nstrips < 1 || strip < 0 || strip >= nstrips || (nstrips > 1 && !owner))
+    return stereo::fail("stereo_trws_strip_belief_lists_host: bad argument", err, errcap);
+  try {
+    stereo::TrwsGraph g;
+    std::string gerr;
+    if (!stereo::build_trws_graph(N, E, conn, g, gerr, 0, nstrips > 1 ? owner : nullptr, nstrips)) return stereo::fail(gerr, err, errcap);
+    stereo::StripLayout L;
+    if (nstrips > 1) {
+      if (!g.fast_ok) return stereo::fail("stereo_trws_strip_belief_lists_host: graph outside the descriptor-driven kernels' range", err, errcap);
+      if (!stereo::build_strip_layout(g, strip, L, gerr)) return stereo::fail(gerr, err, errcap);
+    }
+    stereo::StripBeliefLists B;
+    if (!stereo::build_strip_belief_lists(g, strip, L.nodes, L.edges, B, gerr)) return stereo::fail(gerr, err, errcap);
+    if (n_own) *n_own = (int64_t)B.own.size();
+    if (n_fwd) *n_fwd = (int64_t)B.fidx.size();
+    if (n_bwd) *n_bwd = (int64_t)B.bidx.size();
+    if (own) std::copy(B.own.begin(), B.own.end(), own);
+    if (fptr) std::copy(B.fptr.begin(), B.fptr.end(), fptr);
+    if (fidx) std::copy(B.fidx.begin(), B.fidx.end(), fidx);
+    if (bptr) std::copy(B.bptr.begin(), B.bptr.end(), bptr);
+    if (bidx) std::copy(B.bidx.begin(), B.bidx.end(), bidx);
+    return 0;
+  } catch (const std::exception &e) {
+    return stereo::fail(std::string("stereo_trws_strip_belief_lists_host: ") + e.what(), err, errcap);
   }
 }

@@ -163,4 +163,15 @@ struct StripLayout {
 };
 bool build_strip_layout(const TrwsGraph &g, int strip, StripLayout &out, std::string &err);
 
+// What the two belief kernels (trws_beliefs.hip) walk on a strip: its own nodes in rank order as
+// strip-local ids, and per such node the firstForward / firstBackward lists as strip-local edge ids in the GLOBAL
+// list order (a belief is a sequence of fp64 adds in that order).  Every listed edge has an own endpoint, so it
+// has a local id.  nodes / edges: the strip's local -> global ids (StripLayout); one strip (g.nstrips == 1, no
+// owner table): the whole problem's lists, ids unchanged.
+struct StripBeliefLists {
+  std::vector<int32_t> own, fptr, fidx, bptr, bidx;
+};
+bool build_strip_belief_lists(const TrwsGraph &g, int strip, const std::vector<int32_t> &nodes, const std::vector<int32_t> &edges,
+                              StripBeliefLists &out, std::string &err);
+
 }  // namespace stereo

@@ -69,6 +69,30 @@ void launch_beliefs_accum(const double *unary, const double *msg, const int32_t 
 void launch_beliefs_finish(const double *part, const double *msg, const int32_t *order, const int32_t *bptr,
                            const int32_t *bidx, int K, int64_t N, double *mm, double *conf, int32_t *argmin,
                            hipStream_t s);
-
+// phase 2 of a strip with its rows written at map[local node id] (local -> global) in arrays of the whole problem
+void launch_beliefs_finish_map(const double *part, const double *msg, const int32_t *order, const int32_t *bptr,
+                               const int32_t *bidx, const int64_t *map, int K, int64_t N, double *mm, double *conf,
+                               int32_t *argmin, hipStream_t s);
+// Either phase for several plans in ONE launch (the logical strips of a device, the members of a batch): a table of
+// blocks in device memory, workgroup b works for plan m with first[m] <= b < first[m + 1] (beliefs_workgroups each).
+// Phase 1: in = unary, ptr / idx = firstForward lists, out = partial sums.  Phase 2: in = partial sums, ptr / idx =
+// firstBackward lists, map = local -> global node ids or NULL; one output set for all plans.
+struct BeliefBlock {
+  const double *in, *msg;
+  const int32_t *order, *ptr, *idx;
+  const int64_t *map;
+  double *out;
+  int64_t n;
+  int K, lg;
+};
+struct BeliefGroupArgs {
+  const BeliefBlock *pp;
+  int n;
+  int first[kMaxGroup + 1];
+};
+int beliefs_lanes_log2(int K);
+int beliefs_workgroups(int64_t N, int K);
+void launch_beliefs_accum_group(const BeliefGroupArgs &ga, hipStream_t s);
+void launch_beliefs_finish_group(const BeliefGroupArgs &ga, double *mm, double *conf, int32_t *argmin, hipStream_t s);
 
 }  // namespace stereo

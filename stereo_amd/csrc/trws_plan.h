@@ -24,13 +24,14 @@ constexpr int kCtlWords = 8;  // d_ctl: ticket, abort flag, four words of give-u
 static_assert(kFamilyPipeMaxK == kWave && kFamilyPipe2MaxK == 2 * kWave && kFamilyWideMaxK == 4 * kWave &&
               kFamilyGenericMaxK == kGenericMaxK && kFamilyLargeMaxK == kLargeMaxK, "trws_family.h restates the kernels' label ranges");
 
-// The environment switches a plan freezes at creation (the last two are read by the gateway and by trws_graph.cpp).
+// The environment switches a plan freezes at creation (the last three are read by the gateway and by trws_graph.cpp).
 // Creation reads its switches through this table and the gateway's cache key is made of the same table: a cached
 // plan must not outlive them.
-enum TrwsSwitch { kSwFast, kSwSpec, kSwGranules, kSwCertificate, kSwSpinSeconds, kSwProf, kSwTimeline, kSwFineGrained, kSwGpus, kSwSpecSeg, kSwCount };
+enum TrwsSwitch { kSwFast, kSwSpec, kSwGranules, kSwCertificate, kSwSpinSeconds, kSwProf, kSwTimeline, kSwFineGrained, kSwGpus, kSwSpecSeg, kSwBeliefsStrips, kSwCount };
 constexpr const char *kTrwsSwitchNames[kSwCount] = {
     "STEREO_HIP_TRWS_FAST", "STEREO_HIP_TRWS_SPEC", "STEREO_HIP_TRWS_GRANULES", "STEREO_HIP_TRWS_CERTIFICATE", "STEREO_HIP_TRWS_SPIN_SECONDS",
-    "STEREO_HIP_TRWS_PROF", "STEREO_HIP_TRWS_TIMELINE", "STEREO_HIP_STRIPS_FINEGRAINED", "STEREO_HIP_GPUS", "STEREO_HIP_TRWS_SPEC_SEG"};
+    "STEREO_HIP_TRWS_PROF", "STEREO_HIP_TRWS_TIMELINE", "STEREO_HIP_STRIPS_FINEGRAINED", "STEREO_HIP_GPUS", "STEREO_HIP_TRWS_SPEC_SEG",
+    "STEREO_HIP_TRWS_BELIEFS_STRIPS"};
 inline const char *trws_switch(TrwsSwitch s) { return std::getenv(kTrwsSwitchNames[s]); }
 inline std::string trws_env_key() {
   std::string k;
@@ -126,8 +127,16 @@ struct stereo_trws_plan {
   bool spec_window = false;    // the positions are uniformly spaced over the window rounded up to four (finish_inputs)
   // node beliefs (stereo_trws_plan_keep_min_marginals): phase 1's partial sums D_i + firstForward
   // messages, K x N in node-id order; allocated only while the flag is on.  mm_ready: phase 1 ran in the last iteration
+  // A strip keeps them for its own nodes only (K x n_own, by strip-local id) and walks lists of its own
+  // (trws_graph.h: StripBeliefLists), built and uploaded when the flag is turned on.
   bool keep_mm = false, mm_ready = false;
   stereo::DevBuf<double> d_belief;
+  stereo::DevBuf<int32_t> d_bel_own, d_bel_fptr, d_bel_fidx, d_bel_bptr, d_bel_bidx;
+  // The block tables of the grouped belief launches this plan was the first plan of (phase 1 at [0], phase 2 at
+  // [kMaxGroup]) and what was sent last: a table goes to the device again only when it changes.
+  stereo::DevBuf<stereo::BeliefBlock> d_bel_table;
+  stereo::BeliefBlock bel_sent[2][stereo::kMaxGroup];
+  int bel_sent_n[2] = {0, 0};
   ~stereo_trws_plan() {
     for (int w = 0; w < 2; ++w)
       for (int k = 0; k < 3; ++k)

@@ -217,6 +217,49 @@ void launch_batch(stereo_trws_batch *B, stereo_trws_plan *const *G, const DevPar
   launch_table(in, m, d, what, s, epoch, B);
 }
 
+// What the belief kernels walk on a plan: the whole problem's lists by rank, or a strip's own (StripBeliefLists).
+struct BeliefLists {
+  const int32_t *order, *fptr, *fidx, *bptr, *bidx;
+  int64_t n;
+};
+BeliefLists belief_lists(const stereo_trws_plan *P) {
+  if (P->layout) return {P->d_bel_own.p, P->d_bel_fptr.p, P->d_bel_fidx.p, P->d_bel_bptr.p, P->d_bel_bidx.p, P->layout->n_own};
+  return {P->d_order.p, P->d_fptr.p, P->d_fidx.p, P->d_bptr.p, P->d_bidx.p, P->N};
+}
+
+// The arguments of one grouped belief launch (phase 1 or 2) for the plans G[0 .. m), with the block table on the
+// device: it lives with G[0] and is sent only when it differs from what was sent last -- a blocking copy, behind
+// everything on the device where the table may still be read (phase 2: launches on the caller's streams; phase 1's
+// last reader is behind the collect of the previous iteration).  Called before anything of the iteration is launched.
+BeliefGroupArgs belief_group(stereo_trws_plan *const *G, int m, int phase) {
+  stereo_trws_plan *P0 = G[0];
+  BeliefBlock blocks[kMaxGroup];
+  BeliefGroupArgs ga{};
+  ga.n = m;
+  for (int i = 0; i < m; ++i) {
+    const stereo_trws_plan *P = G[i];
+    const BeliefLists L = belief_lists(P);
+    BeliefBlock &b = blocks[i];
+    std::memset(&b, 0, sizeof(b));   // (compared bytewise below)
+    b.in = phase == 1 ? P->unary : P->d_belief.p; b.msg = P->d_msg.p; b.order = L.order;
+    b.ptr = phase == 1 ? L.fptr : L.bptr; b.idx = phase == 1 ? L.fidx : L.bidx;
+    b.map = (phase == 2 && P->layout) ? P->d_lnodes.p : nullptr;
+    b.out = phase == 1 ? P->d_belief.p : nullptr;
+    b.n = L.n; b.K = P->K; b.lg = beliefs_lanes_log2(P->K);
+    ga.first[i + 1] = ga.first[i] + beliefs_workgroups(L.n, P->K);
+  }
+  const int w = phase - 1;
+  if (!P0->d_bel_table.p) P0->d_bel_table.alloc(2 * kMaxGroup);
+  if (P0->bel_sent_n[w] != m || std::memcmp(P0->bel_sent[w], blocks, sizeof(BeliefBlock) * m) != 0) {
+    if (phase == 2) STEREO_HIP_CHECK(hipDeviceSynchronize());
+    STEREO_HIP_CHECK(hipMemcpy(P0->d_bel_table.p + (size_t)w * kMaxGroup, blocks, sizeof(BeliefBlock) * m, hipMemcpyHostToDevice));
+    std::memcpy(P0->bel_sent[w], blocks, sizeof(BeliefBlock) * m);
+    P0->bel_sent_n[w] = m;
+  }
+  ga.pp = P0->d_bel_table.p + (size_t)w * kMaxGroup;
+  return ga;
+}
+
 // One iteration's launches and device-to-host copies for the plans of one launch (one plan, the strips of a
 // group, or the members of a batch), without waiting for any of them.  launch(what) is the one thing that differs: the
 // plan's own launch (stereo_trws_plan_iterate), the group launch (the issue entries) or the batch launch
@@ -226,6 +269,13 @@ void launch_batch(stereo_trws_batch *B, stereo_trws_plan *const *G, const DevPar
 template <class Launch>
 void issue_iteration(stereo_trws_plan *const *plans, int n, hipStream_t s, bool beliefs, Launch launch) {
   stereo_trws_plan *P0 = plans[0];
+  // node beliefs, phase 1: one plan keeps them -- its own launch; several (logical strips, batch members) -- one launch
+  stereo_trws_plan *keeping[kMaxGroup];
+  int nkeep = 0;
+  for (int i = 0; beliefs && i < n; ++i)
+    if (plans[i]->keep_mm) keeping[nkeep++] = plans[i];
+  BeliefGroupArgs bel{};
+  if (nkeep > 1) bel = belief_group(keeping, nkeep, 1);
   if (P0->time_sweeps) STEREO_HIP_CHECK(hipEventRecord(P0->ev0, s));
   bool fwd_due = false;
   for (int i = 0; i < n; ++i) fwd_due = fwd_due || !plans[i]->fwd_pending;
@@ -240,10 +290,14 @@ void issue_iteration(stereo_trws_plan *const *plans, int n, hipStream_t s, bool 
     STEREO_HIP_CHECK(hipEventRecord(P->ev_lb, P->copy_stream));
     P->lb_in_flight = true;
   }
-  // node beliefs, phase 1: every firstForward edge holds this iteration's backward message into its tail now
-  for (int i = 0; beliefs && i < n; ++i) {
-    stereo_trws_plan *P = plans[i];
-    if (P->keep_mm) launch_beliefs_accum(P->unary, P->d_msg.p, P->d_order.p, P->d_fptr.p, P->d_fidx.p, P->K, P->N, P->d_belief.p, s);
+  // every firstForward edge holds this iteration's backward message into its tail now (in a strip's own copy too: the
+  // row of an edge is written by its two ends' visits only, and the strip's backward launch waited for both)
+  if (nkeep == 1) {
+    stereo_trws_plan *P = keeping[0];
+    const BeliefLists L = belief_lists(P);
+    launch_beliefs_accum(P->unary, P->d_msg.p, L.order, L.fptr, L.fidx, P->K, L.n, P->d_belief.p, s);
+  } else if (nkeep > 1) {
+    launch_beliefs_accum_group(bel, s);
   }
   launch(2);  // forward sweep of the NEXT iteration fused with this iteration's primal
   for (int i = 0; beliefs && i < n; ++i) plans[i]->mm_ready = plans[i]->keep_mm;
@@ -583,7 +637,7 @@ int stereo_trws_plans_issue(stereo_trws_plan *const *plans, int n, void *stream,
     if (P0->d_group.n < (size_t)n) { P0->d_group.alloc(kMaxGroup); P0->h_group.alloc(kMaxGroup); }
     for (int i = 0; i < n; ++i) P0->h_group.p[i] = make_params(plans[i], false);   // (group launches keep the plain chain schedule)
     STEREO_HIP_CHECK(hipMemcpyAsync(P0->d_group.p, P0->h_group.p, sizeof(DevParams) * n, hipMemcpyHostToDevice, s));
-    issue_iteration(plans, n, s, false, [&](int what) { launch_group(plans, n, what, s); });
+    issue_iteration(plans, n, s, true, [&](int what) { launch_group(plans, n, what, s); });
     return 0;
   } catch (const HipError &e) {
     return fail(e.msg, err, errcap);
@@ -600,7 +654,7 @@ int stereo_trws_plan_collect(stereo_trws_plan *P, double *lb_part, double *energ
   if (!P->issued) return fail("stereo_trws_plan_collect: nothing was issued", err, errcap);
   try {
     double lb = 0, en = 0;
-    if (!collect_iteration(P, P->issue_stream, &lb, &en)) return fail(gave_up_text(P), err, errcap);
+    if (!collect_iteration(P, P->issue_stream, &lb, &en)) { P->mm_ready = false; return fail(gave_up_text(P), err, errcap); }
     if (lb_part) *lb_part = lb;
     if (energy_part) *energy_part = en;
     return 0;
@@ -854,54 +908,90 @@ int stereo_trws_plan_path(stereo_trws_plan *P) {
   return (int)P->family;
 }
 
-int stereo_trws_plan_keep_min_marginals(stereo_trws_plan *P, int on, char *err, size_t errcap) {
-  DeviceScope device_scope_(P ? P->device : -1);
-  if (!P) return fail("stereo_trws_plan_keep_min_marginals: NULL plan", err, errcap);
-  if (P->nstrips > 1)
-    return fail("stereo_trws_plan_keep_min_marginals: a row strip has no min-marginals (per-strip beliefs are not "
-                "supported; solve on one plan)", err, errcap);
+// the flag on a whole-problem plan or on a strip (who: the entry's name)
+static int keep_min_marginals_impl(stereo_trws_plan *P, const char *who, int on, char *err, size_t errcap) {
+  auto release = [&] {
+    P->d_belief.release();
+    P->d_bel_own.release(); P->d_bel_fptr.release(); P->d_bel_fidx.release(); P->d_bel_bptr.release(); P->d_bel_bidx.release();
+    P->d_bel_table.release(); P->bel_sent_n[0] = P->bel_sent_n[1] = 0;
+  };
   if (!on) {
     P->keep_mm = false; P->mm_ready = false;
-    P->d_belief.release();
+    release();
     return 0;
   }
   if (P->keep_mm) return 0;
+  if (P->issued) return fail(std::string(who) + ": the iteration issued last has not been collected", err, errcap);
+  const size_t rows = P->layout ? (size_t)P->layout->n_own : (size_t)P->N;
   try {
-    P->d_belief.alloc((size_t)P->N * P->K);
+    if (P->layout) {   // a strip: its own nodes by rank and their lists under strip-local ids
+      StripBeliefLists B;
+      std::string gerr;
+      if (!build_strip_belief_lists(*P->graph, P->strip, P->layout->nodes, P->layout->edges, B, gerr)) return fail(gerr, err, errcap);
+      P->d_bel_own.upload(B.own.data(), B.own.size());
+      P->d_bel_fptr.upload(B.fptr.data(), B.fptr.size()); P->d_bel_fidx.upload(B.fidx.data(), B.fidx.size());
+      P->d_bel_bptr.upload(B.bptr.data(), B.bptr.size()); P->d_bel_bidx.upload(B.bidx.data(), B.bidx.size());
+      STEREO_HIP_CHECK(hipDeviceSynchronize());   // (the lists are host vectors of this scope)
+    }
+    P->d_belief.alloc(rows * P->K);
   } catch (const HipError &e) {
-    P->d_belief.release();
-    return fail("stereo_trws_plan_keep_min_marginals: cannot allocate the " + std::to_string(8 * (size_t)P->N * P->K) +
+    release();
+    return fail(std::string(who) + ": cannot allocate the " + std::to_string(8 * rows * P->K) +
                 "-byte belief buffer (" + e.msg + ")", err, errcap);
   }
   P->keep_mm = true; P->mm_ready = false;
   return 0;
 }
 
-static int min_marginals_impl(stereo_trws_plan *P, const char *who, double *mm, double *conf, int32_t *argmin, bool device,
-                              hipStream_t s, char *err, size_t errcap) {
-  if (!P) return fail(std::string(who) + ": NULL plan", err, errcap);
+int stereo_trws_plan_keep_min_marginals(stereo_trws_plan *P, int on, char *err, size_t errcap) {
+  DeviceScope device_scope_(P ? P->device : -1);
+  if (!P) return fail("stereo_trws_plan_keep_min_marginals: NULL plan", err, errcap);
   if (P->nstrips > 1)
-    return fail(std::string(who) + ": a row strip has no min-marginals (per-strip beliefs are not supported; solve on one plan)",
-                err, errcap);
+    return fail("stereo_trws_plan_keep_min_marginals: a row strip has no min-marginals of the whole problem (a strip keeps those "
+                "of its own nodes: stereo_trws_plan_strip_keep_min_marginals)", err, errcap);
+  return keep_min_marginals_impl(P, "stereo_trws_plan_keep_min_marginals", on, err, errcap);
+}
+
+int stereo_trws_plan_strip_keep_min_marginals(stereo_trws_plan *P, int on, char *err, size_t errcap) {
+  DeviceScope device_scope_(P ? P->device : -1);
+  if (!P) return fail("stereo_trws_plan_strip_keep_min_marginals: NULL plan", err, errcap);
+  return keep_min_marginals_impl(P, "stereo_trws_plan_strip_keep_min_marginals", on, err, errcap);
+}
+
+// what every read checks: the beliefs of the last iteration are there and nothing is in flight
+static int beliefs_readable(const stereo_trws_plan *P, const char *who, char *err, size_t errcap) {
   if (!P->keep_mm || !P->mm_ready)
     return fail(std::string(who) + ": no min-marginals to read: turn them on with stereo_trws_plan_keep_min_marginals and "
                 "iterate first (an upload, bind or reset discards them)", err, errcap);
+  if (P->issued)
+    return fail(std::string(who) + ": no min-marginals to read while an issued iteration has not been collected", err, errcap);
+  return 0;
+}
+
+// strip: the entry takes a strip and returns its own nodes' rows (K x n_own, strip-local order)
+static int min_marginals_impl(stereo_trws_plan *P, const char *who, double *mm, double *conf, int32_t *argmin, bool device,
+                              bool strip, hipStream_t s, char *err, size_t errcap) {
+  if (!P) return fail(std::string(who) + ": NULL plan", err, errcap);
+  if (P->nstrips > 1 && !strip)
+    return fail(std::string(who) + ": a row strip has no min-marginals of the whole problem (its own nodes' rows: "
+                "stereo_trws_plan_strip_min_marginals, stereo_trws_plans_min_marginals_device)", err, errcap);
+  if (int rc = beliefs_readable(P, who, err, errcap)) return rc;
   try {
-    const size_t KN = (size_t)P->N * P->K;
+    const BeliefLists L = belief_lists(P);
+    const size_t KN = (size_t)L.n * P->K;
     if (device) {
-      launch_beliefs_finish(P->d_belief.p, P->d_msg.p, P->d_order.p, P->d_bptr.p, P->d_bidx.p, P->K, P->N, mm, conf, argmin, s);
+      launch_beliefs_finish(P->d_belief.p, P->d_msg.p, L.order, L.bptr, L.bidx, P->K, L.n, mm, conf, argmin, s);
       return 0;
     }
     DevBuf<double> d_mm, d_conf;
     DevBuf<int32_t> d_arg;
     if (mm) d_mm.alloc(KN);
-    if (conf) d_conf.alloc(P->N);
-    if (argmin) d_arg.alloc(P->N);
-    launch_beliefs_finish(P->d_belief.p, P->d_msg.p, P->d_order.p, P->d_bptr.p, P->d_bidx.p, P->K, P->N, d_mm.p, d_conf.p,
-                          d_arg.p, nullptr);
+    if (conf) d_conf.alloc(L.n);
+    if (argmin) d_arg.alloc(L.n);
+    launch_beliefs_finish(P->d_belief.p, P->d_msg.p, L.order, L.bptr, L.bidx, P->K, L.n, d_mm.p, d_conf.p, d_arg.p, nullptr);
     if (mm) STEREO_HIP_CHECK(hipMemcpy(mm, d_mm.p, sizeof(double) * KN, hipMemcpyDeviceToHost));
-    if (conf) STEREO_HIP_CHECK(hipMemcpy(conf, d_conf.p, sizeof(double) * P->N, hipMemcpyDeviceToHost));
-    if (argmin) STEREO_HIP_CHECK(hipMemcpy(argmin, d_arg.p, sizeof(int32_t) * P->N, hipMemcpyDeviceToHost));
+    if (conf) STEREO_HIP_CHECK(hipMemcpy(conf, d_conf.p, sizeof(double) * L.n, hipMemcpyDeviceToHost));
+    if (argmin) STEREO_HIP_CHECK(hipMemcpy(argmin, d_arg.p, sizeof(int32_t) * L.n, hipMemcpyDeviceToHost));
     STEREO_HIP_CHECK(hipDeviceSynchronize());
     return 0;
   } catch (const HipError &e) {
@@ -912,14 +1002,53 @@ static int min_marginals_impl(stereo_trws_plan *P, const char *who, double *mm, 
 int stereo_trws_plan_min_marginals(stereo_trws_plan *P, double *min_marginals, double *confidence, int32_t *argmin, char *err,
                                    size_t errcap) {
   DeviceScope device_scope_(P ? P->device : -1);
-  return min_marginals_impl(P, "stereo_trws_plan_min_marginals", min_marginals, confidence, argmin, false, nullptr, err, errcap);
+  return min_marginals_impl(P, "stereo_trws_plan_min_marginals", min_marginals, confidence, argmin, false, false, nullptr, err, errcap);
 }
 
 int stereo_trws_plan_min_marginals_device(stereo_trws_plan *P, double *d_min_marginals, double *d_confidence,
                                           int32_t *d_argmin, void *stream, char *err, size_t errcap) {
   DeviceScope device_scope_(P ? P->device : -1);
-  return min_marginals_impl(P, "stereo_trws_plan_min_marginals_device", d_min_marginals, d_confidence, d_argmin, true,
+  return min_marginals_impl(P, "stereo_trws_plan_min_marginals_device", d_min_marginals, d_confidence, d_argmin, true, false,
                             (hipStream_t)stream, err, errcap);
+}
+
+int stereo_trws_plan_strip_min_marginals(stereo_trws_plan *P, double *min_marginals, double *confidence, int32_t *argmin,
+                                         char *err, size_t errcap) {
+  DeviceScope device_scope_(P ? P->device : -1);
+  return min_marginals_impl(P, "stereo_trws_plan_strip_min_marginals", min_marginals, confidence, argmin, false, true, nullptr, err, errcap);
+}
+
+int stereo_trws_plans_min_marginals_device(stereo_trws_plan *const *plans, int n, double *d_min_marginals, double *d_confidence,
+                                           int32_t *d_argmin, void *stream, char *err, size_t errcap) {
+  const char *who = "stereo_trws_plans_min_marginals_device";
+  DeviceScope device_scope_(plans && n > 0 && plans[0] ? plans[0]->device : -1);
+  if (!plans || n < 1 || n > kMaxGroup) return fail(std::string(who) + ": need 1 .. 16 plans", err, errcap);
+  for (int i = 0; i < n; ++i) {
+    const stereo_trws_plan *P = plans[i], *P0 = plans[0];
+    if (!P) return fail(std::string(who) + ": NULL plan", err, errcap);
+    for (int j = 0; j < i; ++j)
+      if (plans[j] == P) return fail(std::string(who) + ": a plan is named twice", err, errcap);
+    if (P->device != P0->device || P->graph != P0->graph || P->K != P0->K || P->nstrips != P0->nstrips)
+      return fail(std::string(who) + ": the plans are not strips of one problem on one device", err, errcap);
+    if (int rc = beliefs_readable(P, who, err, errcap)) return rc;
+  }
+  try {
+    hipStream_t s = (hipStream_t)stream;
+    stereo_trws_plan *P0 = plans[0];
+    if (n == 1) {
+      const BeliefLists L = belief_lists(P0);
+      if (P0->layout)
+        launch_beliefs_finish_map(P0->d_belief.p, P0->d_msg.p, L.order, L.bptr, L.bidx, P0->d_lnodes.p, P0->K, L.n, d_min_marginals,
+                                  d_confidence, d_argmin, s);
+      else
+        launch_beliefs_finish(P0->d_belief.p, P0->d_msg.p, L.order, L.bptr, L.bidx, P0->K, L.n, d_min_marginals, d_confidence, d_argmin, s);
+      return 0;
+    }
+    launch_beliefs_finish_group(belief_group(plans, n, 2), d_min_marginals, d_confidence, d_argmin, s);
+    return 0;
+  } catch (const HipError &e) {
+    return fail(e.msg, err, errcap);
+  }
 }
 
 }  // extern "C"

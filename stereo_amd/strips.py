@@ -149,6 +149,25 @@ class _StripPlan:
                                                       C.c_size_t(len(err))), err)
         return lab
 
+    def keep_min_marginals(self, on=True):
+        """Keep the beliefs of the strip's own nodes during the following iterations
+        (stereo_trws_plan_strip_keep_min_marginals): 8 K n_own bytes and one extra kernel per iteration while on."""
+        err = _lib.errbuf()
+        _lib.check(_lib.lib().stereo_trws_plan_strip_keep_min_marginals(self._h, C.c_int(int(bool(on))), err,
+                                                                        C.c_size_t(len(err))), err)
+
+    def own_min_marginals(self):
+        """(node ids, min_marginals K x n_own, confidence n_own, argmin n_own one based) of the strip's own nodes
+        after its last collected iteration (stereo_trws_plan_strip_min_marginals)."""
+        nodes, n_own, _ = self.layout()
+        mm = np.zeros((self.K, n_own), order="F")
+        conf = np.zeros(n_own)
+        arg = np.zeros(n_own, np.int32)
+        err = _lib.errbuf()
+        _lib.check(_lib.lib().stereo_trws_plan_strip_min_marginals(self._h, _ptr(mm), _ptr(conf), _ptr(arg, C.c_int32), err,
+                                                                   C.c_size_t(len(err))), err)
+        return nodes[:n_own].astype(np.int64), mm, conf, arg.astype(np.float64) + 1
+
     def info(self):
         ns, st, nf, nb, a, b = C.c_int(), C.c_int(), C.c_int64(), C.c_int64(), C.c_int(), C.c_int()
         own = C.c_int64()
@@ -279,6 +298,36 @@ class TrwsStrips:
                 lab[owner == g] = lg[owner == g]
         return lab, self.energy, self.lb, float(self.iterations)
 
+    def keep_min_marginals(self, on=True):
+        """Keep node beliefs during the following iterations, every strip those of its own nodes:
+        8 K N bytes over all strips; strips that share the device share one extra launch per iteration."""
+        for p in self.plans:
+            p.keep_min_marginals(on)
+
+    def min_marginals(self):
+        """(min_marginals K x N, confidence N, argmin N one based) of the last run, as TrwsPlan.min_marginals
+        returns them: every strip's own rows at their node ids."""
+        mm = np.zeros((self.K, self.N), order="F")
+        conf = np.zeros(self.N)
+        arg = np.zeros(self.N)
+        for p in self.plans:
+            idx, m, c, a = p.own_min_marginals()
+            mm[:, idx], conf[idx], arg[idx] = m, c, a
+        return mm, conf, arg
+
+    def min_marginals_device(self, d_min_marginals=None, d_confidence=None, d_argmin=None, stream=None):
+        """Same into device memory of the caller, as TrwsPlan.min_marginals_device (argmin int32, ZERO based): strips
+        that share the device fill the arrays in one launch (stereo_trws_plans_min_marginals_device); with a device
+        per strip use min_marginals()."""
+        if self._devices:
+            raise StereoHipError("min_marginals_device: the strips are on devices of their own; use min_marginals()")
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        handles = (C.c_void_p * self.nstrips)(*[p._h for p in self.plans])
+        err = _lib.errbuf()
+        _lib.check(_lib.lib().stereo_trws_plans_min_marginals_device(handles, C.c_int(self.nstrips), vp(d_min_marginals),
+                                                                     vp(d_confidence), vp(d_argmin), vp(stream), err,
+                                                                     C.c_size_t(len(err))), err)
+
     def path(self):
         return self.plans[0].path()
 
@@ -367,6 +416,15 @@ class TrwsStripRank:
                 return done, True
         return done, False
 
+    def keep_min_marginals(self, on=True):
+        """Collective: every rank turns the beliefs of its own nodes on (or off) between iterations."""
+        self._quiesced(self.plan.keep_min_marginals, on)
+
+    def own_min_marginals(self):
+        """(node ids owned by this rank, their min_marginals K x n_own, confidence, argmin one based) after the
+        last iteration; the ranks exchange nothing for it."""
+        return self.plan.own_min_marginals()
+
     def own_labels(self):
         """(node ids owned by this rank, their 1-based labels)."""
         lab = self.plan.labels()
@@ -415,6 +473,25 @@ def strip_layout_host(N, connectivity0, owner, nstrips, strip, direction):
     desc = np.zeros((nv.value, 64), np.int32)
     _lib.check(f(*head, _ptr(nodes, C.c_int32), _ptr(edges, C.c_int32), _ptr(desc, C.c_int32), err, C.c_size_t(len(err))), err)
     return dict(nodes=nodes, n_own=int(no.value), edges=edges, desc=desc)
+
+
+def strip_belief_lists_host(N, connectivity0, owner, nstrips, strip):
+    """Host-only: the lists the belief kernels walk on one strip (stereo_trws_strip_belief_lists_host).
+    Returns dict(own, fptr, fidx, bptr, bidx), strip-local ids; nstrips == 1: the whole problem."""
+    c = _conn_f(connectivity0)
+    E = c.shape[1]
+    owner = None if owner is None else np.ascontiguousarray(owner, dtype=np.int32)
+    no, nf, nb = C.c_int64(), C.c_int64(), C.c_int64()
+    err = _lib.errbuf()
+    f = _lib.lib().stereo_trws_strip_belief_lists_host
+    head = (C.c_int64(N), C.c_int64(E), _ptr(c, C.c_uint32), _ptr(owner, C.c_int32) if owner is not None else None,
+            C.c_int(nstrips), C.c_int(strip), C.byref(no), C.byref(nf), C.byref(nb))
+    _lib.check(f(*head, None, None, None, None, None, err, C.c_size_t(len(err))), err)
+    i32 = lambda n: np.zeros(n, np.int32)
+    out = dict(own=i32(no.value), fptr=i32(no.value + 1), fidx=i32(nf.value), bptr=i32(no.value + 1), bidx=i32(nb.value))
+    _lib.check(f(*head, *[_ptr(out[k], C.c_int32) for k in ("own", "fptr", "fidx", "bptr", "bidx")], err,
+                 C.c_size_t(len(err))), err)
+    return out
 
 
 def dataflow_reference(sched, analysis_in):
