@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <numeric>
 #include <queue>
+#include <set>
 #include <thread>
 
 namespace stereo {
@@ -64,7 +65,8 @@ int spec_segment_length() {
 #define TICK(name) do { if (std::getenv("STEREO_HIP_GRAPH_VERBOSE")) { auto now_ = std::chrono::steady_clock::now(); std::fprintf(stderr, "[graph] -> %s: %.1f ms\n", name, std::chrono::duration<double, std::milli>(now_ - tick_).count()); tick_ = now_; } } while (0)
 bool build_trws_graph(int64_t N, int64_t E, const uint32_t *conn, TrwsGraph &g,
                       std::string &err, int64_t max_resident_runs, const int32_t *owner_in, int nstrips,
-                      int64_t certainly_resident, int ordering) {
+                      int64_t certainly_resident, int ordering, int64_t row_chunk_forward, int64_t chunk_resident,
+                      int64_t row_chunk_backward) {
   auto tick_ = std::chrono::steady_clock::now();
   if (N <= 0 || E < 0) { err = "build_trws_graph: empty problem"; return false; }
   if (N >= INT32_MAX || E >= INT32_MAX) { err = "build_trws_graph: more than 2^31 nodes/edges"; return false; }
@@ -433,317 +435,448 @@ bool build_trws_graph(int64_t N, int64_t E, const uint32_t *conn, TrwsGraph &g,
           }
       }
       DTICK("dir0 tickets");
-      // ---- descriptors, in schedule order (every position is independent of the others: host threads)
-      S.desc.assign((size_t)N * W, 0);
-      DTICK("dir0 descriptor allocation");
-      auto describe = [&](int64_t pa, int64_t pb) {
-      for (int64_t p = pa; p < pb; ++p) {
-        const int32_t r = S.chain_rank[p];
-        int32_t *D = &S.desc[(size_t)p * W];
-        const int nout = optr[r + 1] - optr[r], nin = iptr[r + 1] - iptr[r];
-        const int nd = (int)deps[r].size();
-        uint32_t md = 0;
-        for (int k = 0; k < 8; ++k) {
-          int32_t e = 0, slot = -1, lbe = 0, xn = 0;
-          if (k < nout) {
-            e = oidx[optr[r] + k];
-            lbe = g.lb_pos_edge[e];
-          } else if (k < nout + nin) {
-            const int32_t ik = iptr[r] + (k - nout);
-            e = iidx[ik];
-            // slot of the edge in the outgoing list of the node visited one (0..7) or two (8..15) steps earlier
-            const int32_t o = other_end(e);
-            const int dist = (pred[r] >= 0 && o == pred[r]) ? 1 : (pred2[r] >= 0 && o == pred2[r]) ? 2 : 0;
-            if (dist)
-              for (int32_t w = optr[o]; w < optr[o + 1] && w - optr[o] < TrwsGraph::kMaxSlots; ++w)
-                if (oidx[w] == e) slot = (w - optr[o]) + 8 * (dist - 1);
-            xn = d == 0 ? g.tail[e] : g.head[e];  // the other endpoint: its label feeds the primal
+      // What follows from the runs: the descriptors, the protocol check, lazy flags, the speculative schedule and the
+      // granule marks.  Written once for the chain schedule above (into S) and once more for its sub-row runs
+      // (S.chunked, below): O_run_ptr / O_run_order are the runs over the schedule positions and their ticket order,
+      // pred / deps what a node takes in LDS / waits for.  res: the workgroups certain to be resident where the tickets
+      // may outnumber them (0: never); with_resident: the plain runs' protocol must terminate with that many, too.
+      // Returns whether the loader protocol terminates.
+      auto emit = [&](std::vector<int32_t> &O_desc, std::vector<int32_t> &O_run_ptr, std::vector<int32_t> &O_run_order,
+                      TrwsGraph::Sweep::Spec &O_spec, int64_t res, bool with_resident) -> bool {
+        // ---- descriptors, in schedule order (every position is independent of the others: host threads)
+        O_desc.assign((size_t)N * W, 0);
+        DTICK("dir0 descriptor allocation");
+        auto describe = [&](int64_t pa, int64_t pb) {
+        for (int64_t p = pa; p < pb; ++p) {
+          const int32_t r = S.chain_rank[p];
+          int32_t *D = &O_desc[(size_t)p * W];
+          const int nout = optr[r + 1] - optr[r], nin = iptr[r + 1] - iptr[r];
+          const int nd = (int)deps[r].size();
+          uint32_t md = 0;
+          for (int k = 0; k < 8; ++k) {
+            int32_t e = 0, slot = -1, lbe = 0, xn = 0;
+            if (k < nout) {
+              e = oidx[optr[r] + k];
+              lbe = g.lb_pos_edge[e];
+            } else if (k < nout + nin) {
+              const int32_t ik = iptr[r] + (k - nout);
+              e = iidx[ik];
+              // slot of the edge in the outgoing list of the node visited one (0..7) or two (8..15) steps earlier
+              const int32_t o = other_end(e);
+              const int dist = (pred[r] >= 0 && o == pred[r]) ? 1 : (pred2[r] >= 0 && o == pred2[r]) ? 2 : 0;
+              if (dist)
+                for (int32_t w = optr[o]; w < optr[o + 1] && w - optr[o] < TrwsGraph::kMaxSlots; ++w)
+                  if (oidx[w] == e) slot = (w - optr[o]) + 8 * (dist - 1);
+              xn = d == 0 ? g.tail[e] : g.head[e];  // the other endpoint: its label feeds the primal
+            }
+            if (k < nout + nin && g.mdir[e]) md |= 1u << k;
+            D[4 + k] = e; D[12 + k] = slot; D[24 + k] = lbe; D[32 + k] = xn;
           }
-          if (k < nout + nin && g.mdir[e]) md |= 1u << k;
-          D[4 + k] = e; D[12 + k] = slot; D[24 + k] = lbe; D[32 + k] = xn;
-        }
-        D[0] = g.order[r];
-        D[1] = r;
-        // bit 12: a loader may wait for this node's foreign dependencies while the node two visits
-        // earlier in the run is still being computed (its result only becomes visible one visit
-        // later): true if every dependency comes before that node in this sweep's order -- what is
-        // waited for can then not depend on anything this workgroup still holds back.  False where
-        // two chains feed each other (the interleaved last rows).
-        const int32_t pm = pred[r], pm2 = pm >= 0 ? pred[pm] : -1;
-        const int32_t bound = pm2 >= 0 ? pm2 : pm >= 0 ? pm : r;
-        bool ahead = true;
-        for (int k = 0; k < nd; ++k) ahead = ahead && (d == 0 ? deps[r][k] < bound : deps[r][k] > bound);
-        D[2] = (int32_t)((uint32_t)nout | ((uint32_t)nin << 4) | ((uint32_t)nd << 8) | ((uint32_t)ahead << 12) | (md << 16));
-        D[3] = g.lb_pos_node[r];
-        for (int k = 0; k < 4; ++k) D[20 + k] = k < nd ? deps[r][k] : 0;
-        // strips: which outgoing messages (and whose copy of the flag / label) live in a neighbour's memory
-        uint32_t remote = 0;
-        if (own) {
-          const int32_t mine = own[g.order[r]];
-          for (int k = 0; k < nout && k < 8; ++k) {
-            const int32_t e = oidx[optr[r] + k];
-            const int32_t theirs = own[d == 0 ? g.head[e] : g.tail[e]];
-            if (theirs == mine) continue;
-            remote |= 1u << k;
-            if (theirs > mine) remote |= (1u << (8 + k)) | (1u << 17); else remote |= 1u << 16;
+          D[0] = g.order[r];
+          D[1] = r;
+          // bit 12: a loader may wait for this node's foreign dependencies while the node two visits
+          // earlier in the run is still being computed (its result only becomes visible one visit
+          // later): true if every dependency comes before that node in this sweep's order -- what is
+          // waited for can then not depend on anything this workgroup still holds back.  False where
+          // two chains feed each other (the interleaved last rows).
+          const int32_t pm = pred[r], pm2 = pm >= 0 ? pred[pm] : -1;
+          const int32_t bound = pm2 >= 0 ? pm2 : pm >= 0 ? pm : r;
+          bool ahead = true;
+          for (int k = 0; k < nd; ++k) ahead = ahead && (d == 0 ? deps[r][k] < bound : deps[r][k] > bound);
+          D[2] = (int32_t)((uint32_t)nout | ((uint32_t)nin << 4) | ((uint32_t)nd << 8) | ((uint32_t)ahead << 12) | (md << 16));
+          D[3] = g.lb_pos_node[r];
+          for (int k = 0; k < 4; ++k) D[20 + k] = k < nd ? deps[r][k] : 0;
+          // strips: which outgoing messages (and whose copy of the flag / label) live in a neighbour's memory
+          uint32_t remote = 0;
+          if (own) {
+            const int32_t mine = own[g.order[r]];
+            for (int k = 0; k < nout && k < 8; ++k) {
+              const int32_t e = oidx[optr[r] + k];
+              const int32_t theirs = own[d == 0 ? g.head[e] : g.tail[e]];
+              if (theirs == mine) continue;
+              remote |= 1u << k;
+              if (theirs > mine) remote |= (1u << (8 + k)) | (1u << 17); else remote |= 1u << 16;
+            }
           }
+          D[kDescRemote] = (int32_t)remote;
+          D[kDescEpos] = g.e_pos[r];
+          // slots once more, one byte each (0xff = none), for the compute waves: words 41, 42
+          uint32_t pk[2] = {0, 0};
+          for (int k = 0; k < 8; ++k) pk[k >> 2] |= (uint32_t)(uint8_t)(int8_t)D[12 + k] << (8 * (k & 3));
+          D[41] = (int32_t)pk[0]; D[42] = (int32_t)pk[1];
+          uint32_t fetch = 0;
+          for (int k = nout; k < nout + nin && k < 8; ++k)
+            if (D[12 + k] < 0) fetch |= 1u << k;
+          D[kDescFetch] = (int32_t)fetch;
+          // twins: outgoing messages k and k' that go to the SAME neighbour (the reference's neighbourhood holds every
+          // pair of pixels as two directed edges, dispmap_super.m:279-302, and the orientation step turns both the same
+          // way): nibble k of word 56 = k' (k itself without a twin).  Pairs only, mutual; what makes twins carry the same
+          // message -- equal weights, shared positions, equal old messages -- is the kernel's to check at run time.
+          uint32_t twin = 0;
+          {
+            int tw[8];
+            for (int k = 0; k < 8; ++k) tw[k] = k;
+            for (int k = 0; k < nout && k < 8; ++k) {
+              if (tw[k] != k) continue;
+              const int32_t ek = oidx[optr[r] + k];
+              const int32_t to_k = d == 0 ? g.head[ek] : g.tail[ek];
+              for (int k2 = k + 1; k2 < nout && k2 < 8; ++k2) {
+                const int32_t e2 = oidx[optr[r] + k2];
+                if (tw[k2] == k2 && (d == 0 ? g.head[e2] : g.tail[e2]) == to_k) { tw[k] = k2; tw[k2] = k; break; }
+              }
+            }
+            for (int k = 0; k < 8; ++k) twin |= (uint32_t)tw[k] << (4 * k);
+          }
+          D[kDescTwin] = (int32_t)twin;
         }
-        D[kDescRemote] = (int32_t)remote;
-        D[kDescEpos] = g.e_pos[r];
-        // slots once more, one byte each (0xff = none), for the compute waves: words 41, 42
-        uint32_t pk[2] = {0, 0};
-        for (int k = 0; k < 8; ++k) pk[k >> 2] |= (uint32_t)(uint8_t)(int8_t)D[12 + k] << (8 * (k & 3));
-        D[41] = (int32_t)pk[0]; D[42] = (int32_t)pk[1];
-        uint32_t fetch = 0;
-        for (int k = nout; k < nout + nin && k < 8; ++k)
-          if (D[12 + k] < 0) fetch |= 1u << k;
-        D[kDescFetch] = (int32_t)fetch;
-        // twins: outgoing messages k and k' that go to the SAME neighbour (the reference's neighbourhood holds every
-        // pair of pixels as two directed edges, dispmap_super.m:279-302, and the orientation step turns both the same
-        // way): nibble k of word 56 = k' (k itself without a twin).  Pairs only, mutual; what makes twins carry the same
-        // message -- equal weights, shared positions, equal old messages -- is the kernel's to check at run time.
-        uint32_t twin = 0;
+        };
         {
-          int tw[8];
-          for (int k = 0; k < 8; ++k) tw[k] = k;
-          for (int k = 0; k < nout && k < 8; ++k) {
-            if (tw[k] != k) continue;
-            const int32_t ek = oidx[optr[r] + k];
-            const int32_t to_k = d == 0 ? g.head[ek] : g.tail[ek];
-            for (int k2 = k + 1; k2 < nout && k2 < 8; ++k2) {
-              const int32_t e2 = oidx[optr[r] + k2];
-              if (tw[k2] == k2 && (d == 0 ? g.head[e2] : g.tail[e2]) == to_k) { tw[k] = k2; tw[k2] = k; break; }
-            }
-          }
-          for (int k = 0; k < 8; ++k) twin |= (uint32_t)tw[k] << (4 * k);
+          const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+          const int64_t T = std::max<int64_t>(1, std::min<int64_t>({(int64_t)hw / 2, 32, N / 4096 + 1}));
+          std::vector<std::thread> pool;
+          for (int64_t t = 1; t < T; ++t) pool.emplace_back(describe, N * t / T, N * (t + 1) / T);
+          describe(0, N / T);
+          for (auto &th : pool) th.join();
         }
-        D[kDescTwin] = (int32_t)twin;
-      }
-      };
-      {
-        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-        const int64_t T = std::max<int64_t>(1, std::min<int64_t>({(int64_t)hw / 2, 32, N / 4096 + 1}));
-        std::vector<std::thread> pool;
-        for (int64_t t = 1; t < T; ++t) pool.emplace_back(describe, N * t / T, N * (t + 1) / T);
-        describe(0, N / T);
-        for (auto &th : pool) th.join();
-      }
-      DTICK("dir0 descriptors");
-      // ---- does the loader protocol terminate on this schedule?  (trws.py: simulate_look_ahead and
-      // simulate_spec_schedule state the rules and DESIGN.md 4.1 the kernel lines behind them; this is the same
-      // fixed point, by a work list instead of rounds: linear time.)
-      // The visit that computes position i of a run ends at a workgroup barrier the loader reaches only once the
-      // foreign dependencies of position i + 1 are visible -- and those of position i + 2 where bit 12 lets it wait
-      // two visits ahead --, and the storer raises node i's completion flag behind that barrier.  (Only
-      // trws_wide_kernel's loader B waits two visits ahead; the rule is applied whatever kernel a plan will pick --
-      // a superset of the constraints of trws_pipe_kernel and trws_pipe2_kernel, so what terminates under it
-      // terminates there, at the price of refusing a few graphs those two could take.)  Every run gets a workgroup of
-      // its own here (the ticket order with fewer workgroups is look_ahead_ok's); granules only ever make a row
-      // visible EARLIER.  On the image grid the chain builder never lets two runs wait for each other this way; on
-      // other graphs it can (two runs whose second nodes each hang on the other's first node), and such a graph must
-      // not reach the descriptor-driven kernels.
-      // The speculative schedule (sp != nullptr) makes rows visible LATER: a node of the cut run is visible to
-      // everybody else only when its SEGMENT commits (the storer holds a segment's flags back, spec_commit raises
-      // them), segment q commits behind segment q - 1, starts behind the runner's cut q, and the runner walks the
-      // cut run waiting for every node's foreign dependencies.  A one-node run that hangs on a node of a segment and
-      // feeds a later node of the SAME segment then stops that segment for good -- the host's `fine` test only looks
-      // at dependencies inside the cut run.  Ordinary runs keep the loader coupling above.
-      // wgs > 0: only wgs workgroups are resident; they draw the tickets in order, a finished task frees its workgroup
-      // for the next ticket (every task is monotone, so which tasks ever finish does not depend on timing).
-      auto protocol_terminates = [&](const TrwsGraph::Sweep::Spec *sp, int64_t wgs) -> bool {
-        const std::vector<int32_t> &rptr = sp ? sp->run_ptr : S.chain_run_ptr;
-        const int64_t T = (int64_t)rptr.size() - 1;
-        const int64_t nseg = sp ? sp->nseg : 0, L = sp ? sp->seg_len : 1;
-        // what a task can wait for: [0, N) a node's flag, N + q the runner's cut q, N + nseg + q segment q's commit
-        std::vector<uint8_t> fired(N + 2 * nseg, 0);
-        std::vector<int32_t> wait_head(N + 2 * nseg, -1), wait_next(T + 1, -1), ended(T + 1, 0), work;
-        auto blocked_on = [&](int64_t pos) -> int32_t {   // first dependency of the node at `pos` nobody can see yet
-          for (int32_t x : deps[S.chain_rank[pos]])
-            if (!fired[x]) return x;
-          return -1;
-        };
-        auto wait = [&](int64_t key, int32_t t) { wait_next[t] = wait_head[key]; wait_head[key] = t; };   // (one key at a time)
-        auto fire = [&](int64_t key) {
-          fired[key] = 1;
-          for (int32_t w = wait_head[key]; w >= 0; w = wait_next[w]) work.push_back(w);
-          wait_head[key] = -1;
-        };
-        if (sp) fired[N] = 1;
-        const int64_t ntickets = T + (sp ? 1 : 0);   // task T: the runner
-        int64_t finished = 0, started = 0;
-        auto start_more = [&]() {
-          for (; started < ntickets && (wgs <= 0 || started < wgs + finished); ++started) {
-            const int32_t k = sp ? sp->run_order[started] : S.chain_run_order.empty() ? (int32_t)started : S.chain_run_order[started];
-            work.push_back(k < 0 ? (int32_t)T : k);
-          }
-        };
-        start_more();
-        while (!work.empty() || (start_more(), !work.empty())) {
-          const int32_t k = work.back();
-          work.pop_back();
-          if (k == T) {   // the runner: ended = nodes walked
-            for (;;) {
-              const int64_t cur = sp->c0 + ended[k];
-              if (cur >= sp->c1) { ++finished; break; }
-              const int32_t x = blocked_on(cur);
+        DTICK("dir0 descriptors");
+        // ---- does the loader protocol terminate on this schedule?  (trws.py: simulate_look_ahead and
+        // simulate_spec_schedule state the rules and DESIGN.md 4.1 the kernel lines behind them; this is the same
+        // fixed point, by a work list instead of rounds: linear time.)
+        // The visit that computes position i of a run ends at a workgroup barrier the loader reaches only once the
+        // foreign dependencies of position i + 1 are visible -- and those of position i + 2 where bit 12 lets it wait
+        // two visits ahead --, and the storer raises node i's completion flag behind that barrier.  (Only
+        // trws_wide_kernel's loader B waits two visits ahead; the rule is applied whatever kernel a plan will pick --
+        // a superset of the constraints of trws_pipe_kernel and trws_pipe2_kernel, so what terminates under it
+        // terminates there, at the price of refusing a few graphs those two could take.)  Every run gets a workgroup of
+        // its own here (the ticket order with fewer workgroups is look_ahead_ok's); granules only ever make a row
+        // visible EARLIER.  On the image grid the chain builder never lets two runs wait for each other this way; on
+        // other graphs it can (two runs whose second nodes each hang on the other's first node), and such a graph must
+        // not reach the descriptor-driven kernels.
+        // The speculative schedule (sp != nullptr) makes rows visible LATER: a node of the cut run is visible to
+        // everybody else only when its SEGMENT commits (the storer holds a segment's flags back, spec_commit raises
+        // them), segment q commits behind segment q - 1, starts behind the runner's cut q, and the runner walks the
+        // cut run waiting for every node's foreign dependencies.  A one-node run that hangs on a node of a segment and
+        // feeds a later node of the SAME segment then stops that segment for good -- the host's `fine` test only looks
+        // at dependencies inside the cut run.  Ordinary runs keep the loader coupling above.
+        // wgs > 0: only wgs workgroups are resident; they draw the tickets in order, a finished task frees its workgroup
+        // for the next ticket (every task is monotone, so which tasks ever finish does not depend on timing).
+        auto protocol_terminates = [&](const TrwsGraph::Sweep::Spec *sp, int64_t wgs) -> bool {
+          const std::vector<int32_t> &rptr = sp ? sp->run_ptr : O_run_ptr;
+          const int64_t T = (int64_t)rptr.size() - 1;
+          const int64_t nseg = sp ? sp->nseg : 0, L = sp ? sp->seg_len : 1;
+          // what a task can wait for: [0, N) a node's flag, N + q the runner's cut q, N + nseg + q segment q's commit
+          std::vector<uint8_t> fired(N + 2 * nseg, 0);
+          std::vector<int32_t> wait_head(N + 2 * nseg, -1), wait_next(T + 1, -1), ended(T + 1, 0), work;
+          auto blocked_on = [&](int64_t pos) -> int32_t {   // first dependency of the node at `pos` nobody can see yet
+            for (int32_t x : deps[S.chain_rank[pos]])
+              if (!fired[x]) return x;
+            return -1;
+          };
+          auto wait = [&](int64_t key, int32_t t) { wait_next[t] = wait_head[key]; wait_head[key] = t; };   // (one key at a time)
+          auto fire = [&](int64_t key) {
+            fired[key] = 1;
+            for (int32_t w = wait_head[key]; w >= 0; w = wait_next[w]) work.push_back(w);
+            wait_head[key] = -1;
+          };
+          if (sp) fired[N] = 1;
+          const int64_t ntickets = T + (sp ? 1 : 0);   // task T: the runner
+          int64_t finished = 0, started = 0;
+          auto start_more = [&]() {
+            for (; started < ntickets && (wgs <= 0 || started < wgs + finished); ++started) {
+              const int32_t k = sp ? sp->run_order[started] : O_run_order.empty() ? (int32_t)started : O_run_order[started];
+              work.push_back(k < 0 ? (int32_t)T : k);
+            }
+          };
+          start_more();
+          while (!work.empty() || (start_more(), !work.empty())) {
+            const int32_t k = work.back();
+            work.pop_back();
+            if (k == T) {   // the runner: ended = nodes walked
+              for (;;) {
+                const int64_t cur = sp->c0 + ended[k];
+                if (cur >= sp->c1) { ++finished; break; }
+                const int32_t x = blocked_on(cur);
+                if (x >= 0) { wait(x, k); break; }
+                const int64_t off = ++ended[k];
+                if (sp->c0 + off < sp->c1 && off % L == 0 && off / L < nseg) fire(N + off / L);
+              }
+              continue;
+            }
+            const int64_t a = rptr[k], b = rptr[k + 1];
+            const int64_t seg = sp ? (int64_t)sp->kind[k] - 1 : -1;
+            if (seg >= 0) {   // a segment: ended = nodes walked; nothing is visible before the commit
+              if (!fired[N + seg]) { wait(N + seg, k); continue; }
+              int32_t x = -1;
+              while (a + ended[k] < b && (x = blocked_on(a + ended[k])) < 0) ++ended[k];
+              if (x >= 0) { wait(x, k); continue; }
+              if (seg > 0 && !fired[N + nseg + seg - 1]) { wait(N + nseg + seg - 1, k); continue; }
+              for (int64_t pos = a; pos < b; ++pos) fire(S.chain_rank[pos]);
+              fire(N + nseg + seg);
+              ++finished;
+              continue;
+            }
+            for (;;) {   // an ordinary run: ended = visits ended (the lead-in visit first)
+              if (ended[k] == b - a + 1) { ++finished; break; }
+              const int64_t i = a + ended[k] - 1;   // computed by the visit about to end (a - 1: the lead-in visit)
+              int32_t x = i + 1 < b ? blocked_on(i + 1) : -1;
+              if (x < 0 && i + 2 < b && ((O_desc[(size_t)(i + 2) * W + 2] >> 12) & 1)) x = blocked_on(i + 2);
               if (x >= 0) { wait(x, k); break; }
-              const int64_t off = ++ended[k];
-              if (sp->c0 + off < sp->c1 && off % L == 0 && off / L < nseg) fire(N + off / L);
+              ++ended[k];
+              if (i >= a) fire(S.chain_rank[i]);
             }
-            continue;
           }
-          const int64_t a = rptr[k], b = rptr[k + 1];
-          const int64_t seg = sp ? (int64_t)sp->kind[k] - 1 : -1;
-          if (seg >= 0) {   // a segment: ended = nodes walked; nothing is visible before the commit
-            if (!fired[N + seg]) { wait(N + seg, k); continue; }
-            int32_t x = -1;
-            while (a + ended[k] < b && (x = blocked_on(a + ended[k])) < 0) ++ended[k];
-            if (x >= 0) { wait(x, k); continue; }
-            if (seg > 0 && !fired[N + nseg + seg - 1]) { wait(N + nseg + seg - 1, k); continue; }
-            for (int64_t pos = a; pos < b; ++pos) fire(S.chain_rank[pos]);
-            fire(N + nseg + seg);
-            ++finished;
-            continue;
+          return finished == T + (sp ? 1 : 0);
+        };
+        bool terminates = protocol_terminates(nullptr, 0);
+        if (terminates && with_resident) terminates = protocol_terminates(nullptr, res);
+        DTICK("dir0 protocol check");
+        // Completion flags are raised either in the middle of the next visit (costs a store
+        // drain on that run's critical path, but the dependent run can follow closely) or
+        // lazily at its end (free).  A run is "lazy" if nobody else reads its flags before it
+        // has finished anyway: no node of another run depends on any node but its last.
+        const int64_t RR = (int64_t)O_run_ptr.size() - 1;
+        std::vector<int32_t> run_at(N);
+        for (int64_t k = 0; k < RR; ++k)
+          for (int64_t p = O_run_ptr[k]; p < O_run_ptr[k + 1]; ++p) run_at[S.chain_rank[p]] = (int32_t)k;
+        std::vector<uint8_t> eager(RR, 0);
+        for (int64_t r = 0; r < N; ++r)
+          for (int32_t x : deps[r]) {
+            const int32_t kx = run_at[x];
+            if (x != S.chain_rank[O_run_ptr[kx + 1] - 1]) eager[kx] = 1;
           }
-          for (;;) {   // an ordinary run: ended = visits ended (the lead-in visit first)
-            if (ended[k] == b - a + 1) { ++finished; break; }
-            const int64_t i = a + ended[k] - 1;   // computed by the visit about to end (a - 1: the lead-in visit)
-            int32_t x = i + 1 < b ? blocked_on(i + 1) : -1;
-            if (x < 0 && i + 2 < b && ((S.desc[(size_t)(i + 2) * W + 2] >> 12) & 1)) x = blocked_on(i + 2);
-            if (x >= 0) { wait(x, k); break; }
-            ++ended[k];
-            if (i >= a) fire(S.chain_rank[i]);
-          }
-        }
-        return finished == T + (sp ? 1 : 0);
-      };
-      protocol_ok[d] = protocol_terminates(nullptr, 0);
-      DTICK("dir0 protocol check");
-      // Completion flags are raised either in the middle of the next visit (costs a store
-      // drain on that run's critical path, but the dependent run can follow closely) or
-      // lazily at its end (free).  A run is "lazy" if nobody else reads its flags before it
-      // has finished anyway: no node of another run depends on any node but its last.
-      const int64_t RR = (int64_t)S.chain_run_ptr.size() - 1;
-      std::vector<int32_t> run_at(N);
-      for (int64_t k = 0; k < RR; ++k)
-        for (int64_t p = S.chain_run_ptr[k]; p < S.chain_run_ptr[k + 1]; ++p) run_at[S.chain_rank[p]] = (int32_t)k;
-      std::vector<uint8_t> eager(RR, 0);
-      for (int64_t r = 0; r < N; ++r)
-        for (int32_t x : deps[r]) {
-          const int32_t kx = run_at[x];
-          if (x != S.chain_rank[S.chain_run_ptr[kx + 1] - 1]) eager[kx] = 1;
-        }
-      for (int64_t k = 0; k < RR; ++k)
-        for (int64_t p = S.chain_run_ptr[k]; p < S.chain_run_ptr[k + 1]; ++p) S.desc[(size_t)p * W + 40] = eager[k];
-      S.chain_run_strip.clear();
-      if (own)
-        for (int64_t k = 0; k < RR; ++k) S.chain_run_strip.push_back(own[g.order[S.chain_rank[S.chain_run_ptr[k]]]]);
-      // ---- speculative schedule of the one long serial run (trws_graph.h: Sweep::Spec)
-      S.spec = TrwsGraph::Sweep::Spec();
-      if (ok && !own && RR >= 2) {
-        TrwsGraph::Sweep::Spec sp;
-        int64_t best = -1, len1 = 0, len2 = 0;
-        for (int64_t k = 0; k < RR; ++k) {
-          const int64_t len = S.chain_run_ptr[k + 1] - S.chain_run_ptr[k];
-          if (len > len1) { len2 = len1; len1 = len; best = k; } else if (len > len2) len2 = len;
-        }
-        const int L = spec_segment_length();
-        sp.run = (int32_t)best; sp.c0 = S.chain_run_ptr[best]; sp.c1 = S.chain_run_ptr[best + 1];
-        sp.seg_len = L; sp.nseg = (int32_t)(len1 / L); sp.max_len = (int32_t)(len1 - (int64_t)(sp.nseg - 1) * L);
-        bool fine = sp.nseg >= 8 && sp.nseg < (1 << 20) && len1 + 8 >= 2 * len2;
-        auto seg_of = [&](int64_t p) { return (int32_t)std::min<int64_t>((p - sp.c0) / L, sp.nseg - 1); };
-        std::vector<int64_t> pos_of;
-        if (fine) {
-          pos_of.assign(N, -1);
-          for (int64_t p = sp.c0; p < sp.c1; ++p) pos_of[S.chain_rank[p]] = p;
-        }
-        for (int64_t p = sp.c0; p < sp.c1 && fine; ++p) {
-          const int32_t *D = &S.desc[(size_t)p * W];
-          const int nout = D[2] & 15, nin = (D[2] >> 4) & 15, nd = (D[2] >> 8) & 15, ntot = nout + nin;
-          if (nout > 4 || nin > 4) { fine = false; break; }
-          int nfresh = 0, kfirst = ntot, slots[2] = {-1, -1};
-          for (int k = nout; k < ntot; ++k) {
-            const int sl = D[12 + k];
-            if (sl < 0) continue;
-            if (sl >= 4) { fine = false; break; }   // only what the node in front hands over, from its first four messages
-            if (nfresh == 0) kfirst = k;
-            ++nfresh;
-            if (slots[0] < 0 || slots[0] == sl) slots[0] = sl;
-            else if (slots[1] < 0 || slots[1] == sl) slots[1] = sl;
-            else fine = false;
-          }
-          if (p == sp.c0 ? nfresh != 0 : (nfresh < 1)) fine = false;
-          if (ntot - kfirst > 4 || (ntot - kfirst) - nfresh > 3) fine = false;
-          // a dependency inside the run must have committed before the runner gets here: an earlier segment
-          for (int k = 0; k < nd && fine; ++k) {
-            const int32_t x = D[20 + k];
-            if (pos_of[x] >= 0 && seg_of(pos_of[x]) >= seg_of(p)) fine = false;
-          }
-        }
-        if (fine) {
+        for (int64_t k = 0; k < RR; ++k)
+          for (int64_t p = O_run_ptr[k]; p < O_run_ptr[k + 1]; ++p) O_desc[(size_t)p * W + 40] = eager[k];
+        S.chain_run_strip.clear();
+        if (own)
+          for (int64_t k = 0; k < RR; ++k) S.chain_run_strip.push_back(own[g.order[S.chain_rank[O_run_ptr[k]]]]);
+        // ---- speculative schedule of the one long serial run (trws_graph.h: Sweep::Spec)
+        O_spec = TrwsGraph::Sweep::Spec();
+        if (ok && !own && RR >= 2) {
+          TrwsGraph::Sweep::Spec sp;
+          int64_t best = -1, len1 = 0, len2 = 0;
           for (int64_t k = 0; k < RR; ++k) {
-            if (k == best) for (int32_t q = 0; q < sp.nseg; ++q) { sp.run_ptr.push_back(sp.c0 + q * L); sp.kind.push_back(1 + q); }
-            else { sp.run_ptr.push_back(S.chain_run_ptr[k]); sp.kind.push_back(0); }
+            const int64_t len = O_run_ptr[k + 1] - O_run_ptr[k];
+            if (len > len1) { len2 = len1; len1 = len; best = k; } else if (len > len2) len2 = len;
           }
-          sp.run_ptr.push_back(S.chain_run_ptr[RR]);
-          // tickets: the runner's first, whatever the direction (the workgroup that draws it serves it before anything
-          // else, trws_pipe.hip; it waits for what it needs, holding one CU of 256), then the chain schedule's order
-          // with the cut run's ticket replaced by its segments'
-          sp.run_order.push_back(-1);
-          for (int64_t t = 0; t < RR; ++t) {
-            const int32_t k = S.chain_run_order.empty() ? (int32_t)t : S.chain_run_order[t];
-            if (k == best) for (int32_t q = 0; q < sp.nseg; ++q) sp.run_order.push_back((int32_t)best + q);
-            else sp.run_order.push_back(k < best ? k : k + sp.nseg - 1);
+          const int L = spec_segment_length();
+          sp.run = (int32_t)best; sp.c0 = O_run_ptr[best]; sp.c1 = O_run_ptr[best + 1];
+          sp.seg_len = L; sp.nseg = (int32_t)(len1 / L); sp.max_len = (int32_t)(len1 - (int64_t)(sp.nseg - 1) * L);
+          bool fine = sp.nseg >= 8 && sp.nseg < (1 << 20) && len1 + 8 >= 2 * len2;
+          auto seg_of = [&](int64_t p) { return (int32_t)std::min<int64_t>((p - sp.c0) / L, sp.nseg - 1); };
+          std::vector<int64_t> pos_of;
+          if (fine) {
+            pos_of.assign(N, -1);
+            for (int64_t p = sp.c0; p < sp.c1; ++p) pos_of[S.chain_rank[p]] = p;
           }
-          sp.ok = true;
-          // (never a schedule the host cannot show to terminate: such a graph keeps the plain chain schedule)
-          // (with every task resident, and -- where the tickets outnumber the workgroups certain to be resident -- with
-          //  that many workgroups drawing tickets in order: a segment holds its workgroup until it commits)
-          const int64_t Wres = resident > 0 && (int64_t)sp.run_order.size() > resident ? resident : 0;
-          if (protocol_terminates(&sp, 0) && (Wres == 0 || protocol_terminates(&sp, Wres))) S.spec = std::move(sp);
-        }
-      }
-      // ---- tagged-granule hand-over (word 57, trws_graph.h): the rows a node fetches from another ordinary run that
-      // drew an earlier ticket come as granules, published by the producer as soon as they are final; everything
-      // else -- the speculative schedule's cut run (its segments hold their flags back until they commit, a granule
-      // must never show an uncommitted row), rows of the same run, strips -- keeps the completion flags.
-      // (serial: a consumer marks its producer's descriptor too)
-      if (!own) {
-        std::vector<int32_t> pos_at(N), ticket_of(RR);
-        for (int64_t p = 0; p < N; ++p) pos_at[S.chain_rank[p]] = (int32_t)p;
-        for (int64_t t = 0; t < RR; ++t) ticket_of[S.chain_run_order.empty() ? t : S.chain_run_order[t]] = (int32_t)t;
-        const int32_t cut = S.spec.ok ? S.spec.run : -1;
-        for (int64_t p = 0; p < N; ++p) {
-          const int32_t r = S.chain_rank[p], kr = run_at[r];
-          if (kr == cut) continue;
-          int32_t *D = &S.desc[(size_t)p * W];
-          const int nd = (D[2] >> 8) & 15;
-          const uint32_t fetch = (uint32_t)D[kDescFetch];
-          uint32_t gm = 0;
-          for (int k = 0; k < 8; ++k) {
-            if (!((fetch >> k) & 1)) continue;
-            const int32_t ko = run_at[g.rank[D[32 + k]]];
-            if (ko != kr && ko != cut && ticket_of[ko] < ticket_of[kr]) gm |= 1u << k;
+          for (int64_t p = sp.c0; p < sp.c1 && fine; ++p) {
+            const int32_t *D = &O_desc[(size_t)p * W];
+            const int nout = D[2] & 15, nin = (D[2] >> 4) & 15, nd = (D[2] >> 8) & 15, ntot = nout + nin;
+            if (nout > 4 || nin > 4) { fine = false; break; }
+            int nfresh = 0, kfirst = ntot, slots[2] = {-1, -1};
+            for (int k = nout; k < ntot; ++k) {
+              const int sl = D[12 + k];
+              if (sl < 0) continue;
+              if (sl >= 4) { fine = false; break; }   // only what the node in front hands over, from its first four messages
+              if (nfresh == 0) kfirst = k;
+              ++nfresh;
+              if (slots[0] < 0 || slots[0] == sl) slots[0] = sl;
+              else if (slots[1] < 0 || slots[1] == sl) slots[1] = sl;
+              else fine = false;
+            }
+            if (p == sp.c0 ? nfresh != 0 : (nfresh < 1)) fine = false;
+            if (ntot - kfirst > 4 || (ntot - kfirst) - nfresh > 3) fine = false;
+            // a dependency inside the run must have committed before the runner gets here: an earlier segment
+            for (int k = 0; k < nd && fine; ++k) {
+              const int32_t x = D[20 + k];
+              if (pos_of[x] >= 0 && seg_of(pos_of[x]) >= seg_of(p)) fine = false;
+            }
           }
-          if (__builtin_popcount(gm) > 4) gm = 0;   // (the kernel sweeps at most four granule rows)
-          if (!gm) continue;
-          // a dependency whose rows all come as granules is no longer waited for by its flag
-          uint32_t flags = 0;
-          for (int q = 0; q < nd; ++q) {
-            bool feeds = false, covered = true;
-            for (int k = 0; k < 8; ++k)
-              if (((fetch >> k) & 1) && g.rank[D[32 + k]] == D[20 + q]) { feeds = true; covered = covered && ((gm >> k) & 1); }
-            if (!(feeds && covered)) flags |= 1u << q;
-          }
-          D[kDescGran] |= (int32_t)(gm | (flags << 16));
-          for (int k = 0; k < 8; ++k) {
-            if (!((gm >> k) & 1)) continue;
-            int32_t *P = &S.desc[(size_t)pos_at[g.rank[D[32 + k]]] * W];
-            const int pout = P[2] & 15;
-            for (int j = 0; j < pout; ++j)
-              if (P[4 + j] == D[4 + k]) P[kDescGran] |= (int32_t)((1u << (8 + j)) | (1u << 20));
+          if (fine) {
+            for (int64_t k = 0; k < RR; ++k) {
+              if (k == best) for (int32_t q = 0; q < sp.nseg; ++q) { sp.run_ptr.push_back(sp.c0 + q * L); sp.kind.push_back(1 + q); }
+              else { sp.run_ptr.push_back(O_run_ptr[k]); sp.kind.push_back(0); }
+            }
+            sp.run_ptr.push_back(O_run_ptr[RR]);
+            // tickets: the runner's first, whatever the direction (the workgroup that draws it serves it before anything
+            // else, trws_pipe.hip; it waits for what it needs, holding one CU of 256), then the chain schedule's order
+            // with the cut run's ticket replaced by its segments'
+            sp.run_order.push_back(-1);
+            for (int64_t t = 0; t < RR; ++t) {
+              const int32_t k = O_run_order.empty() ? (int32_t)t : O_run_order[t];
+              if (k == best) for (int32_t q = 0; q < sp.nseg; ++q) sp.run_order.push_back((int32_t)best + q);
+              else sp.run_order.push_back(k < best ? k : k + sp.nseg - 1);
+            }
+            sp.ok = true;
+            // (never a schedule the host cannot show to terminate: such a graph keeps the plain chain schedule)
+            // (with every task resident, and -- where the tickets outnumber the workgroups certain to be resident -- with
+            //  that many workgroups drawing tickets in order: a segment holds its workgroup until it commits)
+            const int64_t Wres = res > 0 && (int64_t)sp.run_order.size() > res ? res : 0;
+            if (protocol_terminates(&sp, 0) && (Wres == 0 || protocol_terminates(&sp, Wres))) O_spec = std::move(sp);
           }
         }
+        // ---- tagged-granule hand-over (word 57, trws_graph.h): the rows a node fetches from another ordinary run that
+        // drew an earlier ticket come as granules, published by the producer as soon as they are final; everything
+        // else -- the speculative schedule's cut run (its segments hold their flags back until they commit, a granule
+        // must never show an uncommitted row), rows of the same run, strips -- keeps the completion flags.
+        // (serial: a consumer marks its producer's descriptor too)
+        if (!own) {
+          std::vector<int32_t> pos_at(N), ticket_of(RR);
+          for (int64_t p = 0; p < N; ++p) pos_at[S.chain_rank[p]] = (int32_t)p;
+          for (int64_t t = 0; t < RR; ++t) ticket_of[O_run_order.empty() ? t : O_run_order[t]] = (int32_t)t;
+          const int32_t cut = O_spec.ok ? O_spec.run : -1;
+          for (int64_t p = 0; p < N; ++p) {
+            const int32_t r = S.chain_rank[p], kr = run_at[r];
+            if (kr == cut) continue;
+            int32_t *D = &O_desc[(size_t)p * W];
+            const int nd = (D[2] >> 8) & 15;
+            const uint32_t fetch = (uint32_t)D[kDescFetch];
+            uint32_t gm = 0;
+            for (int k = 0; k < 8; ++k) {
+              if (!((fetch >> k) & 1)) continue;
+              const int32_t ko = run_at[g.rank[D[32 + k]]];
+              if (ko != kr && ko != cut && ticket_of[ko] < ticket_of[kr]) gm |= 1u << k;
+            }
+            if (__builtin_popcount(gm) > 4) gm = 0;   // (the kernel sweeps at most four granule rows)
+            if (!gm) continue;
+            // a dependency whose rows all come as granules is no longer waited for by its flag
+            uint32_t flags = 0;
+            for (int q = 0; q < nd; ++q) {
+              bool feeds = false, covered = true;
+              for (int k = 0; k < 8; ++k)
+                if (((fetch >> k) & 1) && g.rank[D[32 + k]] == D[20 + q]) { feeds = true; covered = covered && ((gm >> k) & 1); }
+              if (!(feeds && covered)) flags |= 1u << q;
+            }
+            D[kDescGran] |= (int32_t)(gm | (flags << 16));
+            for (int k = 0; k < 8; ++k) {
+              if (!((gm >> k) & 1)) continue;
+              int32_t *P = &O_desc[(size_t)pos_at[g.rank[D[32 + k]]] * W];
+              const int pout = P[2] & 15;
+              for (int j = 0; j < pout; ++j)
+                if (P[4 + j] == D[4 + k]) P[kDescGran] |= (int32_t)((1u << (8 + j)) | (1u << 20));
+            }
+          }
+        }
+        return terminates;
+      };
+      protocol_ok[d] = emit(S.desc, S.chain_run_ptr, S.chain_run_order, S.spec, resident, false);
+      // ---- sub-row runs (trws_graph.h: Sweep::Chunked): the same positions, every ordinary run longer than row_chunk cut
+      // into consecutive runs of at most row_chunk positions.  The first node of such a run has no predecessor in LDS
+      // any more: the last node of the run in front becomes one more foreign dependency, its rows come from memory (or
+      // as granules).  Tickets follow the wavefront: a linear extension of the runs' dependencies that prefers the
+      // run whose first node can start first.  Kept only if everything the chain schedule is checked for holds with
+      // chunk_resident workgroups; otherwise the direction keeps whole rows.
+      S.chunked = TrwsGraph::Sweep::Chunked();
+      const int64_t row_chunk = d == 1 && row_chunk_backward >= 0 ? row_chunk_backward : row_chunk_forward;
+      if (row_chunk > 0 && ok && !own && protocol_ok[d] && R > std::max<int64_t>(chunk_resident, 1)) {
+        TrwsGraph::Sweep::Chunked &C = S.chunked;
+        const int32_t whole = S.spec.ok ? S.spec.run : -1;   // (the speculative schedule's cut run stays in one piece)
+        std::vector<uint8_t> starts(N + 1, 0);   // by position: a run starts here
+        std::vector<int32_t> pos_of(N), c_run_at(N), c_first_lev, ready_at(N), done_at(N);
+        for (int64_t q = 0; q < N; ++q) pos_of[S.chain_rank[q]] = (int32_t)q;
+        for (int64_t k = 0; k < R; ++k) {
+          const int64_t a = S.chain_run_ptr[k], b = S.chain_run_ptr[k + 1];
+          for (int64_t at = a; at < b; at += k == whole ? b - a : row_chunk) starts[at] = 1;
+        }
+        // what the node at position q waits for: its foreign dependencies, and at the start of a piece its predecessor
+        auto each_dep = [&](int64_t q, auto &&f) {
+          const int32_t r = S.chain_rank[q];
+          for (int32_t x : deps[r]) f(x);
+          if (starts[q] && pred[r] >= 0) f(pred[r]);
+        };
+        // Tickets: of the runs whose producers all have theirs, the one whose first node can start first (then the
+        // earliest position).  Where two runs wait for each other (the first pieces of the two interleaved rows) no run is
+        // ready: the lowest run left is cut once more in front of its first node that waits for a run without a
+        // ticket, and the tickets are dealt again.  No such cut: whole rows.
+        bool fine = true;
+        int64_t RC = 0;
+        for (int round = 0; fine; ++round) {
+          C.run_ptr.clear(); C.run_order.clear(); c_first_lev.clear();
+          // when a node can start, in quarter visits: a visit takes 4, one of the speculative schedule's runner 1, and
+          // a row from another run arrives 3 behind the end of the visit that made it (row lag = hand-over + visit,
+          // DESIGN.md 4.4) -- the dependency level counts every hop as one visit, and would draw the first pieces of
+          // all rows before the second piece of the first
+          for (int64_t pp = 0; pp < N; ++pp) {
+            const int32_t r = d == 0 ? (int32_t)pp : (int32_t)(N - 1 - pp);
+            const int64_t q = pos_of[r];
+            int32_t t = 0;
+            for (int32_t x : deps[r]) t = std::max(t, done_at[x] + 3);
+            if (pred[r] >= 0) t = std::max(t, done_at[pred[r]] + (starts[q] ? 3 : 0));
+            ready_at[r] = t;
+            done_at[r] = t + (whole >= 0 && q >= S.chain_run_ptr[whole] && q < S.chain_run_ptr[whole + 1] ? 1 : 4);
+          }
+          for (int64_t q = 0; q < N; ++q) {
+            if (starts[q]) { C.run_ptr.push_back((int32_t)q); c_first_lev.push_back(ready_at[S.chain_rank[q]]); }
+            c_run_at[q] = (int32_t)C.run_ptr.size() - 1;
+          }
+          C.run_ptr.push_back((int32_t)N);
+          RC = (int64_t)C.run_ptr.size() - 1;
+          std::vector<std::vector<int32_t>> feeds(RC);
+          std::vector<int32_t> waits(RC, 0);
+          std::vector<uint8_t> drawn(RC, 0);
+          for (int64_t q = 0; q < N; ++q)
+            each_dep(q, [&](int32_t x) {
+              const int32_t kx = c_run_at[pos_of[x]], kq = c_run_at[q];
+              if (kx != kq) { feeds[kx].push_back(kq); ++waits[kq]; }
+            });
+          typedef std::pair<int32_t, int32_t> Key;   // (start of the first node, run)
+          std::set<Key> ready, left;
+          for (int64_t k = 0; k < RC; ++k) {
+            left.insert(Key(c_first_lev[k], (int32_t)k));
+            if (!waits[k]) ready.insert(Key(c_first_lev[k], (int32_t)k));
+          }
+          bool again = false;
+          while (!left.empty()) {
+            if (ready.empty()) {
+              const int32_t k = left.begin()->second;
+              int64_t q = C.run_ptr[k];
+              for (; q < C.run_ptr[k + 1]; ++q) {
+                bool served = true;
+                each_dep(q, [&](int32_t x) { const int32_t kx = c_run_at[pos_of[x]]; served = served && (kx == k || drawn[kx]); });
+                if (!served) break;
+              }
+              if (q == C.run_ptr[k] || q == C.run_ptr[k + 1] || round >= 64) fine = false;
+              else { starts[q] = 1; again = true; }
+              break;
+            }
+            const Key top = *ready.begin();
+            ready.erase(top); left.erase(top);
+            drawn[top.second] = 1;
+            C.run_order.push_back(top.second);
+            for (int32_t k : feeds[top.second])
+              if (--waits[k] == 0) ready.insert(Key(c_first_lev[k], k));
+          }
+          if (!again) break;
+        }
+        // a piece's first node: the node in front is one more foreign dependency (the fast kernels take four)
+        bool any = false;
+        std::vector<int32_t> c_run_of(N);
+        for (int64_t q = 0; q < N && fine; ++q) {
+          const int32_t r = S.chain_rank[q];
+          c_run_of[r] = c_run_at[q];
+          if (!starts[q] || pred[r] < 0) continue;
+          fine = deps[r].size() < 4;
+          if (fine) { deps[r].push_back(pred[r]); pred[r] = -1; any = true; }
+        }
+        fine = fine && any;
+        if (fine) {
+          // the look-ahead rule of the chain schedule's tickets, on these (a linear extension looks ahead to nobody)
+          std::vector<int32_t> ticket(RC), ahead(RC, 0);
+          for (int64_t t = 0; t < RC; ++t) ticket[C.run_order[t]] = (int32_t)t;
+          for (int64_t r = 0; r < N; ++r)
+            for (int32_t x : deps[r]) {
+              const int32_t mine = ticket[c_run_of[r]], theirs = ticket[c_run_of[x]];
+              ahead[mine] = std::max(ahead[mine], theirs - mine);
+            }
+          for (int64_t t = 0; t < RC && fine; ++t)
+            if (ahead[t] > 1 || (ahead[t] == 1 && t + 1 < RC && ahead[t + 1] > 0)) fine = false;
+        }
+        if (fine) fine = emit(C.desc, C.run_ptr, C.run_order, C.spec, std::max<int64_t>(chunk_resident, 1), true);
+        // (one speculative schedule serves both sets of runs: the plan's buffers are sized by it)
+        if (fine && S.spec.ok)
+          fine = C.spec.ok && C.spec.c0 == S.spec.c0 && C.spec.c1 == S.spec.c1 && C.spec.nseg == S.spec.nseg;
+        if (fine && !S.spec.ok) C.spec = TrwsGraph::Sweep::Spec();
+        if (fine) { C.ok = true; C.chunk = (int32_t)row_chunk; }
+        else C = TrwsGraph::Sweep::Chunked();
       }
     };
 #undef DTICK
@@ -756,7 +889,7 @@ bool build_trws_graph(int64_t N, int64_t E, const uint32_t *conn, TrwsGraph &g,
       for (int d = 0; d < 2; ++d) {
         TrwsGraph::Sweep &S = g.sweep[d];
         S.desc = std::vector<int32_t>(); S.chain_rank.clear(); S.chain_run_ptr.clear(); S.chain_run_order.clear();
-        S.chain_run_strip.clear(); S.spec = TrwsGraph::Sweep::Spec();
+        S.chain_run_strip.clear(); S.spec = TrwsGraph::Sweep::Spec(); S.chunked = TrwsGraph::Sweep::Chunked();
       }
     }
   }
@@ -905,27 +1038,38 @@ static int schedule_impl(int64_t N, int64_t E, const uint32_t *conn, int64_t max
                          int direction, const int32_t *owner, int nstrips, int64_t *rank_at, int64_t *run_ptr,
                          int64_t *nruns, int64_t *ticket_run, int64_t *pred_rank, int64_t *dep_ptr,
                          int64_t *dep_rank, int64_t *run_strip, int64_t *remote, const char *who, char *err,
-                         size_t errcap) {
+                         size_t errcap, int64_t row_chunk = 0, int64_t chunk_resident = 0, int64_t *chunk_info = nullptr,
+                         int32_t *desc_out = nullptr) {
   stereo::TrwsGraph g;
   std::string gerr;
   if (!conn && E > 0) return stereo::fail(std::string(who) + ": NULL connectivity", err, errcap);
   if (direction != 0 && direction != 1) return stereo::fail(std::string(who) + ": direction must be 0 or 1", err, errcap);
-  if (!stereo::build_trws_graph(N, E, conn, g, gerr, max_resident_runs, owner, nstrips)) return stereo::fail(gerr, err, errcap);
+  if (!stereo::build_trws_graph(N, E, conn, g, gerr, max_resident_runs, owner, nstrips, 256, 0, row_chunk, chunk_resident))
+    return stereo::fail(gerr, err, errcap);
   if (!g.fast_ok) return stereo::fail(std::string(who) + ": graph not eligible for the descriptor-driven kernels", err, errcap);
   const stereo::TrwsGraph::Sweep &S = g.sweep[direction];
   constexpr int W = stereo::TrwsGraph::kDescWords;
-  const int64_t R = (int64_t)S.chain_run_ptr.size() - 1;
+  // the sub-row runs where the direction has them (chunk_info[0]), the chain schedule otherwise
+  const bool sub = S.chunked.ok;
+  const std::vector<int32_t> &S_desc = sub ? S.chunked.desc : S.desc, &S_run_ptr = sub ? S.chunked.run_ptr : S.chain_run_ptr;
+  const std::vector<int32_t> &S_run_order = sub ? S.chunked.run_order : S.chain_run_order;
+  if (chunk_info) {
+    const stereo::TrwsGraph::Sweep::Spec &sp = sub ? S.chunked.spec : S.spec;
+    chunk_info[0] = sub ? 1 : 0; chunk_info[1] = S.chunked.chunk; chunk_info[2] = sp.ok ? 1 : 0; chunk_info[3] = sp.ok ? sp.run : -1;
+  }
+  if (desc_out) std::copy(S_desc.begin(), S_desc.end(), desc_out);
+  const int64_t R = (int64_t)S_run_ptr.size() - 1;
   if (nruns) *nruns = R;
   for (int64_t p = 0; p < N; ++p) if (rank_at) rank_at[p] = S.chain_rank[p];
-  for (int64_t k = 0; k <= R; ++k) if (run_ptr) run_ptr[k] = S.chain_run_ptr[k];
-  for (int64_t t = 0; t < R; ++t) if (ticket_run) ticket_run[t] = S.chain_run_order.empty() ? t : S.chain_run_order[t];
+  for (int64_t k = 0; k <= R; ++k) if (run_ptr) run_ptr[k] = S_run_ptr[k];
+  for (int64_t t = 0; t < R; ++t) if (ticket_run) ticket_run[t] = S_run_order.empty() ? t : S_run_order[t];
   for (int64_t k = 0; k < R; ++k) if (run_strip) run_strip[k] = S.chain_run_strip.empty() ? 0 : S.chain_run_strip[k];
   // predecessor and dependencies as the kernels see them: from the descriptors
   int64_t dp = 0;
   std::vector<int64_t> pos_of(N);
   for (int64_t p = 0; p < N; ++p) pos_of[S.chain_rank[p]] = p;
   for (int64_t r = 0; r < N; ++r) {
-    const int32_t *D = &S.desc[(size_t)pos_of[r] * W];
+    const int32_t *D = &S_desc[(size_t)pos_of[r] * W];
     const int nout = D[2] & 15, nin = (D[2] >> 4) & 15, nd = (D[2] >> 8) & 15;
     int64_t pr = -1;
     for (int k = nout; k < nout + nin; ++k)
@@ -955,6 +1099,20 @@ extern "C" int stereo_trws_schedule_strips(int64_t N, int64_t E, const uint32_t 
   if (nstrips > 1 && !owner) return stereo::fail("stereo_trws_schedule_strips: NULL owner", err, errcap);
   return schedule_impl(N, E, conn, max_resident_runs, direction, owner, nstrips, rank_at, run_ptr, nruns, ticket_run,
                        pred_rank, dep_ptr, dep_rank, run_strip, remote, "stereo_trws_schedule_strips", err, errcap);
+}
+
+// Host-only view of the sub-row runs (trws_graph.h: Sweep::Chunked), for CPU tests: stereo_trws_schedule's arrays for the
+// runs of at most row_chunk positions that a launch with chunk_resident resident workgroups would walk, and their
+// descriptors (N x kDescWords, may be NULL).  chunk_info[0..3] = the direction has sub-row runs (0: the arrays are the
+// chain schedule's, as from stereo_trws_schedule), chunk length, the speculative schedule exists, its cut run.
+extern "C" int stereo_trws_schedule_chunked(int64_t N, int64_t E, const uint32_t *conn, int64_t max_resident_runs, int direction,
+                                            int64_t row_chunk, int64_t chunk_resident, int64_t *chunk_info, int64_t *rank_at,
+                                            int64_t *run_ptr, int64_t *nruns, int64_t *ticket_run, int64_t *pred_rank,
+                                            int64_t *dep_ptr, int64_t *dep_rank, int32_t *desc, char *err, size_t errcap) {
+  if (row_chunk < 0 || chunk_resident < 0) return stereo::fail("stereo_trws_schedule_chunked: bad argument", err, errcap);
+  return schedule_impl(N, E, conn, max_resident_runs, direction, nullptr, 1, rank_at, run_ptr, nruns, ticket_run, pred_rank,
+                       dep_ptr, dep_rank, nullptr, nullptr, "stereo_trws_schedule_chunked", err, errcap, row_chunk,
+                       chunk_resident, chunk_info, desc);
 }
 
 // Host-only view of the speculative schedule (trws_graph.h: Sweep::Spec), for CPU tests of its dependency structure.

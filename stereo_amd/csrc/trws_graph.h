@@ -96,6 +96,18 @@ struct TrwsGraph {
       std::vector<int32_t> run_order;    // ticket -> run; -1: the runner's ticket (ticket 0)
       std::vector<int32_t> kind;         // per run: 0, or 1 + segment index
     } spec;
+    // Sub-row runs: the chain schedule with every ordinary run longer than `chunk` positions cut into
+    // consecutive runs of at most that many, so that a workgroup is held for a piece of a grid row and not for the
+    // whole of it.  Same positions (chain_rank), other runs, tickets and descriptors: a piece's first node waits for the
+    // last node of the piece in front like for any other foreign node.  The speculative schedule's cut run stays whole;
+    // `spec` is that schedule over these runs.  Built on request for one direction at a time (build_trws_graph:
+    // row_chunk), kept only where the checks of the chain schedule hold on it.
+    struct Chunked {
+      bool ok = false;
+      int32_t chunk = 0;
+      std::vector<int32_t> desc, run_ptr, run_order;   // as desc / chain_run_ptr / chain_run_order (run_order: never empty)
+      Spec spec;
+    } chunked;
   } sweep[2];
   static constexpr int kDescWords = 64;
   // every node has <= 8 incident edges and <= 4 foreign dependencies per direction, and the loader protocol
@@ -113,7 +125,10 @@ struct TrwsGraph {
 bool build_trws_graph(int64_t N, int64_t E, const uint32_t *conn, TrwsGraph &g,
                       std::string &err, int64_t max_resident_runs = 0,
                       const int32_t *owner = nullptr, int nstrips = 1, int64_t certainly_resident = 256,
-                      int ordering = 0);
+                      int ordering = 0, int64_t row_chunk = 0, int64_t chunk_resident = 0, int64_t row_chunk_backward = -1);
+// row_chunk > 0: also build Sweep::chunked with runs of at most that many positions, in every direction that has more
+// runs than chunk_resident workgroups (those certain to be resident in the launch that will walk them);
+// row_chunk_backward >= 0: the backward sweep's own length (0: whole rows there).
 // visits per segment of the speculative schedule (STEREO_HIP_TRWS_SPEC_SEG, default 16)
 int spec_segment_length();
 // ordering: 0 = SetAutomaticOrdering (ordering.cpp:7-157, what the gateway calls, trws_mex.cpp:121);

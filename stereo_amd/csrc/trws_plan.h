@@ -27,11 +27,16 @@ static_assert(kFamilyPipeMaxK == kWave && kFamilyPipe2MaxK == 2 * kWave && kFami
 // The environment switches a plan freezes at creation (the last three are read by the gateway and by trws_graph.cpp).
 // Creation reads its switches through this table and the gateway's cache key is made of the same table: a cached
 // plan must not outlive them.
-enum TrwsSwitch { kSwFast, kSwSpec, kSwGranules, kSwCertificate, kSwSpinSeconds, kSwProf, kSwTimeline, kSwFineGrained, kSwGpus, kSwSpecSeg, kSwBeliefsStrips, kSwCount };
+enum TrwsSwitch { kSwFast, kSwSpec, kSwGranules, kSwCertificate, kSwSpinSeconds, kSwProf, kSwTimeline, kSwFineGrained, kSwGpus, kSwSpecSeg, kSwBeliefsStrips, kSwRowChunk, kSwIterateAhead, kSwCount };
 constexpr const char *kTrwsSwitchNames[kSwCount] = {
     "STEREO_HIP_TRWS_FAST", "STEREO_HIP_TRWS_SPEC", "STEREO_HIP_TRWS_GRANULES", "STEREO_HIP_TRWS_CERTIFICATE", "STEREO_HIP_TRWS_SPIN_SECONDS",
     "STEREO_HIP_TRWS_PROF", "STEREO_HIP_TRWS_TIMELINE", "STEREO_HIP_STRIPS_FINEGRAINED", "STEREO_HIP_GPUS", "STEREO_HIP_TRWS_SPEC_SEG",
-    "STEREO_HIP_TRWS_BELIEFS_STRIPS"};
+    "STEREO_HIP_TRWS_BELIEFS_STRIPS", "STEREO_HIP_TRWS_ROW_CHUNK", "STEREO_HIP_TRWS_ITERATE_AHEAD"};
+// STEREO_HIP_TRWS_ROW_CHUNK unset: positions per sub-row run of the K <= 64 family in the forward and in the backward
+// sweep; 0: whole rows.  Measured: the backward sweep wants more workgroups than there are and gains
+// from pieces, the forward sweep sits at the line and only pays for their hand-overs.  The switch takes "n" for both
+// sweeps or "f,b".
+constexpr int kRowChunkDefault[2] = {0, 112};
 inline const char *trws_switch(TrwsSwitch s) { return std::getenv(kTrwsSwitchNames[s]); }
 inline std::string trws_env_key() {
   std::string k;
@@ -60,6 +65,12 @@ struct stereo_trws_plan {
   stereo::DevBuf<int32_t> d_run_ptr[2], d_dep_ptr[2], d_dep_rank[2], d_done, d_ctl;  // d_ctl: [ticket, abort, give-up report x 4]
   stereo::DevBuf<int8_t> d_in_slot[2];
   stereo::DevBuf<int32_t> d_desc[2];
+  // sub-row runs (trws_graph.h: Sweep::Chunked) of the directions that have them: what the plan's OWN launches on the
+  // K <= 64 kernel walk instead of the chain schedule (strip groups and batches, the members' own launches inside a
+  // batch included, keep that one)
+  bool sub_rows[2] = {false, false};
+  stereo::DevBuf<int32_t> d_sub_desc[2], d_sub_run_ptr[2], d_sub_run_order[2];
+  stereo::DevBuf<int32_t> d_sub_spec_run_ptr[2], d_sub_spec_run_order[2], d_sub_spec_kind[2];
   // which sweep kernel runs the plan (trws_family.h): the facts and the families still possible are fixed at creation,
   // the family follows every upload / bind (finish_inputs)
   stereo::TrwsPlanFacts facts;
@@ -94,6 +105,18 @@ struct stereo_trws_plan {
   hipStream_t copy_stream = nullptr;
   hipEvent_t ev_bwd = nullptr, ev_lb = nullptr;
   bool lb_in_flight = false;
+  // The backward sweep of the NEXT iteration, launched behind the fused launch before the host has this iteration's
+  // sums (stereo_trws_plan_iterate).  Pending: it has been launched and no iteration has taken it yet.
+  // Until one does, its lower-bound terms wait in h_lb_next, its sweep launch is not counted, and h_held has what
+  // d_fallbacks [0] and d_spec_stat [1 .. 32] read before it: a caller sees the plan as if the sweep had not run.
+  bool bwd_pending = false;
+  bool ahead_allowed = true;   // STEREO_HIP_TRWS_ITERATE_AHEAD is not 0 (measurement aid: the sweep behind the sums again)
+  hipEvent_t ev_ahead = nullptr;   // recorded behind the pending sweep: a call on another stream waits for it
+  stereo::PinnedBuf<double> h_lb_next;
+  stereo::PinnedBuf<unsigned long long> h_held;
+  int64_t held_launches = 0;
+  // ev_fwd: the fused launch and the copies behind it on its stream are done; ev_end: the iteration's terms are on the host
+  hipEvent_t ev_lb_next = nullptr, ev0_next = nullptr, ev_fwd = nullptr, ev_end = nullptr;
   double sweep_ms = 0;
   int64_t sweep_launches = 0;
   bool time_sweeps = false;
@@ -146,6 +169,11 @@ struct stereo_trws_plan {
     if (ev1) (void)hipEventDestroy(ev1);
     if (ev_bwd) (void)hipEventDestroy(ev_bwd);
     if (ev_lb) (void)hipEventDestroy(ev_lb);
+    if (ev_lb_next) (void)hipEventDestroy(ev_lb_next);
+    if (ev0_next) (void)hipEventDestroy(ev0_next);
+    if (ev_end) (void)hipEventDestroy(ev_end);
+    if (ev_fwd) (void)hipEventDestroy(ev_fwd);
+    if (ev_ahead) (void)hipEventDestroy(ev_ahead);
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
   }
 };
@@ -168,8 +196,13 @@ namespace stereo {
 
 // trws_plan.hip
 bool spec_active(const stereo_trws_plan *P);   // the speculative schedule runs with the plan's current inputs
-DevParams make_params(stereo_trws_plan *P, bool allow_spec = true);
+// allow_spec: the speculative schedule (a plan's own launches); allow_sub: its sub-row runs (a single plan, no batch)
+DevParams make_params(stereo_trws_plan *P, bool allow_spec = true, bool allow_sub = true);
+// the plan's own launches walk direction d's sub-row runs; the speculative schedule over the runs they walk
+bool own_sub_rows(const stereo_trws_plan *P, int d);
+const TrwsGraph::Sweep::Spec &own_spec(const stereo_trws_plan *P, int d);
 size_t persistent_lds_bytes(bool large, int Kp);   // dynamic LDS of the generic / the large family's sweep kernel
+constexpr int kHeldWords = 33;                     // stereo_trws_plan::h_held
 
 // trws_inputs.hip: what an upload or bind leaves to do on the device and on the positions
 void run_argsort(const double *vals, uint16_t *perm, int K, int64_t count, hipStream_t s);

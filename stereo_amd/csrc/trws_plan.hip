@@ -57,7 +57,14 @@ bool spec_active(const stereo_trws_plan *P) {
          P->pos_ascending && P->window <= 8 && P->uniform_step != 0 && P->spec_window;
 }
 
-DevParams make_params(stereo_trws_plan *P, bool allow_spec) {
+bool own_sub_rows(const stereo_trws_plan *P, int d) { return P->sub_rows[d] && P->family == TrwsFamily::Pipe && P->nstrips == 1; }
+const TrwsGraph::Sweep::Spec &own_spec(const stereo_trws_plan *P, int d) {
+  return own_sub_rows(P, d) ? P->graph->sweep[d].chunked.spec : P->graph->sweep[d].spec;
+}
+
+// allow_spec: the plan's own launches (speculative schedule); false: a launch it shares with other plans.
+// allow_sub: its sub-row runs as well -- a single plan only, not a member's own launches inside a batch.
+DevParams make_params(stereo_trws_plan *P, bool allow_spec, bool allow_sub) {
   DevParams p{};
   p.K = P->K; p.Kp = P->Kp; p.kernel = P->kernel; p.lambda = P->lambda;
   p.unary = P->unary; p.msg = P->d_msg.p; p.q = P->q; p.qprim = P->qprim; p.pos = P->pos;
@@ -108,15 +115,23 @@ DevParams make_params(stereo_trws_plan *P, bool allow_spec) {
   if (const char *dbg = std::getenv("STEREO_HIP_TRWS_DEBUG")) p.debug = std::atoi(dbg);
   p.tl_stride = p.nruns[0];
   p.self = P->d_self.p;
+  bool sub[2] = {false, false};
+  for (int d = 0; d < 2 && allow_spec && allow_sub; ++d) {
+    if (!(sub[d] = own_sub_rows(P, d))) continue;
+    const TrwsGraph::Sweep::Chunked &C = P->graph->sweep[d].chunked;
+    p.run_ptr[d] = P->d_sub_run_ptr[d].p; p.nruns[d] = p.ntickets[d] = (int)C.run_ptr.size() - 1;
+    p.run_order[d] = P->d_sub_run_order[d].p; p.desc[d] = P->d_sub_desc[d].p;
+    p.tl_stride = std::max(p.nruns[0], p.nruns[1]);
+  }
   if (allow_spec && spec_active(P)) {
     // the chain schedule with the long run cut into segments + the runner's ticket
     for (int d = 0; d < 2; ++d) {
-      const TrwsGraph::Sweep::Spec &sp = P->graph->sweep[d].spec;
-      p.run_ptr[d] = P->d_spec_run_ptr[d].p; p.nruns[d] = (int)sp.kind.size();
-      p.run_order[d] = P->d_spec_run_order[d].p; p.ntickets[d] = (int)sp.run_order.size();
-      p.spec_kind[d] = P->d_spec_kind[d].p; p.spec_c0[d] = sp.c0; p.spec_c1[d] = sp.c1;
+      const TrwsGraph::Sweep::Spec &sp = sub[d] ? P->graph->sweep[d].chunked.spec : P->graph->sweep[d].spec;
+      p.run_ptr[d] = (sub[d] ? P->d_sub_spec_run_ptr[d] : P->d_spec_run_ptr[d]).p; p.nruns[d] = (int)sp.kind.size();
+      p.run_order[d] = (sub[d] ? P->d_sub_spec_run_order[d] : P->d_spec_run_order[d]).p; p.ntickets[d] = (int)sp.run_order.size();
+      p.spec_kind[d] = (sub[d] ? P->d_sub_spec_kind[d] : P->d_spec_kind[d]).p; p.spec_c0[d] = sp.c0; p.spec_c1[d] = sp.c1;
     }
-    const TrwsGraph::Sweep::Spec &sp = P->graph->sweep[0].spec;
+    const TrwsGraph::Sweep::Spec &sp = P->graph->sweep[0].spec;   // (the same segments over either set of runs)
     p.spec_len = sp.seg_len; p.spec_nseg = sp.nseg; p.spec_max_len = sp.max_len;
     p.spec_rows = P->d_spec_rows.p; p.spec_x = P->d_spec_x.p; p.spec_undo = P->d_spec_undo.p; p.spec_stat = P->d_spec_stat.p;
     p.tl_stride = std::max(p.nruns[0], p.nruns[1]);
@@ -208,6 +223,7 @@ void launch_batch(stereo_trws_batch *B, stereo_trws_plan *const *G, const DevPar
   int m = 0, epoch = 0;
   for (int i = 0; i < n; ++i) {
     if (what == 0 && G[i]->fwd_pending) continue;
+    if (what == 1 && G[i]->bwd_pending) continue;   // (its backward sweep has run too: issue_backward_ahead)
     epoch = std::max(epoch, G[i]->epoch + 1);
     h[m] = params[i];
     in[m++] = G[i];
@@ -265,9 +281,11 @@ BeliefGroupArgs belief_group(stereo_trws_plan *const *G, int m, int phase) {
 // plan's own launch (stereo_trws_plan_iterate), the group launch (the issue entries) or the batch launch
 // (stereo_trws_batch_iterate); beliefs: with phase 1 of the node beliefs, for every plan that keeps them.
 // Strips are in one state; the members of a batch need not be: launch(0) is for the plans whose forward sweep has
-// not run yet, and the batch launch leaves the others out of it.
+// not run yet, and the batch launch leaves the others out of it.  The same holds for launch(1) and a plan whose backward
+// sweep is pending (issue_backward_ahead): the iteration takes that sweep and its terms instead of launching one.
+// ahead: issue_backward_ahead follows and sends the energy terms itself, past the sweep it launches.
 template <class Launch>
-void issue_iteration(stereo_trws_plan *const *plans, int n, hipStream_t s, bool beliefs, Launch launch) {
+void issue_iteration(stereo_trws_plan *const *plans, int n, hipStream_t s, bool beliefs, Launch launch, bool ahead = false) {
   stereo_trws_plan *P0 = plans[0];
   // node beliefs, phase 1: one plan keeps them -- its own launch; several (logical strips, batch members) -- one launch
   stereo_trws_plan *keeping[kMaxGroup];
@@ -276,15 +294,26 @@ void issue_iteration(stereo_trws_plan *const *plans, int n, hipStream_t s, bool 
     if (plans[i]->keep_mm) keeping[nkeep++] = plans[i];
   BeliefGroupArgs bel{};
   if (nkeep > 1) bel = belief_group(keeping, nkeep, 1);
-  if (P0->time_sweeps) STEREO_HIP_CHECK(hipEventRecord(P0->ev0, s));
-  bool fwd_due = false;
-  for (int i = 0; i < n; ++i) fwd_due = fwd_due || !plans[i]->fwd_pending;
+  // a pending backward sweep may still be running on the stream of the call that launched it
+  for (int i = 0; i < n; ++i)
+    if (plans[i]->bwd_pending && plans[i]->issue_stream != s) STEREO_HIP_CHECK(hipStreamWaitEvent(s, plans[i]->ev_ahead, 0));
+  if (P0->bwd_pending) std::swap(P0->ev0, P0->ev0_next);   // (recorded in front of the pending sweep)
+  else if (P0->time_sweeps) STEREO_HIP_CHECK(hipEventRecord(P0->ev0, s));
+  bool fwd_due = false, bwd_due = false;
+  for (int i = 0; i < n; ++i) { fwd_due = fwd_due || !plans[i]->fwd_pending; bwd_due = bwd_due || !plans[i]->bwd_pending; }
   if (fwd_due) launch(0);
-  launch(1);
+  if (bwd_due) launch(1);
   // the backward sweep's lower-bound terms travel while the next launch runs
-  STEREO_HIP_CHECK(hipEventRecord(P0->ev_bwd, s));
+  if (bwd_due) STEREO_HIP_CHECK(hipEventRecord(P0->ev_bwd, s));
   for (int i = 0; i < n; ++i) {
     stereo_trws_plan *P = plans[i];
+    if (P->bwd_pending) {   // the pending sweep becomes this iteration's: its terms are on their way already
+      std::swap(P->h_lb.p, P->h_lb_next.p);
+      std::swap(P->ev_lb, P->ev_lb_next);
+      P->sweep_launches += P->held_launches;
+      P->held_launches = 0; P->bwd_pending = false; P->lb_in_flight = true;
+      continue;
+    }
     STEREO_HIP_CHECK(hipStreamWaitEvent(P->copy_stream, P0->ev_bwd, 0));
     STEREO_HIP_CHECK(hipMemcpyAsync(P->h_lb.p, P->d_lbterms.p, sizeof(double) * P->n_lb, hipMemcpyDeviceToHost, P->copy_stream));
     STEREO_HIP_CHECK(hipEventRecord(P->ev_lb, P->copy_stream));
@@ -305,14 +334,64 @@ void issue_iteration(stereo_trws_plan *const *plans, int n, hipStream_t s, bool 
   for (int i = 0; i < n; ++i) {
     stereo_trws_plan *P = plans[i];
     P->fwd_pending = true;
-    STEREO_HIP_CHECK(hipMemcpyAsync(P->h_en.p, P->d_eterms.p, sizeof(double) * P->n_en, hipMemcpyDeviceToHost, s));
+    if (!ahead) STEREO_HIP_CHECK(hipMemcpyAsync(P->h_en.p, P->d_eterms.p, sizeof(double) * P->n_en, hipMemcpyDeviceToHost, s));
     STEREO_HIP_CHECK(hipMemcpyAsync(P->h_ctl.p, P->d_ctl.p, kCtlWords * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     P->issued = true; P->issue_stream = s; P->timed_by = P0;
   }
 }
 
+// The backward sweep of the iteration AFTER the one issued last, right behind its fused launch: the device goes on while
+// the host waits for that iteration's terms, copies and sums them.  Whether the loop goes on is not known yet, so nothing
+// of the sweep shows until an iteration takes it (issue_iteration): the terms go to a buffer of their own, the launch is
+// not counted, and the counters the sweep adds to are read first.  The energy terms of the issued iteration -- nothing a
+// backward sweep writes -- go to the host on the copy stream, so that the sweep starts right behind the fused launch.
+// A single plan's own launches only, behind issue_iteration(.., ahead = true).
+void issue_backward_ahead(stereo_trws_plan *P, const DevParams &p, hipStream_t s) {
+  if (!P->h_lb_next.p) {
+    P->h_lb_next.alloc(P->n_lb); P->h_held.alloc(kHeldWords);
+    std::memset(P->h_held.p, 0, sizeof(unsigned long long) * kHeldWords);
+    STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_lb_next, hipEventDisableTiming));
+    STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_end, hipEventDisableTiming));
+    STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_fwd, hipEventDisableTiming));
+    STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_ahead, hipEventDisableTiming));
+    STEREO_HIP_CHECK(hipEventCreate(&P->ev0_next));
+  }
+  STEREO_HIP_CHECK(hipMemcpyAsync(P->h_held.p, P->d_fallbacks.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  if (P->d_spec_stat.p)
+    STEREO_HIP_CHECK(hipMemcpyAsync(P->h_held.p + 1, P->d_spec_stat.p, sizeof(unsigned long long) * 32, hipMemcpyDeviceToHost, s));
+  STEREO_HIP_CHECK(hipEventRecord(P->ev_fwd, s));
+  STEREO_HIP_CHECK(hipStreamWaitEvent(P->copy_stream, P->ev_fwd, 0));
+  STEREO_HIP_CHECK(hipMemcpyAsync(P->h_en.p, P->d_eterms.p, sizeof(double) * P->n_en, hipMemcpyDeviceToHost, P->copy_stream));
+  STEREO_HIP_CHECK(hipEventRecord(P->ev_end, P->copy_stream));   // what collect_iteration waits for instead of the stream
+  // d_lbterms is free once the issued iteration's terms have left it
+  if (P->lb_in_flight) STEREO_HIP_CHECK(hipStreamWaitEvent(s, P->ev_lb, 0));
+  STEREO_HIP_CHECK(hipEventRecord(P->ev0_next, s));
+  const int64_t counted = P->sweep_launches;
+  launch_persistent(P, p, 1, s);
+  P->held_launches = P->sweep_launches - counted; P->sweep_launches = counted;
+  STEREO_HIP_CHECK(hipEventRecord(P->ev_bwd, s));
+  STEREO_HIP_CHECK(hipEventRecord(P->ev_ahead, s));   // (ev_bwd is recorded again by every iteration; this one stays)
+  STEREO_HIP_CHECK(hipStreamWaitEvent(P->copy_stream, P->ev_bwd, 0));
+  STEREO_HIP_CHECK(hipMemcpyAsync(P->h_lb_next.p, P->d_lbterms.p, sizeof(double) * P->n_lb, hipMemcpyDeviceToHost, P->copy_stream));
+  STEREO_HIP_CHECK(hipEventRecord(P->ev_lb_next, P->copy_stream));
+  P->bwd_pending = true;
+}
+
+// A pending backward sweep that no iteration will take (new inputs, a reset): wait for it and give the counters back
+// what they read before it.  Its messages and flags go with the state that is reset.
+void discard_backward_ahead(stereo_trws_plan *P) {
+  if (!P->bwd_pending) return;
+  STEREO_HIP_CHECK(hipStreamSynchronize(P->issue_stream));
+  STEREO_HIP_CHECK(hipStreamSynchronize(P->copy_stream));
+  STEREO_HIP_CHECK(hipMemcpy(P->d_fallbacks.p, P->h_held.p, sizeof(unsigned long long), hipMemcpyHostToDevice));
+  if (P->d_spec_stat.p)
+    STEREO_HIP_CHECK(hipMemcpy(P->d_spec_stat.p, P->h_held.p + 1, sizeof(unsigned long long) * 32, hipMemcpyHostToDevice));
+  P->bwd_pending = false; P->held_launches = 0;
+}
+
 // Zero messages (MRFEnergy.cpp:115-133), labels, flags and every piece of iteration state.
 void reset_state(stereo_trws_plan *P) {
+  discard_backward_ahead(P);
   STEREO_HIP_CHECK(hipMemset(P->d_msg.p, 0, sizeof(double) * (size_t)P->El * P->K));
   STEREO_HIP_CHECK(hipMemset(P->d_x.p, 0, sizeof(int32_t) * P->Nl));
   STEREO_HIP_CHECK(hipMemset(P->d_done.p, 0, sizeof(int32_t) * P->d_done.n));
@@ -428,6 +507,7 @@ int stereo_trws_plan_upload(stereo_trws_plan *P, const double *unary, const doub
   bool shared = false;
   if (int rc = check_inputs("stereo_trws_plan_upload", P, unary, q, qprim, positions, alphas, tol, &shared, err, errcap)) return rc;
   try {
+    discard_backward_ahead(P);   // (it still reads the inputs that are about to be overwritten)
     const size_t K = P->K;
     // a strip keeps the rows of its own nodes + halo and of the edges with an own endpoint
     std::vector<double> part;
@@ -462,6 +542,7 @@ static int bind_device(const char *who, bool strip_local, stereo_trws_plan *P, c
   bool shared = false;
   if (int rc = check_inputs(who, P, d_unary, d_q, d_qprim, d_positions, d_alphas, tol, &shared, err, errcap)) return rc;
   try {
+    discard_backward_ahead(P);   // (nothing reads the arrays bound before once this call has returned)
     if (P->nstrips > 1 && !strip_local) {
       auto rows = [&](const double *full, DevBuf<double> &own, const DevBuf<int64_t> &ids, int64_t n, int width) {
         own.alloc((size_t)n * width);
@@ -527,7 +608,8 @@ static bool collect_iteration(stereo_trws_plan *P, hipStream_t s, double *lb_out
     STEREO_HIP_CHECK(hipEventSynchronize(P->ev_lb));
     for (int64_t i = 0; i < P->n_lb; ++i) lb += P->h_lb.p[i];
   }
-  STEREO_HIP_CHECK(hipStreamSynchronize(s));
+  // (with the next backward sweep behind it on the stream, the iteration's own end)
+  if (P->bwd_pending) STEREO_HIP_CHECK(hipEventSynchronize(P->ev_end)); else STEREO_HIP_CHECK(hipStreamSynchronize(s));
   P->issued = false;
   if (P->h_ctl.p[1]) return false;
   if (P->time_sweeps && (!P->timed_by || P->timed_by->time_sweeps)) {
@@ -574,8 +656,8 @@ static int strip_ready(stereo_trws_plan *P, const char *who, char *err, size_t e
 
 // The parameters of a plan's OWN launches (speculative schedule included), with the block once more in global memory:
 // chain_runner / spec_commit read their parameters there; sent when it changes.
-static DevParams own_params(stereo_trws_plan *P) {
-  const DevParams p = make_params(P);
+static DevParams own_params(stereo_trws_plan *P, bool allow_sub = true) {
+  const DevParams p = make_params(P, true, allow_sub);
   if (!P->self_sent || std::memcmp(P->h_self.p, &p, sizeof(DevParams)) != 0) {
     std::memcpy(P->h_self.p, &p, sizeof(DevParams));
     STEREO_HIP_CHECK(hipMemcpy(P->d_self.p, P->h_self.p, sizeof(DevParams), hipMemcpyHostToDevice));
@@ -598,7 +680,11 @@ int stereo_trws_plan_iterate(stereo_trws_plan *P, int iters, double max_relgap, 
   try {
     const DevParams p = own_params(P);
     for (int it = 0; it < iters; ++it) {
-      issue_iteration(&P, 1, s, true, [&](int what) { launch_persistent(P, p, what, s); });
+      // another iteration is asked for: its backward sweep runs while the host sums this one's terms.  (Node beliefs
+      // hang on the state between the two launches: a plan that keeps them waits.)
+      const bool ahead = it + 1 < iters && !P->keep_mm && P->ahead_allowed;
+      issue_iteration(&P, 1, s, true, [&](int what) { launch_persistent(P, p, what, s); }, ahead);
+      if (ahead) issue_backward_ahead(P, p, s);
       double lb = 0, en = 0;
       if (!collect_iteration(P, s, &lb, &en)) { P->mm_ready = false; return fail(gave_up_text(P), err, errcap); }
       P->lb = lb; P->energy = en; P->iterations += 1;
@@ -623,7 +709,7 @@ int stereo_trws_plans_issue(stereo_trws_plan *const *plans, int n, void *stream,
     stereo_trws_plan *P = plans[i], *P0 = plans[0];
     if (P->issued) return fail("stereo_trws_plans_issue: the previous iteration has not been collected", err, errcap);
     if (P->device != P0->device || P->graph != P0->graph || P->K != P0->K || P->kernel != P0->kernel ||
-        P->epoch != P0->epoch || P->fwd_pending != P0->fwd_pending || P->family != P0->family ||
+        P->epoch != P0->epoch || P->fwd_pending != P0->fwd_pending || P->bwd_pending != P0->bwd_pending || P->family != P0->family ||
         (P->pos == nullptr) != (P0->pos == nullptr) || P->mode != P0->mode)
       return fail("stereo_trws_plans_issue: the plans are not strips of one problem on one device in the same state", err, errcap);
     if (!pipelined(P->family))
@@ -734,7 +820,7 @@ int stereo_trws_batch_iterate(stereo_trws_batch *B, int iters, double max_relgap
   try {
     // (batches keep the plain chain schedule, like the strip groups)
     DevParams all[kMaxGroup], own[kMaxGroup];
-    for (int i = 0; i < n; ++i) { all[i] = make_params(B->members[i], false); own[i] = own_params(B->members[i]); }
+    for (int i = 0; i < n; ++i) { all[i] = make_params(B->members[i], false); own[i] = own_params(B->members[i], false); }
     for (int it = 0; it < iters; ++it) {
       stereo_trws_plan *G[kMaxGroup];
       DevParams params[kMaxGroup];
@@ -865,8 +951,13 @@ int stereo_trws_plan_strip_info(stereo_trws_plan *P, int *nstrips, int *strip, i
   if (nstrips) *nstrips = P->nstrips;
   if (strip) *strip = P->strip;
   if (own_nodes) *own_nodes = P->n_en;
-  if (runs_forward) *runs_forward = P->nstrips > 1 ? P->ntickets[0] : (int64_t)P->graph->sweep[0].chain_run_ptr.size() - 1;
-  if (runs_backward) *runs_backward = P->nstrips > 1 ? P->ntickets[1] : (int64_t)P->graph->sweep[1].chain_run_ptr.size() - 1;
+  // (a whole problem: the runs its own launches walk -- the sub-row runs where it has them)
+  auto own_runs = [&](int d) {
+    const stereo::TrwsGraph::Sweep &S = P->graph->sweep[d];
+    return (int64_t)(own_sub_rows(P, d) ? S.chunked.run_ptr.size() : S.chain_run_ptr.size()) - 1;
+  };
+  if (runs_forward) *runs_forward = P->nstrips > 1 ? P->ntickets[0] : own_runs(0);
+  if (runs_backward) *runs_backward = P->nstrips > 1 ? P->ntickets[1] : own_runs(1);
   if (needs_previous) *needs_previous = P->need_peer[0] ? 1 : 0;
   if (needs_next) *needs_next = P->need_peer[1] ? 1 : 0;
   return 0;

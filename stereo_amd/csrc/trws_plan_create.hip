@@ -14,12 +14,13 @@ namespace {
 // size); consecutive plans for the same image grid -- every trws() call of a fusion loop --
 // share the last one.
 struct GraphKey {
-  int64_t N = -1, E = -1, capacity = -1, cus = -1;
+  int64_t N = -1, E = -1, capacity = -1, cus = -1, chunk = 0, chunk_b = 0, chunk_resident = 0;
   int nstrips = 1, ordering = 0, seg = 0;
   const uint32_t *conn = nullptr;   // the caller's arrays in a key made for a lookup, the cache's copies in the one it keeps
   const int32_t *owner = nullptr;
   bool operator==(const GraphKey &o) const {
-    return std::tie(N, E, capacity, cus, nstrips, ordering, seg) == std::tie(o.N, o.E, o.capacity, o.cus, o.nstrips, o.ordering, o.seg) &&
+    return std::tie(N, E, capacity, cus, nstrips, ordering, seg, chunk, chunk_b, chunk_resident) ==
+               std::tie(o.N, o.E, o.capacity, o.cus, o.nstrips, o.ordering, o.seg, o.chunk, o.chunk_b, o.chunk_resident) &&
            std::memcmp(conn, o.conn, sizeof(uint32_t) * 2 * (size_t)E) == 0 &&
            (nstrips == 1 || std::memcmp(owner, o.owner, sizeof(int32_t) * (size_t)N) == 0);
   }
@@ -31,7 +32,8 @@ std::shared_ptr<const TrwsGraph> shared_graph_for(GraphKey key, std::string &ger
   std::lock_guard<std::mutex> lock(mutex);
   if (cache.g && cache.key == key) return cache.g;
   auto fresh = std::make_shared<TrwsGraph>();
-  if (!build_trws_graph(key.N, key.E, key.conn, *fresh, gerr, key.capacity, key.nstrips > 1 ? key.owner : nullptr, key.nstrips, key.cus, key.ordering))
+  if (!build_trws_graph(key.N, key.E, key.conn, *fresh, gerr, key.capacity, key.nstrips > 1 ? key.owner : nullptr, key.nstrips, key.cus, key.ordering,
+                        key.chunk, key.chunk_resident, key.chunk_b))
     return nullptr;
   cache.g.reset();
   if (key.N <= (1 << 23)) {  // (3000 x 2000: 3 GB of descriptors stay in host memory until the next connectivity)
@@ -99,6 +101,18 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
       GraphKey key;
       key.N = N; key.E = E; key.capacity = capacity; key.cus = P->cus; key.nstrips = nstrips; key.ordering = ordering;
       key.seg = spec_segment_length(); key.conn = conn; key.owner = owner;
+      // Sub-row runs: for a whole problem the K <= 64 kernel may run, in the directions with more runs
+      // than the launch is certain to keep resident -- elsewhere a run finds a workgroup of its own anyway.
+      if (possible(at_best, TrwsFamily::Pipe) && nstrips == 1) {
+        key.chunk = kRowChunkDefault[0]; key.chunk_b = kRowChunkDefault[1];
+        if (const char *c = trws_switch(kSwRowChunk)) {
+          key.chunk = key.chunk_b = std::max(0, std::atoi(c));
+          if (const char *comma = std::strchr(c, ',')) key.chunk_b = std::max(0, std::atoi(comma + 1));
+        }
+        key.chunk_resident = max_blocks > 0 ? std::min<int64_t>(P->cus, max_blocks) : P->cus;
+        if (const char *be = std::getenv("STEREO_HIP_TRWS_BLOCKS"))
+          if (std::atoi(be) > 0) key.chunk_resident = std::min<int64_t>(key.chunk_resident, std::atoi(be));
+      }
       P->graph = shared_graph_for(key, gerr);
       if (!P->graph) return fail(gerr, err, errcap);
     }
@@ -151,6 +165,12 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
         P->d_chain_run_ptr[d].upload(S.chain_run_ptr.data(), S.chain_run_ptr.size());
         if (!S.chain_run_order.empty()) P->d_chain_run_order[d].upload(S.chain_run_order.data(), S.chain_run_order.size());
       }
+      if (g.fast_ok && S.chunked.ok && possible(at_best, TrwsFamily::Pipe) && !share) {
+        P->sub_rows[d] = true;
+        P->d_sub_desc[d].upload(S.chunked.desc.data(), S.chunked.desc.size());
+        P->d_sub_run_ptr[d].upload(S.chunked.run_ptr.data(), S.chunked.run_ptr.size());
+        P->d_sub_run_order[d].upload(S.chunked.run_order.data(), S.chunked.run_order.size());
+      }
     }
     }
     {
@@ -169,6 +189,12 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
           P->d_spec_run_ptr[d].upload(sp.run_ptr.data(), sp.run_ptr.size());
           P->d_spec_run_order[d].upload(sp.run_order.data(), sp.run_order.size());
           P->d_spec_kind[d].upload(sp.kind.data(), sp.kind.size());
+          if (P->sub_rows[d]) {
+            const TrwsGraph::Sweep::Spec &cs = g.sweep[d].chunked.spec;
+            P->d_sub_spec_run_ptr[d].upload(cs.run_ptr.data(), cs.run_ptr.size());
+            P->d_sub_spec_run_order[d].upload(cs.run_order.data(), cs.run_order.size());
+            P->d_sub_spec_kind[d].upload(cs.kind.data(), cs.kind.size());
+          }
         }
         const size_t ml = (size_t)std::max(s0.max_len, s1.max_len);
         P->d_spec_rows.alloc((size_t)s0.nseg * 8 * K);
@@ -196,6 +222,7 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
     P->d_fallbacks.alloc(1);
     STEREO_HIP_CHECK(hipMemset(P->d_fallbacks.p, 0, sizeof(unsigned long long)));
     if (const char *c = trws_switch(kSwCertificate)) P->certificate = std::string(c) != "0";
+    if (const char *c = trws_switch(kSwIterateAhead)) P->ahead_allowed = std::atoi(c) != 0;
     {
       // how long a visit may wait for another workgroup before the launch gives up: inside one launch
       // a flag is late by microseconds; a neighbouring strip's launch belongs to another process and
@@ -207,7 +234,9 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
     if (trws_switch(kSwProf)) { P->d_prof.alloc(64); STEREO_HIP_CHECK(hipMemset(P->d_prof.p, 0, 512)); }
     if (trws_switch(kSwTimeline))
       P->d_timeline.alloc(4 * std::max({g.sweep[0].run_ptr.size(), g.sweep[0].chain_run_ptr.size(), g.sweep[1].chain_run_ptr.size(),
-                                         g.sweep[0].spec.kind.size() + 1, g.sweep[1].spec.kind.size() + 1}) + 8);
+                                         g.sweep[0].spec.kind.size() + 1, g.sweep[1].spec.kind.size() + 1,
+                                         g.sweep[0].chunked.run_ptr.size(), g.sweep[1].chunked.run_ptr.size(),
+                                         g.sweep[0].chunked.spec.kind.size() + 1, g.sweep[1].chunked.spec.kind.size() + 1}) + 8);
     STEREO_HIP_CHECK(hipMemset(P->d_done.p, 0, sizeof(int32_t) * P->d_done.n));
     STEREO_HIP_CHECK(hipMemset(P->d_ctl.p, 0, sizeof(int32_t) * kCtlWords));
     {
@@ -217,6 +246,10 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
         runs = std::max<int64_t>({runs, (int64_t)g.sweep[0].chain_run_ptr.size() - 1, (int64_t)g.sweep[1].chain_run_ptr.size() - 1});
       if (nstrips > 1) runs = std::max<int64_t>({1, (int64_t)P->ntickets[0], (int64_t)P->ntickets[1]});
       if (P->spec_allowed) runs = std::max<int64_t>({runs, (int64_t)g.sweep[0].spec.run_order.size(), (int64_t)g.sweep[1].spec.run_order.size()});
+      for (int d = 0; d < 2; ++d)
+        if (P->sub_rows[d])
+          runs = std::max<int64_t>({runs, (int64_t)g.sweep[d].chunked.run_ptr.size() - 1,
+                                    P->spec_allowed ? (int64_t)g.sweep[d].chunked.spec.run_order.size() : 0});
       P->grid_blocks = (int)std::min<int64_t>(runs, P->cus * per_cu);
       if (max_blocks > 0) P->grid_blocks = std::min(P->grid_blocks, max_blocks);
     }
@@ -276,6 +309,7 @@ int stereo_trws_plan_create_strip(int kernel, int K, int64_t N, int64_t E, const
 
 void stereo_trws_plan_destroy(stereo_trws_plan *plan) {
   DeviceScope device_scope_(plan ? plan->device : -1);
+  if (plan && plan->bwd_pending) (void)hipDeviceSynchronize();   // (a backward sweep launched ahead may still be running)
   if (plan && plan->d_timeline.p) print_timeline(plan);
   if (plan && plan->d_prof.p) print_profile(plan);
   delete plan;

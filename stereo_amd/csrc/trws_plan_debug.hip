@@ -52,13 +52,19 @@ __global__ __launch_bounds__(kWave) void trws_messages_kernel(DevParams p, int K
 void print_timeline(const stereo_trws_plan *plan) {
   const bool chain = pipelined(plan->family);
   const bool spec = spec_active(plan);
-  const size_t R = spec ? std::max(plan->graph->sweep[0].spec.kind.size(), plan->graph->sweep[1].spec.kind.size())
+  // (the stride of make_params: the runs the plan's own launches walk)
+  const bool sub = own_sub_rows(plan, 0) || own_sub_rows(plan, 1);
+  auto own_runs = [&](int d) {
+    return own_sub_rows(plan, d) ? plan->graph->sweep[d].chunked.run_ptr.size() - 1 : plan->graph->sweep[d].chain_run_ptr.size() - 1;
+  };
+  const size_t R = spec ? std::max(own_spec(plan, 0).kind.size(), own_spec(plan, 1).kind.size())
+                        : sub ? std::max(own_runs(0), own_runs(1))
                         : (chain ? plan->graph->sweep[0].chain_run_ptr.size() : plan->graph->sweep[0].run_ptr.size()) - 1;
   std::vector<unsigned long long> t(4 * (R + 1) + 8);
   if (hipMemcpy(t.data(), plan->d_timeline.p, sizeof(unsigned long long) * (4 * R + 4), hipMemcpyDeviceToHost) == hipSuccess) {
     if (spec)
       for (int d = 0; d < 2; ++d) {
-        const auto &sp = plan->graph->sweep[d].spec;
+        const auto &sp = own_spec(plan, d);
         const unsigned long long t0 = t[(2 * R + d) * 2];
         std::fprintf(stderr, "[stereo_hip timeline] dir %d speculative: runner %.0f us; segments (us since the runner started, start..commit): ", d,
                      (t[(2 * R + d) * 2 + 1] - t0) / 100.0);
@@ -67,6 +73,25 @@ void print_timeline(const stereo_trws_plan *plan) {
                        ((double)t[((size_t)d * R + sp.run + q) * 2 + 1] - (double)t0) / 100.0);
         std::fprintf(stderr, "last[..%.0f]\n", ((double)t[((size_t)d * R + sp.run + sp.nseg - 1) * 2 + 1] - (double)t0) / 100.0);
       }
+    // sub-row runs: the whole rows once more (runs of the chain schedule, its numbers) -- first start .. last end of a row's pieces
+    for (int d = 0; d < 2; ++d) {
+      if (!own_sub_rows(plan, d)) continue;
+      const TrwsGraph::Sweep &S = plan->graph->sweep[d];
+      const std::vector<int32_t> &rp = spec ? S.chunked.spec.run_ptr : S.chunked.run_ptr;
+      const size_t RW = S.chain_run_ptr.size() - 1, step = (RW + (spec ? S.spec.nseg - 1 : 0)) / 12 + 1;
+      const unsigned long long t0 = t[(size_t)d * R * 2];
+      std::fprintf(stderr, "[stereo_hip timeline] dir %d whole rows (us since run 0 start): ", d);
+      for (size_t k = 8; k < RW; k += step) {
+        double lo = 1e300, hi = -1e300;
+        for (size_t j = 0; j + 1 < rp.size(); ++j)
+          if (rp[j] >= S.chain_run_ptr[k] && rp[j] < S.chain_run_ptr[k + 1]) {
+            lo = std::min(lo, ((double)t[(d * R + j) * 2] - (double)t0) / 100.0);
+            hi = std::max(hi, ((double)t[(d * R + j) * 2 + 1] - (double)t0) / 100.0);
+          }
+        std::fprintf(stderr, "row%zu[%.0f..%.0f] ", k, lo, hi);
+      }
+      std::fprintf(stderr, "\n");
+    }
     for (int d = 0; d < 2; ++d) {
       const unsigned long long t0 = t[(size_t)d * R * 2];
       std::fprintf(stderr, "[stereo_hip timeline] dir %d (us since run 0 start): ", d);
@@ -185,6 +210,21 @@ int stereo_trws_plan_counters(stereo_trws_plan *P, int64_t *serial_messages, int
   DeviceScope device_scope_(P ? P->device : -1);
   if (!P) return 1;
   unsigned long long v = 0;
+  if (P->bwd_pending) {
+    // a backward sweep no iteration has taken yet (trws_plan.h) does not show: the count from before it; a reset leaves
+    // the device with what that sweep adds
+    v = P->h_held.p[0];
+    if (reset) {
+      unsigned long long now = 0;
+      if (hipStreamSynchronize(P->issue_stream) != hipSuccess) return 1;
+      if (hipMemcpy(&now, P->d_fallbacks.p, sizeof(now), hipMemcpyDeviceToHost) != hipSuccess) return 1;
+      now -= v;
+      if (hipMemcpy(P->d_fallbacks.p, &now, sizeof(now), hipMemcpyHostToDevice) != hipSuccess) return 1;
+      P->h_held.p[0] = 0;
+    }
+    if (serial_messages) *serial_messages = (int64_t)v;
+    return 0;
+  }
   if (hipMemcpy(&v, P->d_fallbacks.p, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return 1;
   if (serial_messages) *serial_messages = (int64_t)v;
   if (reset && hipMemset(P->d_fallbacks.p, 0, sizeof(v)) != hipSuccess) return 1;
@@ -198,6 +238,7 @@ int stereo_trws_plan_spec_stats(stereo_trws_plan *P, int64_t out[4]) {
   if (P->d_spec_stat.p) {
     unsigned long long v[32] = {0};
     if (hipMemcpy(v, P->d_spec_stat.p, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return 1;
+    if (P->bwd_pending) std::memcpy(v, P->h_held.p + 1, sizeof(v));   // (as they read before the sweep no iteration has taken yet)
     if (std::getenv("STEREO_HIP_TRWS_TIMELINE"))
       std::fprintf(stderr, "[stereo_hip spec] last sweeps, roles done after (us): forward messages %.0f labels %.0f last loader %.0f publisher %.0f | backward messages %.0f "
                            "last loader %.0f publisher %.0f\n", v[8] / 100.0, v[9] / 100.0, v[10] / 100.0, v[11] / 100.0, v[12] / 100.0, v[14] / 100.0, v[15] / 100.0);

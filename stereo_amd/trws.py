@@ -337,6 +337,34 @@ def schedule(N, connectivity0, direction, max_resident_runs=0):
                 dep_ptr=dep_ptr, dep_rank=dep_rank[:dep_ptr[N]])
 
 
+def schedule_chunked(N, connectivity0, direction, row_chunk, resident, max_resident_runs=0):
+    """Host-only inspection of the sub-row runs (stereo_trws_schedule_chunked): schedule()'s dict for runs of at most
+    `row_chunk` positions under `resident` resident workgroups, plus desc ((N, 64) int32, schedule order), chunked
+    (False: the direction keeps whole rows and everything is the chain schedule's), spec_ok and spec_run (the run the
+    speculative schedule cuts, which stays whole; -1 without one)."""
+    c = np.asarray(connectivity0)
+    if c.ndim != 2 or c.shape[0] != 2:
+        raise StereoHipError("connectivity must be 2 x E")
+    c = np.asfortranarray(c, dtype=np.uint32)
+    E = c.shape[1]
+    i64 = lambda n: np.zeros(n, np.int64)
+    rank_at, run_ptr, ticket_run, pred, dep_ptr, dep_rank = i64(N), i64(N + 1), i64(N), i64(N), i64(N + 1), i64(4 * N)
+    info = i64(4)
+    desc = np.zeros((N, 64), np.int32)
+    nruns = C.c_int64(0)
+    err = _lib.errbuf()
+    P = lambda a: _ptr(a, C.c_int64)
+    rc = _lib.lib().stereo_trws_schedule_chunked(C.c_int64(N), C.c_int64(E), _ptr(c, C.c_uint32), C.c_int64(max_resident_runs),
+                                                 C.c_int(direction), C.c_int64(int(row_chunk)), C.c_int64(int(resident)), P(info),
+                                                 P(rank_at), P(run_ptr), C.byref(nruns), P(ticket_run), P(pred), P(dep_ptr),
+                                                 P(dep_rank), _ptr(desc, C.c_int32), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    R = nruns.value
+    return dict(rank_at=rank_at, run_ptr=run_ptr[:R + 1], ticket_run=ticket_run[:R], pred_rank=pred,
+                dep_ptr=dep_ptr, dep_rank=dep_rank[:dep_ptr[N]], desc=desc, chunked=bool(info[0]), chunk=int(info[1]),
+                spec_ok=bool(info[2]), spec_run=int(info[3]))
+
+
 def simulate_schedule(sched, workgroups, visit=1.0, handover=0.0):
     """Discrete simulation of the dataflow sweep on `workgroups` resident workgroups that take
     run tickets in order: a visit costs `visit`, a message from another run arrives `handover`
