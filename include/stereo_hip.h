@@ -28,8 +28,9 @@ extern "C" {
  * stereo_fusion_fuse_until_convergence.  5: stereo_segpln_wta, stereo_segpln_planes.  6: stereo_segment_* (the segmenters
  * behind dispmap_globalstereo), stereo_trws_plan_debug_terms / _messages, stereo_segpln_planes_batch.  7: TRW-S takes
  * up to 4096 labels with one shared strictly ascending positions vector (stereo_trws_plan_path 5).  8: stereo_trws_batch_*
- * (independent plans that share one launch per sweep). */
-#define STEREO_HIP_ABI_VERSION 9
+ * (independent plans that share one launch per sweep).  10: stereo_trws_plans_state_* (solver state: save / load),
+ * stereo_trws_state_check, stereo_trws_strip_state_rows_host. */
+#define STEREO_HIP_ABI_VERSION 10
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -144,7 +145,9 @@ int stereo_trws_plan_bind_device(stereo_trws_plan *plan, const double *d_unary,
                                  double tol, char *err, size_t errcap);
 /* Both calls start a NEW minimisation: if the plan has iterated before, they imply
  * stereo_trws_plan_reset (an iterate call runs the forward sweep of the following iteration ahead
- * of time, so messages computed from the old inputs cannot be continued with new ones). */
+ * of time, so messages computed from the old inputs cannot be continued with new ones).  To go on
+ * from messages that exist -- a saved run, a warm start with other unaries -- upload or bind first,
+ * then load a solver state (stereo_trws_plans_state_load below). */
 
 /* Zero all messages (MRFEnergy.cpp:115-133) and the iteration counter. */
 int stereo_trws_plan_reset(stereo_trws_plan *plan, char *err, size_t errcap);
@@ -387,6 +390,75 @@ int stereo_trws_strip_belief_lists_host(int64_t N, int64_t E, const uint32_t *co
                                         int nstrips, int strip, int64_t *n_own, int64_t *n_fwd, int64_t *n_bwd,
                                         int32_t *own, int32_t *fptr, int32_t *fidx, int32_t *bptr, int32_t *bidx,
                                         char *err, size_t errcap);
+/* ---- solver state: save and restore; resume, re-shard, warm start ---------------- *
+ * No reference counterpart (MRFEnergy keeps its messages inside the object).  A state is what a minimisation has
+ * computed, in the CALLER's layout, so that it can leave the plan that ran it and enter another one -- a fresh plan in
+ * another process, row strips instead of one plan or back, another kernel family, a batch member: this header, the
+ * messages (E x K doubles: MATLAB's K x E, label fastest, the caller's edge order) and the labels (N int32, zero based,
+ * node-id order: what stereo_trws_plan_result reports minus one).  Inputs (unary, q, qprim, positions, alphas, tol),
+ * sweep statistics, counters and node beliefs are not part of it.
+ *   phase 0  the messages stand as after a backward sweep.  What a fresh or reset plan saves (zero messages,
+ *            iterations 0), and the door for foreign messages.
+ *   phase 1  the forward sweep of iteration `iterations` + 1 has run: where every iterate call leaves a plan.
+ *   phase 2  the backward sweep of that iteration has run as well and no iteration has taken it (an iterate call that
+ *            stopped on max_relgap before its last iteration); its bound, summed in the single plan's order, is
+ *            lower_bound_next.  Single plans only.
+ * Every kernel family, strips and batches promise identical results, so a run that goes on from a loaded state equals
+ * the uninterrupted run bit for bit (strips: labels and messages; their energy and bound are sums of partial sums as
+ * always).  Exact and min-plus message modes may differ between save and load: no bit promise across them. */
+#define STEREO_TRWS_STATE_MAGIC 0x53575254u /* "TRWS" */
+#define STEREO_TRWS_STATE_VERSION 1
+typedef struct stereo_trws_state_header {
+  uint32_t magic, version;
+  int32_t kernel, K;
+  int64_t N, E;
+  int32_t message_mode;       /* as given to stereo_trws_plan_create, STEREO_TRWS_ORDER_INDEX included */
+  int32_t phase;              /* 0, 1, 2 */
+  uint64_t connectivity_key;  /* FNV-1a (64 bit) over the 2 x E uint32 words of the connectivity */
+  int64_t iterations;
+  double energy, lower_bound, lower_bound_next;
+} stereo_trws_state_header;
+/* n == 1 and a plan of the whole problem: that plan.  Otherwise plans[0 .. n) are ALL the strips of one problem, each
+ * once, in one state (same iteration count, nothing issued and uncollected).
+ * save waits for the plans' streams, reads, and leaves every plan exactly as it was (a pending sweep and the counters
+ * held for it included).  messages / labels: host arrays, E x K doubles and N int32.  From strips every edge row is
+ * taken from the one strip whose copy is valid (stereo_trws_strip_state_rows_host), every label from its owner. */
+int stereo_trws_plans_state_save(stereo_trws_plan *const *plans, int n, stereo_trws_state_header *header,
+                                 double *messages, int32_t *labels, char *err, size_t errcap);
+/* load = stereo_trws_plan_reset (a pending sweep is discarded as there), then messages, labels, iteration count,
+ * energy and bound are the state's and the plan continues as the saved one would have: stereo_trws_plan_result returns
+ * what it returned there, the first launch of the next iterate is the backward sweep (phase 1) or the fused launch
+ * (phase 2).  The plans need their inputs first ("upload or bind first, then load": an upload wipes the state).
+ * Refused, naming the field: another magic, version, kernel, K, N, E or connectivity, a differing
+ * STEREO_TRWS_ORDER_INDEX bit, phase 2 into strips.  Node beliefs (stereo_trws_plan_keep_min_marginals) cannot be
+ * rebuilt from a state: they are readable again after one iteration.  Every strip takes every row it stores. */
+int stereo_trws_plans_state_load(stereo_trws_plan *const *plans, int n, const stereo_trws_state_header *header,
+                                 const double *messages, const int32_t *labels, char *err, size_t errcap);
+/* The same with DEVICE arrays of the caller (e.g. torch tensors) on the plans' device; the header stays on the host.
+ * save: the copies / the gather are enqueued on `stream` (hipStream_t, NULL = default) behind the plans' own work and
+ * not waited for.  load: the plans' state is reset first (synchronously), the copies / the scatter run on `stream`,
+ * and the call returns when they are done. */
+int stereo_trws_plans_state_save_device(stereo_trws_plan *const *plans, int n, stereo_trws_state_header *header,
+                                        double *d_messages, int32_t *d_labels, void *stream, char *err, size_t errcap);
+int stereo_trws_plans_state_load_device(stereo_trws_plan *const *plans, int n, const stereo_trws_state_header *header,
+                                        const double *d_messages, const int32_t *d_labels, void *stream, char *err,
+                                        size_t errcap);
+/* One plan of a whole problem: the group entries with n == 1. */
+int stereo_trws_plan_state_save(stereo_trws_plan *plan, stereo_trws_state_header *header, double *messages,
+                                int32_t *labels, char *err, size_t errcap);
+int stereo_trws_plan_state_load(stereo_trws_plan *plan, const stereo_trws_state_header *header, const double *messages,
+                                const int32_t *labels, char *err, size_t errcap);
+/* Host only (no device).  The refusal rule of load: 0 if a plan created with (kernel, K, N, E, conn, message_mode)
+ * takes the state, else nonzero with the reason -- which names the field -- in why. */
+int stereo_trws_state_check(const stereo_trws_state_header *header, int kernel, int K, int64_t N, int64_t E,
+                            const uint32_t *conn, int message_mode, char *why, size_t cap);
+/* Host only: take[e] = 1 for the global edge rows strip `strip` is authoritative for in `phase` (0 or 1).  A strip
+ * stores a row for every edge with an own endpoint, but a visit writes a cross-strip message only into the copy of
+ * the strip that owns the RECEIVING end: at rest in phase 1 the valid copy of an edge is with the owner of its endpoint
+ * later in the node order, in phase 0 with the owner of the earlier one.  Over the strips every edge is taken once.
+ * Nonzero on a bad argument (the reason: stereo_hip_last_error). */
+int stereo_trws_strip_state_rows_host(int64_t N, int64_t E, const uint32_t *conn, const int32_t *owner, int nstrips,
+                                      int strip, int phase, uint8_t *take);
 /* Diagnostics (any output may be NULL). */
 int stereo_trws_plan_strip_info(stereo_trws_plan *plan, int *nstrips, int *strip, int64_t *own_nodes,
                                 int64_t *runs_forward, int64_t *runs_backward, int *needs_previous,

@@ -3,6 +3,7 @@
 
 #include "../../include/stereo_hip.h"
 #include "common.h"
+#include "trws_state.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1215,5 +1216,31 @@ extern "C" int stereo_trws_strip_belief_lists_host(int64_t N, int64_t E, const u
     return 0;
   } catch (const std::exception &e) {
     return stereo::fail(std::string("stereo_trws_strip_belief_lists_host: ") + e.what(), err, errcap);
+  }
+}
+
+// Host-only views of the solver state's rules (trws_state.h): what a load refuses, and the edge rows a
+// strip is authoritative for.
+extern "C" int stereo_trws_state_check(const stereo_trws_state_header *header, int kernel, int K, int64_t N, int64_t E,
+                                       const uint32_t *conn, int message_mode, char *why, size_t cap) {
+  if (!header || (!conn && E > 0) || E < 0) return stereo::fail("stereo_trws_state_check: bad argument", why, cap);
+  const std::string r = stereo::trws_state_refusal(*header, kernel, K, N, E, stereo::trws_connectivity_key(conn, E), message_mode);
+  if (!r.empty()) return stereo::fail("stereo_trws_state_check: " + r, why, cap);
+  if (why && cap) why[0] = 0;
+  return 0;
+}
+
+extern "C" int stereo_trws_strip_state_rows_host(int64_t N, int64_t E, const uint32_t *conn, const int32_t *owner, int nstrips,
+                                                 int strip, int phase, uint8_t *take) {
+  if (!conn || !owner || !take || nstrips < 2 || strip < 0 || strip >= nstrips || (phase != 0 && phase != 1))
+    return stereo::fail("stereo_trws_strip_state_rows_host: bad argument (strips have phases 0 and 1)", nullptr, 0);
+  try {
+    stereo::TrwsGraph g;
+    std::string gerr;
+    if (!stereo::build_trws_graph(N, E, conn, g, gerr, 0, owner, nstrips)) return stereo::fail(gerr, nullptr, 0);
+    stereo::strip_state_rows(g, strip, phase, take);
+    return 0;
+  } catch (const std::exception &e) {
+    return stereo::fail(std::string("stereo_trws_strip_state_rows_host: ") + e.what(), nullptr, 0);
   }
 }

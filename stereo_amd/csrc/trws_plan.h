@@ -16,6 +16,7 @@
 #include "trws_graph.h"
 #include "trws_dev.h"
 #include "trws_launch.h"
+#include "trws_state.h"
 
 namespace stereo {
 
@@ -53,6 +54,10 @@ inline std::string trws_env_key() {
 struct stereo_trws_plan {
   int kernel = 1, K = 0, Kp = 0, mode = 0, device = 0;
   int64_t N = 0, E = 0;
+  // what a solver state is checked against (trws_state.h): the key of the connectivity given at creation, and
+  // STEREO_TRWS_ORDER_INDEX if the plan was created with it (mode has the message mode alone)
+  uint64_t conn_key = 0;
+  int order_flag = 0;
   std::shared_ptr<const stereo::TrwsGraph> graph;  // host-side analysis; shared with the cache of the last connectivity
   // device copies of the graph
   stereo::DevBuf<int32_t> d_tail, d_order, d_fptr, d_fidx, d_bptr, d_bidx, d_lbn, d_lbe, d_x;
@@ -160,6 +165,16 @@ struct stereo_trws_plan {
   stereo::DevBuf<stereo::BeliefBlock> d_bel_table;
   stereo::BeliefBlock bel_sent[2][stereo::kMaxGroup];
   int bel_sent_n[2] = {0, 0};
+  // solver state.  state_loaded_at: the iteration count a loaded state came with, -1: none since the
+  // last reset (a strip whose count still equals it has no terms of its own to sum energy and bound from).  Allocated
+  // by the first save / load of a strip group on one device: the strip's authoritative rows by local edge id per
+  // phase, and -- with the first plan of a group -- the block tables of the grouped gather [0] and scatter [kMaxGroup]
+  // launches with what was sent last
+  int64_t state_loaded_at = -1;
+  stereo::DevBuf<uint8_t> d_state_take[2];
+  stereo::DevBuf<stereo::StateBlock> d_state_table;
+  stereo::StateBlock state_sent[2][stereo::kMaxGroup];
+  int state_sent_n[2] = {0, 0};
   ~stereo_trws_plan() {
     for (int w = 0; w < 2; ++w)
       for (int k = 0; k < 3; ++k)
@@ -203,6 +218,11 @@ bool own_sub_rows(const stereo_trws_plan *P, int d);
 const TrwsGraph::Sweep::Spec &own_spec(const stereo_trws_plan *P, int d);
 size_t persistent_lds_bytes(bool large, int Kp);   // dynamic LDS of the generic / the large family's sweep kernel
 constexpr int kHeldWords = 33;                     // stereo_trws_plan::h_held
+// the state of a minimisation: zero messages, labels, flags, counters of iterations (a pending sweep is discarded first)
+void reset_state(stereo_trws_plan *P);
+void discard_backward_ahead(stereo_trws_plan *P);
+// the buffers and events of a backward sweep launched ahead, on first use (issue_backward_ahead; a loaded phase-2 state)
+void ensure_ahead_buffers(stereo_trws_plan *P);
 
 // trws_inputs.hip: what an upload or bind leaves to do on the device and on the positions
 void run_argsort(const double *vals, uint16_t *perm, int K, int64_t count, hipStream_t s);

@@ -32,6 +32,7 @@
 //   trws_plan.hip        this file: inputs, iterations, results, strip wiring, min-marginals
 //   trws_inputs.hip      sort permutations of the positions, analysis of a shared positions vector
 //   trws_plan_debug.hip  timeline / profiler printouts, development aids, stereo_trws_messages
+//   trws_state.h/.hip    solver state: save / load, its refusal rule, the strips' gather and scatter
 //   trws_gateway.hip     what trws_mex reaches: stereo_trws, its plan cache, row strips behind it
 #include <algorithm>
 #include <cstring>
@@ -347,15 +348,7 @@ void issue_iteration(stereo_trws_plan *const *plans, int n, hipStream_t s, bool 
 // backward sweep writes -- go to the host on the copy stream, so that the sweep starts right behind the fused launch.
 // A single plan's own launches only, behind issue_iteration(.., ahead = true).
 void issue_backward_ahead(stereo_trws_plan *P, const DevParams &p, hipStream_t s) {
-  if (!P->h_lb_next.p) {
-    P->h_lb_next.alloc(P->n_lb); P->h_held.alloc(kHeldWords);
-    std::memset(P->h_held.p, 0, sizeof(unsigned long long) * kHeldWords);
-    STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_lb_next, hipEventDisableTiming));
-    STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_end, hipEventDisableTiming));
-    STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_fwd, hipEventDisableTiming));
-    STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_ahead, hipEventDisableTiming));
-    STEREO_HIP_CHECK(hipEventCreate(&P->ev0_next));
-  }
+  ensure_ahead_buffers(P);
   STEREO_HIP_CHECK(hipMemcpyAsync(P->h_held.p, P->d_fallbacks.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   if (P->d_spec_stat.p)
     STEREO_HIP_CHECK(hipMemcpyAsync(P->h_held.p + 1, P->d_spec_stat.p, sizeof(unsigned long long) * 32, hipMemcpyDeviceToHost, s));
@@ -375,6 +368,19 @@ void issue_backward_ahead(stereo_trws_plan *P, const DevParams &p, hipStream_t s
   STEREO_HIP_CHECK(hipMemcpyAsync(P->h_lb_next.p, P->d_lbterms.p, sizeof(double) * P->n_lb, hipMemcpyDeviceToHost, P->copy_stream));
   STEREO_HIP_CHECK(hipEventRecord(P->ev_lb_next, P->copy_stream));
   P->bwd_pending = true;
+}
+
+}  // namespace
+
+void ensure_ahead_buffers(stereo_trws_plan *P) {
+  if (P->h_lb_next.p) return;
+  P->h_lb_next.alloc(P->n_lb); P->h_held.alloc(kHeldWords);
+  std::memset(P->h_held.p, 0, sizeof(unsigned long long) * kHeldWords);
+  STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_lb_next, hipEventDisableTiming));
+  STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_end, hipEventDisableTiming));
+  STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_fwd, hipEventDisableTiming));
+  STEREO_HIP_CHECK(hipEventCreateWithFlags(&P->ev_ahead, hipEventDisableTiming));
+  STEREO_HIP_CHECK(hipEventCreate(&P->ev0_next));
 }
 
 // A pending backward sweep that no iteration will take (new inputs, a reset): wait for it and give the counters back
@@ -400,8 +406,10 @@ void reset_state(stereo_trws_plan *P) {
   STEREO_HIP_CHECK(hipMemset(P->d_ctl.p, 0, sizeof(int32_t) * kCtlWords));
   STEREO_HIP_CHECK(hipDeviceSynchronize());
   P->iterations = 0; P->energy = 0; P->lb = 0; P->epoch = 0; P->fwd_pending = false;
-  P->lb_in_flight = false; P->issued = false; P->mm_ready = false;
+  P->lb_in_flight = false; P->issued = false; P->mm_ready = false; P->state_loaded_at = -1;
 }
+
+namespace {
 
 void finish_inputs(stereo_trws_plan *P) {
   // New inputs start a new minimisation: the forward sweep of the next iteration has usually run
@@ -422,6 +430,7 @@ void finish_inputs(stereo_trws_plan *P) {
   sort_positions(P);
   P->family = family;
   P->uniform_step = 0; P->pos_ascending = false; P->window = 0; P->spec_window = false;
+  P->pos_first = P->pos_last = P->pos_gap = 0;   // (of the positions before: a plan keeps its state across uploads now)
   const bool windowed = asc && P->lambda >= 0;
   if (windowed || family == TrwsFamily::Large) {
     P->pos_first = hp[0]; P->pos_last = hp[P->K - 1];

@@ -79,6 +79,8 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
     std::unique_ptr<stereo_trws_plan> P(new stereo_trws_plan);
     P->kernel = kernel; P->K = K; P->Kp = (K + 1) & ~1; P->mode = message_mode; P->N = N; P->E = E;
     P->nstrips = nstrips; P->strip = strip;
+    P->order_flag = ordering ? STEREO_TRWS_ORDER_INDEX : 0;
+    P->conn_key = conn ? trws_connectivity_key(conn, E) : share ? share->conn_key : 0;
     std::string gerr;
     // Workgroups that stay resident: runs beyond that are cut / dispensed by dependency level.  The
     // bound comes from the device in use (a partitioned or masked MI355X exposes fewer CUs): one

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import StereoHipError
-from .trws import _ptr, MESSAGES_EXACT
+from .trws import _ptr, MESSAGES_EXACT, _save_state, _load_state, _save_state_device, _load_state_device
 
 IPC_BYTES = 256  # STEREO_TRWS_IPC_BYTES
 
@@ -328,11 +328,52 @@ class TrwsStrips:
                                                                      vp(d_confidence), vp(d_argmin), vp(stream), err,
                                                                      C.c_size_t(len(err))), err)
 
+    def _handles(self):
+        return (C.c_void_p * self.nstrips)(*[p._h for p in self.plans])
+
+    def save_state(self):
+        """The solver state of the whole problem as a TrwsState: every edge row from the strip whose
+        copy is valid, every label from its owner.  What a single plan saves at the same iteration, messages and
+        labels bit for bit.  The strips are left as they were."""
+        return _save_state(self._handles(), self.nstrips, self.N, self.E, self.K)
+
+    def load_state(self, state):
+        """Continue from `state` (saved by a single plan or by any number of strips; phases 0 and 1) with the strips'
+        current inputs: upload or bind first, then load."""
+        _load_state(self._handles(), self.nstrips, state, self.N, self.E, self.K)
+        self.energy, self.lb, self.iterations = state.energy, state.lower_bound, int(state.iterations)
+
+    def save_state_device(self, d_messages, d_labels, stream=None):
+        """save_state into device memory of the caller ((E, K) float64, (N,) int32) in one gather launch on `stream`;
+        strips that share the device only.  Returns a TrwsState that holds the header alone."""
+        if self._devices:
+            raise StereoHipError("save_state_device: the strips are on devices of their own; use save_state()")
+        return _save_state_device(self._handles(), self.nstrips, d_messages, d_labels, stream)
+
+    def load_state_device(self, state, d_messages, d_labels, stream=None):
+        """load_state from device memory of the caller in one scatter launch on `stream`, waited for."""
+        if self._devices:
+            raise StereoHipError("load_state_device: the strips are on devices of their own; use load_state()")
+        _load_state_device(self._handles(), self.nstrips, state, d_messages, d_labels, stream)
+        self.energy, self.lb, self.iterations = state.energy, state.lower_bound, int(state.iterations)
+
     def path(self):
         return self.plans[0].path()
 
     def serial_messages(self, reset=False):
         return sum(p.serial_messages(reset) for p in self.plans)
+
+
+def strip_state_rows_host(N, connectivity0, owner, nstrips, strip, phase):
+    """Host-only: the global edge rows strip `strip` is authoritative for in `phase` (0 or 1) as a bool array
+    (stereo_trws_strip_state_rows_host)."""
+    c = _conn_f(connectivity0)
+    owner = np.ascontiguousarray(owner, dtype=np.int32)
+    take = np.zeros(c.shape[1], np.uint8)
+    rc = _lib.lib().stereo_trws_strip_state_rows_host(C.c_int64(N), C.c_int64(c.shape[1]), _ptr(c, C.c_uint32), _ptr(owner, C.c_int32),
+                                                      C.c_int(nstrips), C.c_int(strip), C.c_int(phase), _ptr(take, C.c_uint8))
+    _lib.check(rc, None)
+    return take.astype(bool)
 
 
 def make_strips(kernel, K, H, W, connectivity0, nstrips, **kw):

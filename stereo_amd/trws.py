@@ -82,6 +82,109 @@ def trws(kernel, unary, connectivity, q, qprim, alphas, tol, options=None, min_m
     return lab, en.value, lb.value, it.value, mm, conf
 
 
+class StateHeader(C.Structure):
+    """stereo_trws_state_header (include/stereo_hip.h)."""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("kernel", C.c_int32), ("K", C.c_int32),
+                ("N", C.c_int64), ("E", C.c_int64), ("message_mode", C.c_int32), ("phase", C.c_int32),
+                ("connectivity_key", C.c_uint64), ("iterations", C.c_int64), ("energy", C.c_double),
+                ("lower_bound", C.c_double), ("lower_bound_next", C.c_double)]
+
+
+class TrwsState:
+    """A solver state: the header's fields as attributes, ``messages`` (E, K) float64 C-contiguous
+    (MATLAB's K x E in the caller's edge order) and ``labels`` (N,) int32, zero based.  Inputs are not part of it.
+    Saved by ``TrwsPlan.save_state`` / ``TrwsStrips.save_state``, taken by their ``load_state``."""
+
+    FIELDS = tuple(name for name, _ in StateHeader._fields_)
+
+    def __init__(self, header, messages, labels):
+        for name in self.FIELDS:
+            setattr(self, name, getattr(header, name))
+        self.messages, self.labels = messages, labels
+
+    def header(self):
+        h = StateHeader()
+        for name in self.FIELDS:
+            setattr(h, name, getattr(self, name))
+        return h
+
+    def to_file(self, path):
+        """np.savez: data only (header fields as scalars, the two arrays)."""
+        with open(path, "wb") as f:
+            np.savez(f, messages=self.messages, labels=self.labels,
+                     **{name: np.asarray(getattr(self, name), dtype=np.dtype(ctype)) for name, ctype in StateHeader._fields_})
+
+    @classmethod
+    def from_file(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            h = StateHeader()
+            for name in cls.FIELDS:
+                setattr(h, name, z[name].item())
+            return cls(h, np.ascontiguousarray(z["messages"], dtype=np.float64), np.ascontiguousarray(z["labels"], dtype=np.int32))
+
+
+def state_check(state, kernel, K, N, connectivity0, message_mode=MESSAGES_EXACT):
+    """Host only (stereo_trws_state_check): raises StereoHipError naming the field if a plan created with these
+    arguments would refuse the state (a TrwsState or a StateHeader)."""
+    c = np.asarray(connectivity0)
+    if c.ndim != 2 or c.shape[0] != 2:
+        raise StereoHipError("connectivity must be 2 x E")
+    c = np.asfortranarray(c, dtype=np.uint32)
+    h = state.header() if isinstance(state, TrwsState) else state
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_trws_state_check(C.byref(h), C.c_int(int(kernel)), C.c_int(int(K)), C.c_int64(int(N)),
+                                            C.c_int64(c.shape[1]), _ptr(c, C.c_uint32), C.c_int(int(message_mode)), err,
+                                            C.c_size_t(len(err)))
+    _lib.check(rc, err)
+
+
+def _save_state(handles, n, N, E, K):
+    """stereo_trws_plans_state_save into fresh host arrays."""
+    h = StateHeader()
+    m = np.zeros((E, K))
+    x = np.zeros(N, np.int32)
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_trws_plans_state_save(handles, C.c_int(n), C.byref(h), _ptr(m), _ptr(x, C.c_int32), err,
+                                                 C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return TrwsState(h, m, x)
+
+
+def _load_state(handles, n, state, N, E, K):
+    """stereo_trws_plans_state_load for plans of N nodes, E edges, K labels.  The library checks the header before it
+    reads the arrays; arrays that do not have the plans' sizes are never handed to it."""
+    m = np.ascontiguousarray(state.messages, dtype=np.float64)
+    x = np.ascontiguousarray(state.labels, dtype=np.int32)
+    h = state.header()
+    fits = m.shape == (E, K) and x.shape == (N,)
+    if not fits and (h.E, h.K, h.N) == (E, K, N):
+        raise StereoHipError("TrwsState: messages must be (E, K) = (%d, %d) and labels (N,) = (%d,)" % (E, K, N))
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_trws_plans_state_load(handles, C.c_int(n), C.byref(h), _ptr(m) if fits else None,
+                                                 _ptr(x, C.c_int32) if fits else None, err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+
+
+def _save_state_device(handles, n, d_messages, d_labels, stream):
+    """stereo_trws_plans_state_save_device: the arrays stay on the device, a TrwsState without them comes back."""
+    h = StateHeader()
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_trws_plans_state_save_device(handles, C.c_int(n), C.byref(h), C.c_void_p(int(d_messages)),
+                                                        C.c_void_p(int(d_labels)), C.c_void_p(int(stream)) if stream else None,
+                                                        err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return TrwsState(h, None, None)
+
+
+def _load_state_device(handles, n, state, d_messages, d_labels, stream):
+    h = state.header() if isinstance(state, TrwsState) else state
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_trws_plans_state_load_device(handles, C.c_int(n), C.byref(h), C.c_void_p(int(d_messages)),
+                                                        C.c_void_p(int(d_labels)), C.c_void_p(int(stream)) if stream else None,
+                                                        err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+
+
 class TrwsPlan:
     """Device-resident TRW-S solver for one connectivity (stereo_trws_plan_*)."""
 
@@ -198,6 +301,24 @@ class TrwsPlan:
                                                               vp(d_argmin), vp(stream), err,
                                                               C.c_size_t(len(err)))
         _lib.check(rc, err)
+
+    def save_state(self):
+        """The plan's solver state as a TrwsState on the host; the plan is left exactly as it was."""
+        return _save_state((C.c_void_p * 1)(self._h), 1, self.N, self.E, self.K)
+
+    def load_state(self, state):
+        """Continue from `state` with the plan's current inputs: upload or bind first, then load.  Implies reset()."""
+        _load_state((C.c_void_p * 1)(self._h), 1, state, self.N, self.E, self.K)
+
+    def save_state_device(self, d_messages, d_labels, stream=None):
+        """Same into device memory of the caller (ints, e.g. tensor.data_ptr()): (E, K) float64 and (N,) int32, copied on
+        `stream` without waiting for it.  Returns a TrwsState that holds the header alone."""
+        return _save_state_device((C.c_void_p * 1)(self._h), 1, d_messages, d_labels, stream)
+
+    def load_state_device(self, state, d_messages, d_labels, stream=None):
+        """load_state from device memory of the caller, complete on `stream` (the copies run there and are waited
+        for); `state` gives the header."""
+        _load_state_device((C.c_void_p * 1)(self._h), 1, state, d_messages, d_labels, stream)
 
     def info(self):
         rank = np.zeros(self.N, np.int64)
