@@ -194,7 +194,10 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
           const int nout = f & 15, md = (f >> 16) & 255;
           const int myrow = sti[72 + (lane & 7)];  // LDS offsets (doubles) of the node's message rows, from the loader
           const unsigned twins = SHARED ? (unsigned)__builtin_amdgcn_readfirstlane(sti[kDescTwin]) : 0x76543210u;
-          const int gpub = p.gran ? (__builtin_amdgcn_readfirstlane(sti[kDescGran]) >> 8) & 255 : 0;   // messages published as granules
+          // lanes 0-7: the edge ids of the node's messages, lane 8: the granule word -- one LDS read in flight with the
+          // ones above, so that publishing behind the message waits for no LDS round trip (it used to wait for three)
+          const int gword = sti[lane == 8 ? kDescGran : 4 + (lane & 7)];
+          const int gpub = p.gran ? (RLI(gword, 8) >> 8) & 255 : 0;   // messages published as granules
           VSTAMP(0);
           if (wave < nout || (BACKWARD && wave == 0)) {  // waves without a message stay out of the way
           double Di = act ? st[kStD + lane] : 0.0;
@@ -269,11 +272,11 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
                 // (lanes < K only: the granules of a lane beyond K are nobody's)
                 const int gmine = gpub & ((1 << j) | (cp.active() ? 1 << partner : 0));
                 if (gmine) {
-                  granule_delay(p, __builtin_amdgcn_readfirstlane(sti[0]));
+                  if (p.debug & 262144) granule_delay(p, __builtin_amdgcn_readfirstlane(sti[0]));   // (the node's number is read only when asked for: an LDS round trip)
                   if ((gmine >> j) & 1)
-                    if (act) publish_granules(p.gran + 2 * ((size_t)(unsigned)__builtin_amdgcn_readfirstlane(sti[4 + j]) * (unsigned)Kv + lane), newm, epoch);
+                    if (act) publish_granules(p.gran + 2 * ((size_t)(unsigned)RLI(gword, j) * (unsigned)Kv + lane), newm, epoch);
                   if ((gmine >> partner) & 1 && partner != j)
-                    if (act) publish_granules(p.gran + 2 * ((size_t)(unsigned)__builtin_amdgcn_readfirstlane(sti[4 + partner]) * (unsigned)Kv + lane), newm, epoch);
+                    if (act) publish_granules(p.gran + 2 * ((size_t)(unsigned)RLI(gword, partner) * (unsigned)Kv + lane), newm, epoch);
                 }
               }
             }
