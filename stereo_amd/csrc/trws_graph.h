@@ -63,7 +63,7 @@ struct TrwsGraph {
     // slot of that edge in the predecessor's outgoing list, or -1
     std::vector<int8_t> in_slot;
     // Packed per-position descriptors for the fast kernels (kDescWords int32 each,
-    // layout in trws.hip: NodeDesc); empty unless fast_ok.  They are laid out in the order of
+    // layout below: kDescNode ...); empty unless fast_ok.  They are laid out in the order of
     // the CHAIN schedule below, which is what the descriptor-driven kernels walk.
     std::vector<int32_t> desc;
     // Chain schedule of the fast kernels: a run is a path of the dependency DAG (every node
@@ -100,8 +100,8 @@ struct TrwsGraph {
     // consecutive runs of at most that many, so that a workgroup is held for a piece of a grid row and not for the
     // whole of it.  Same positions (chain_rank), other runs, tickets and descriptors: a piece's first node waits for the
     // last node of the piece in front like for any other foreign node.  The speculative schedule's cut run stays whole;
-    // `spec` is that schedule over these runs.  Built on request for one direction at a time (build_trws_graph:
-    // row_chunk), kept only where the checks of the chain schedule hold on it.
+    // `spec` is that schedule over these runs.  Built on request for one direction at a time (TrwsGraphOptions:
+    // row_chunk_forward / row_chunk_backward), kept only where the checks of the chain schedule hold on it.
     struct Chunked {
       bool ok = false;
       int32_t chunk = 0;
@@ -111,32 +111,74 @@ struct TrwsGraph {
   } sweep[2];
   static constexpr int kDescWords = 64;
   // every node has <= 8 incident edges and <= 4 foreign dependencies per direction, and the loader protocol
-  // terminates on both chain schedules (trws_graph.cpp); false: the generic kernel takes the graph
+  // terminates on both chain schedules (trws_graph_desc.cpp); false: the generic kernel takes the graph
   bool fast_ok = false;
   static constexpr int kMaxSlots = 8;
 };
 
+// What build_trws_graph is asked for besides the connectivity.  Everything that changes the result is a member, so a
+// cache of graphs (trws_plan_create.hip) compares keys with the one operator== below and cannot miss an option.
+struct TrwsGraphOptions {
+  // > 0: if a sweep has more runs than that, cut runs in front of nodes that wait long for a foreign node and
+  // dispense them in dependency-level order (trws_graph.cpp: contiguous_runs, trws_graph_schedule.cpp: chain_runs)
+  int64_t max_resident_runs = 0;
+  const int32_t *owner = nullptr;     // N entries, values 0 .. nstrips-1, or nullptr: see TrwsGraph::owner
+  int nstrips = 1;
+  int64_t certainly_resident = 256;   // workgroups sure to be resident whatever the kernel's LDS use (the CU count)
+  // 0 = SetAutomaticOrdering (ordering.cpp:7-157, what the gateway calls, trws_mex.cpp:121);
+  // 1 = node index order, MRFEnergy's order when SetAutomaticOrdering is not called (nodes in the
+  // order they were added, MRFEnergy.cpp:37-76).  On the image grid: H + W - 1 anti-diagonal levels,
+  // no serial border chain.  Another valid TRW-S schedule, not the gateway's results.
+  int ordering = 0;
+  // row_chunk_forward > 0: also build Sweep::chunked with runs of at most that many positions, in every direction that
+  // has more runs than chunk_resident workgroups (those certain to be resident in the launch that will walk them);
+  // row_chunk_backward >= 0: the backward sweep's own length (0: whole rows there).
+  int64_t row_chunk_forward = 0, row_chunk_backward = -1, chunk_resident = 0;
+  // visits per segment of the speculative schedule; 0: spec_segment_length(), read once per build
+  int seg_len = 0;
+};
+// (owner is compared by the one who keeps the arrays: by content, not by address)
+inline bool operator==(const TrwsGraphOptions &a, const TrwsGraphOptions &b) {
+  return a.max_resident_runs == b.max_resident_runs && a.nstrips == b.nstrips && a.certainly_resident == b.certainly_resident &&
+         a.ordering == b.ordering && a.row_chunk_forward == b.row_chunk_forward && a.row_chunk_backward == b.row_chunk_backward &&
+         a.chunk_resident == b.chunk_resident && a.seg_len == b.seg_len;
+}
+
 // conn: 2 x E zero-based (column major: conn[2e] = tail, conn[2e+1] = head).
 // Returns false and sets `err` on invalid input.
-// max_resident_runs > 0: if a sweep has more runs than that, cut runs in front of nodes that
-// wait long for a foreign node and dispense them in dependency-level order (see trws_graph.cpp).
-// owner (N entries, values 0 .. nstrips-1) or nullptr: see TrwsGraph::owner.
-// certainly_resident: workgroups sure to be resident whatever the kernel's LDS use (the CU count).
-bool build_trws_graph(int64_t N, int64_t E, const uint32_t *conn, TrwsGraph &g,
-                      std::string &err, int64_t max_resident_runs = 0,
-                      const int32_t *owner = nullptr, int nstrips = 1, int64_t certainly_resident = 256,
-                      int ordering = 0, int64_t row_chunk = 0, int64_t chunk_resident = 0, int64_t row_chunk_backward = -1);
-// row_chunk > 0: also build Sweep::chunked with runs of at most that many positions, in every direction that has more
-// runs than chunk_resident workgroups (those certain to be resident in the launch that will walk them);
-// row_chunk_backward >= 0: the backward sweep's own length (0: whole rows there).
+bool build_trws_graph(int64_t N, int64_t E, const uint32_t *conn, const TrwsGraphOptions &opt, TrwsGraph &g, std::string &err);
 // visits per segment of the speculative schedule (STEREO_HIP_TRWS_SPEC_SEG, default 16)
 int spec_segment_length();
-// ordering: 0 = SetAutomaticOrdering (ordering.cpp:7-157, what the gateway calls, trws_mex.cpp:121);
-// 1 = node index order, MRFEnergy's order when SetAutomaticOrdering is not called (nodes in the
-// order they were added, MRFEnergy.cpp:37-76).  On the image grid: H + W - 1 anti-diagonal levels,
-// no serial border chain.  Another valid TRW-S schedule, not the gateway's results.
 
-// Descriptor words added for strips (layout of the rest: trws.hip NodeDesc)
+// ticket -> run of a schedule's ticket order (run_order, chain_run_order, Chunked::run_order): empty = 0, 1, 2, ...
+inline int32_t run_of_ticket(const std::vector<int32_t> &order, int64_t t) { return order.empty() ? (int32_t)t : order[(size_t)t]; }
+
+// The descriptor of one visit: kDescWords int32, decoded on the device by decode_desc (trws_dev.h: NodeDesc).
+//   word 0: node id            word 1: rank (the index of the node's completion flag)
+//   word 2: counts, see desc_pack            word 3: position of the node's lower-bound term (lb_pos_node)
+//   words 4-11:  edge ids, the n_out outgoing ones first, then the n_in incoming ones (k below: index in this list)
+//   words 12-19: per edge k: slot of an incoming edge in the outgoing list of the node visited one (0..7) or two
+//                (8..15) steps earlier in the same run, which hands the row over in LDS; -1: none
+//   words 20-23: ranks of the foreign dependencies (completion flags waited for)
+//   words 24-31: per outgoing edge k: position of its lower-bound term (lb_pos_edge)
+//   words 32-39: per incoming edge k: the node at its other end (its label feeds the primal)
+//   word 40: completion flags are raised in the middle of the next visit (1) or lazily at the run's end (0)
+//   words 41, 42: words 12-19 once more, one byte each (0xff = none), for the compute waves
+constexpr int kDescNode = 0, kDescRank = 1, kDescCounts = 2, kDescLbNode = 3, kDescEdge = 4, kDescSlot = 12, kDescDep = 20,
+              kDescLbEdge = 24, kDescOther = 32, kDescEager = 40, kDescSlotBytes = 41;
+constexpr int kMaxDeps = 4;   // foreign dependencies a descriptor holds
+// word 2: n_out | n_in << 4 | dependencies << 8 | bit 12 (a loader may wait for the node's dependencies two visits
+// ahead, trws_graph_desc.cpp: describe_visit) | Swap() parity of edge k << (16 + k)
+inline int32_t desc_pack(int nout, int nin, int ndep, bool ahead, uint32_t mdir) {
+  return (int32_t)((uint32_t)nout | ((uint32_t)nin << 4) | ((uint32_t)ndep << 8) | ((uint32_t)ahead << 12) | (mdir << 16));
+}
+inline int desc_nout(const int32_t *D) { return D[kDescCounts] & 15; }
+inline int desc_nin(const int32_t *D) { return (D[kDescCounts] >> 4) & 15; }
+inline int desc_ndep(const int32_t *D) { return (D[kDescCounts] >> 8) & 15; }
+inline bool desc_ahead(const int32_t *D) { return (D[kDescCounts] >> 12) & 1; }
+inline uint32_t desc_mdir(const int32_t *D) { return ((uint32_t)D[kDescCounts] >> 16) & 255; }
+
+// Descriptor words added for strips
 //   word 43: bits 0-7 outgoing message k goes to the neighbouring strip; bits 8-15 which one
 //            (0 = previous strip, 1 = next strip); bit 16 / 17: flag (+ label) also raised in the
 //            previous / next strip's memory

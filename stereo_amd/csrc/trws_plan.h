@@ -25,7 +25,7 @@ constexpr int kCtlWords = 8;  // d_ctl: ticket, abort flag, four words of give-u
 static_assert(kFamilyPipeMaxK == kWave && kFamilyPipe2MaxK == 2 * kWave && kFamilyWideMaxK == 4 * kWave &&
               kFamilyGenericMaxK == kGenericMaxK && kFamilyLargeMaxK == kLargeMaxK, "trws_family.h restates the kernels' label ranges");
 
-// The environment switches a plan freezes at creation (the last three are read by the gateway and by trws_graph.cpp).
+// The environment switches a plan freezes at creation (the last three are read by the gateway and by trws_graph.cpp: spec_segment_length).
 // Creation reads its switches through this table and the gateway's cache key is made of the same table: a cached
 // plan must not outlive them.
 enum TrwsSwitch { kSwFast, kSwSpec, kSwGranules, kSwCertificate, kSwSpinSeconds, kSwProf, kSwTimeline, kSwFineGrained, kSwGpus, kSwSpecSeg, kSwBeliefsStrips, kSwRowChunk, kSwIterateAhead, kSwCount };

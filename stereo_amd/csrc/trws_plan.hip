@@ -26,7 +26,10 @@
 //
 // The host code around the kernels, by concern:
 //   trws_family.h/.cpp   the kernel-family rule (host only)
-//   trws_graph.h/.cpp    graph analysis: order, schedules, descriptors, strip layouts (host only)
+//   trws_graph.h         graph analysis (host only), one stage per function behind build_trws_graph: trws_graph.cpp order,
+//                        lists, rank-contiguous runs · trws_graph_schedule.cpp chain schedule, sub-row runs ·
+//                        trws_graph_desc.cpp descriptors, protocol proof, marks · trws_graph_strips.cpp strip layouts ·
+//                        trws_graph_views.cpp host views for tests · trws_graph_stages.h what the stages pass on
 //   trws_plan.h          struct stereo_trws_plan, the table of creation-time switches (internal)
 //   trws_plan_create.hip creation (with the cache of the last graph analysis) and destruction
 //   trws_plan.hip        this file: inputs, iterations, results, strip wiring, min-marginals

@@ -3,7 +3,6 @@
 #include <algorithm>
 #include <cstring>
 #include <mutex>
-#include <tuple>
 
 #include "trws_plan.h"
 
@@ -14,15 +13,12 @@ namespace {
 // size); consecutive plans for the same image grid -- every trws() call of a fusion loop --
 // share the last one.
 struct GraphKey {
-  int64_t N = -1, E = -1, capacity = -1, cus = -1, chunk = 0, chunk_b = 0, chunk_resident = 0;
-  int nstrips = 1, ordering = 0, seg = 0;
+  int64_t N = -1, E = -1;
   const uint32_t *conn = nullptr;   // the caller's arrays in a key made for a lookup, the cache's copies in the one it keeps
-  const int32_t *owner = nullptr;
+  TrwsGraphOptions opt;             // (opt.owner likewise; read only with more than one strip)
   bool operator==(const GraphKey &o) const {
-    return std::tie(N, E, capacity, cus, nstrips, ordering, seg, chunk, chunk_b, chunk_resident) ==
-               std::tie(o.N, o.E, o.capacity, o.cus, o.nstrips, o.ordering, o.seg, o.chunk, o.chunk_b, o.chunk_resident) &&
-           std::memcmp(conn, o.conn, sizeof(uint32_t) * 2 * (size_t)E) == 0 &&
-           (nstrips == 1 || std::memcmp(owner, o.owner, sizeof(int32_t) * (size_t)N) == 0);
+    return N == o.N && E == o.E && opt == o.opt && std::memcmp(conn, o.conn, sizeof(uint32_t) * 2 * (size_t)E) == 0 &&
+           (opt.nstrips == 1 || std::memcmp(opt.owner, o.opt.owner, sizeof(int32_t) * (size_t)N) == 0);
   }
 };
 
@@ -32,14 +28,12 @@ std::shared_ptr<const TrwsGraph> shared_graph_for(GraphKey key, std::string &ger
   std::lock_guard<std::mutex> lock(mutex);
   if (cache.g && cache.key == key) return cache.g;
   auto fresh = std::make_shared<TrwsGraph>();
-  if (!build_trws_graph(key.N, key.E, key.conn, *fresh, gerr, key.capacity, key.nstrips > 1 ? key.owner : nullptr, key.nstrips, key.cus, key.ordering,
-                        key.chunk, key.chunk_resident, key.chunk_b))
-    return nullptr;
+  if (!build_trws_graph(key.N, key.E, key.conn, key.opt, *fresh, gerr)) return nullptr;
   cache.g.reset();
   if (key.N <= (1 << 23)) {  // (3000 x 2000: 3 GB of descriptors stay in host memory until the next connectivity)
     cache.conn.assign(key.conn, key.conn + 2 * (size_t)key.E);
-    if (key.nstrips > 1) cache.owner.assign(key.owner, key.owner + key.N); else cache.owner.clear();
-    cache.key = key; cache.key.conn = cache.conn.data(); cache.key.owner = cache.owner.data();
+    if (key.opt.nstrips > 1) cache.owner.assign(key.opt.owner, key.opt.owner + key.N); else cache.owner.clear();
+    cache.key = key; cache.key.conn = cache.conn.data(); cache.key.opt.owner = cache.owner.data();
     cache.g = fresh;
   } else {
     cache.conn.clear(); cache.owner.clear();
@@ -101,19 +95,21 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
       P->graph = share->graph;
     } else {
       GraphKey key;
-      key.N = N; key.E = E; key.capacity = capacity; key.cus = P->cus; key.nstrips = nstrips; key.ordering = ordering;
-      key.seg = spec_segment_length(); key.conn = conn; key.owner = owner;
+      TrwsGraphOptions &opt = key.opt;
+      key.N = N; key.E = E; key.conn = conn;
+      opt.max_resident_runs = capacity; opt.certainly_resident = P->cus; opt.nstrips = nstrips; opt.ordering = ordering;
+      opt.seg_len = spec_segment_length(); opt.owner = nstrips > 1 ? owner : nullptr;
       // Sub-row runs: for a whole problem the K <= 64 kernel may run, in the directions with more runs
       // than the launch is certain to keep resident -- elsewhere a run finds a workgroup of its own anyway.
       if (possible(at_best, TrwsFamily::Pipe) && nstrips == 1) {
-        key.chunk = kRowChunkDefault[0]; key.chunk_b = kRowChunkDefault[1];
+        opt.row_chunk_forward = kRowChunkDefault[0]; opt.row_chunk_backward = kRowChunkDefault[1];
         if (const char *c = trws_switch(kSwRowChunk)) {
-          key.chunk = key.chunk_b = std::max(0, std::atoi(c));
-          if (const char *comma = std::strchr(c, ',')) key.chunk_b = std::max(0, std::atoi(comma + 1));
+          opt.row_chunk_forward = opt.row_chunk_backward = std::max(0, std::atoi(c));
+          if (const char *comma = std::strchr(c, ',')) opt.row_chunk_backward = std::max(0, std::atoi(comma + 1));
         }
-        key.chunk_resident = max_blocks > 0 ? std::min<int64_t>(P->cus, max_blocks) : P->cus;
+        opt.chunk_resident = max_blocks > 0 ? std::min<int64_t>(P->cus, max_blocks) : P->cus;
         if (const char *be = std::getenv("STEREO_HIP_TRWS_BLOCKS"))
-          if (std::atoi(be) > 0) key.chunk_resident = std::min<int64_t>(key.chunk_resident, std::atoi(be));
+          if (std::atoi(be) > 0) opt.chunk_resident = std::min<int64_t>(opt.chunk_resident, std::atoi(be));
       }
       P->graph = shared_graph_for(key, gerr);
       if (!P->graph) return fail(gerr, err, errcap);

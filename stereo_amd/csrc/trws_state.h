@@ -1,6 +1,6 @@
 // The solver state's host-side rules (the C ABI: include/stereo_hip.h), host only: the key of a
 // connectivity, what a load refuses, and which rows of a state a strip is authoritative for.  Shared by plan creation,
-// trws_state.hip and the host-only entries in trws_graph.cpp.
+// trws_state.hip and the host-only entries in trws_graph_views.cpp.
 #pragma once
 #include <cstdint>
 #include <string>

@@ -226,7 +226,7 @@ int state_save(const char *who, stereo_trws_plan *const *plans, int n, stereo_tr
       // Strips commit sums of per-strip partial sums, equal to the single plan's to rounding only.  A state is
       // canonical, so its energy and bound are summed once more from the terms of the iteration collected last (they
       // are still in the strips' host buffers), in the single plan's order: a strip's terms are that order restricted
-      // to its nodes (trws_graph.cpp: lb_pos_node / lb_pos_edge, e_pos), so a cursor per strip merges them back.
+      // to its nodes (trws_graph.cpp: flatten_lists -- lb_pos_node / lb_pos_edge, e_pos), so a cursor per strip merges them back.
       const TrwsGraph &g = *P0->graph;
       int64_t at[kMaxGroup] = {0};
       double lb = 0, en = 0;

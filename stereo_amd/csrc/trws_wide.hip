@@ -1032,7 +1032,7 @@ __device__ __forceinline__ void wide_body(DevParams p, int epoch) {
       // stage, then this wave waits for node pos + 2's flags and sends its requests, which stay in
       // flight across the barrier: flag round trip and fetch round trip of a node overlap with the
       // visit before its own instead of adding up inside it.  Only where the descriptor allows it
-      // (bit 12 of word 2, trws_graph.cpp): what is waited for must not depend on the nodes this
+      // (bit 12 of word 2, trws_graph_desc.cpp: describe_visit): what is waited for must not depend on the nodes this
       // workgroup has not yet made visible; elsewhere (the interleaved last rows) the node is fetched
       // during the visit before its own, as loader B always did.
       typedef int wide_v4i __attribute__((ext_vector_type(4)));

@@ -1,7 +1,8 @@
 """CPU: AddressSanitizer + UndefinedBehaviorSanitizer runs (SURVEY.md 5 "race detection / sanitizers":
 the reference has none).  (i) the oracle's C restatement -- every parity test leans on it --
 (`make -C oracle sanitize`), (ii) the product's host-side graph analysis and strip schedule
-(stereo_amd/csrc/trws_graph.cpp through tools/sanitize_graph.cpp)."""
+(stereo_amd/csrc/trws_graph*.cpp through tools/sanitize_graph.cpp)."""
+import glob
 import os
 import shutil
 import subprocess
@@ -31,7 +32,7 @@ def test_host_graph_analysis_is_clean_under_sanitizers(tmp_path):
     exe = str(tmp_path / "sanitize_graph")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-w",
-           os.path.join(ROOT, "tools", "sanitize_graph.cpp"), os.path.join(ROOT, "stereo_amd", "csrc", "trws_graph.cpp"),
+           os.path.join(ROOT, "tools", "sanitize_graph.cpp"), *sorted(glob.glob(os.path.join(ROOT, "stereo_amd", "csrc", "trws_graph*.cpp"))),
            "-o", exe, "-lpthread"]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert b.returncode == 0, b.stderr[-3000:]

@@ -98,6 +98,7 @@ def test_bad_arguments_are_refused():
 
 def test_list_builder_is_clean_under_sanitizers(tmp_path):
     """tools/sanitize_strip_lists.cpp: the builder over the grids above under ASan + UBSan, a stand-alone program."""
+    import glob
     import os
     import shutil
     import subprocess
@@ -107,7 +108,7 @@ def test_list_builder_is_clean_under_sanitizers(tmp_path):
     exe = str(tmp_path / "sanitize_strip_lists")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(root, "include"), "-w",
-           os.path.join(root, "tools", "sanitize_strip_lists.cpp"), os.path.join(root, "stereo_amd", "csrc", "trws_graph.cpp"),
+           os.path.join(root, "tools", "sanitize_strip_lists.cpp"), *sorted(glob.glob(os.path.join(root, "stereo_amd", "csrc", "trws_graph*.cpp"))),
            "-o", exe, "-lpthread"]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     if b.returncode != 0 and "sanitize" in b.stderr.lower() and "cannot find" in b.stderr.lower():

@@ -143,6 +143,7 @@ def test_state_file_round_trip(tmp_path):
 
 def test_state_rules_are_clean_under_sanitizers(tmp_path):
     """tools/sanitize_state_rows.cpp: both host entries under ASan + UBSan, a stand-alone program."""
+    import glob
     import os
     import shutil
     import subprocess
@@ -152,7 +153,7 @@ def test_state_rules_are_clean_under_sanitizers(tmp_path):
     exe = str(tmp_path / "sanitize_state_rows")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(root, "include"), "-w",
-           os.path.join(root, "tools", "sanitize_state_rows.cpp"), os.path.join(root, "stereo_amd", "csrc", "trws_graph.cpp"),
+           os.path.join(root, "tools", "sanitize_state_rows.cpp"), *sorted(glob.glob(os.path.join(root, "stereo_amd", "csrc", "trws_graph*.cpp"))),
            "-o", exe, "-lpthread"]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     if b.returncode != 0 and "sanitize" in b.stderr.lower() and "cannot find" in b.stderr.lower():

@@ -1,7 +1,7 @@
 // Microbenchmark (development tool): cycles per message update for the three
 // message paths, one wave, data in LDS/L2.  Build & run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude tools/micro_message.hip \
-//         stereo_amd/csrc/trws_graph.cpp -o /tmp/micro && /tmp/micro
+//         stereo_amd/csrc/trws_graph*.cpp -o /tmp/micro && /tmp/micro
 #include "../stereo_amd/csrc/trws.hip"
 
 using namespace stereo;

@@ -1,8 +1,8 @@
-// Development / CI tool: the product's host-side graph analysis (stereo_amd/csrc/trws_graph.cpp: node
+// Development / CI tool: the product's host-side graph analysis (stereo_amd/csrc/trws_graph*.cpp: node
 // order, orientation, lists, dataflow schedule, strip cuts, descriptors) under AddressSanitizer +
 // UndefinedBehaviorSanitizer, on grids of awkward shapes, random multigraphs and row strips.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-//       -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude tools/sanitize_graph.cpp stereo_amd/csrc/trws_graph.cpp
+//       -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude tools/sanitize_graph.cpp stereo_amd/csrc/trws_graph*.cpp
 #include <cstdint>
 #include <cstdio>
 #include <string>

@@ -3,7 +3,7 @@
 // under AddressSanitizer + UndefinedBehaviorSanitizer, with arrays of exactly the sizes the entries take.
 // Prints SANITIZE_STATE_ROWS_OK.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -D__HIP_PLATFORM_AMD__ \
-//       -I/opt/rocm/include -Iinclude tools/sanitize_state_rows.cpp stereo_amd/csrc/trws_graph.cpp -lpthread
+//       -I/opt/rocm/include -Iinclude tools/sanitize_state_rows.cpp stereo_amd/csrc/trws_graph*.cpp -lpthread
 #include <cstdint>
 #include <cstdio>
 #include <cstring>

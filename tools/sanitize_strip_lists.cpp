@@ -1,9 +1,9 @@
 // Development / CI tool (tests/test_strip_beliefs_cpu.py): the host-side builder of a strip's belief lists
-// (stereo_amd/csrc/trws_graph.cpp: build_strip_belief_lists behind stereo_trws_strip_belief_lists_host) under
+// (stereo_amd/csrc/trws_graph*.cpp: build_strip_belief_lists behind stereo_trws_strip_belief_lists_host) under
 // AddressSanitizer + UndefinedBehaviorSanitizer, over the CPU test's grids and strip counts, with arrays of exactly the
 // sizes the entry reports.  Prints SANITIZE_STRIP_LISTS_OK.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -D__HIP_PLATFORM_AMD__ \
-//       -I/opt/rocm/include -Iinclude tools/sanitize_strip_lists.cpp stereo_amd/csrc/trws_graph.cpp -lpthread
+//       -I/opt/rocm/include -Iinclude tools/sanitize_strip_lists.cpp stereo_amd/csrc/trws_graph*.cpp -lpthread
 #include <cstdint>
 #include <cstdio>
 #include <string>
