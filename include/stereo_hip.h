@@ -29,8 +29,9 @@ extern "C" {
  * behind dispmap_globalstereo), stereo_trws_plan_debug_terms / _messages, stereo_segpln_planes_batch.  7: TRW-S takes
  * up to 4096 labels with one shared strictly ascending positions vector (stereo_trws_plan_path 5).  8: stereo_trws_batch_*
  * (independent plans that share one launch per sweep).  10: stereo_trws_plans_state_* (solver state: save / load),
- * stereo_trws_state_check, stereo_trws_strip_state_rows_host. */
-#define STEREO_HIP_ABI_VERSION 10
+ * stereo_trws_state_check, stereo_trws_strip_state_rows_host.  11: stereo_lr_check / stereo_lr_fill (left-right
+ * consistency). */
+#define STEREO_HIP_ABI_VERSION 11
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -626,6 +627,51 @@ int stereo_ncc_best_disp(const double *ncc, int H, int W, int D, int layout, con
 int stereo_globalstereo_unary(const double *im0, const double *im1, int H, int W, int C,
                               const double *P2, double d_min, double d_step, double col_thresh,
                               const double *assignment, double *U, char *err, size_t errcap);
+
+/* ---- left-right consistency: cross-check, occlusion map, fill ------------------------ *
+ * No reference counterpart (the reference's maps are single-view).  A disparity map is H x W doubles,
+ * column major as stereo_ncc_best_disp writes it: element (y, x) at y + H*x, zero based.  A pixel at
+ * column x of the map's own view with disparity d matches column x - direction*d of the other view
+ * (dispmap_ncc.m:143-154 is direction = +1, the left-referenced map; -1 is the right-referenced one).
+ *
+ * Refused with a message: direction other than +1 / -1, tol negative or NaN, H or W below 1,
+ * H*W >= 2^31 (columns and sources are int32), NULL for a required array.  H = 1 and W = 1 are valid.
+ * The arguments are checked before the device is looked for. */
+
+/* status (int32) and residual (double, may be NULL) per pixel of d_ref:
+ *   d = d_ref(y, x) not finite                                  -> status 4, residual NaN
+ *   xi = floor(x - direction*d + 0.5) outside 0 .. W - 1         -> status 3 (out of view), residual NaN
+ *   dr = d_other(y, xi) not finite                              -> status 4, residual NaN
+ *   residual = d - dr;  |residual| <= tol                       -> status 0 (consistent)
+ *                       residual < 0                            -> status 1 (occluded: the other view sees
+ *                                                                  something nearer there)
+ *                       residual > 0                            -> status 2 (mismatch)
+ * The nearest column, ties to the higher index; no interpolation of d_other.  Every operation is exact in
+ * IEEE double, so the outputs are those of the same lines written in any language, bit for bit. */
+int stereo_lr_check(const double *d_ref, const double *d_other, int H, int W, int direction,
+                    double tol, int32_t *status, double *residual, char *err, size_t errcap);
+/* Row by row: a pixel with status 0 keeps its disparity, source = x.  Any other pixel takes the nearest
+ * status-0 pixel of its row at a lower column (l) and at a higher column (r): the one with the smaller
+ * disparity (the background) -- r only if its disparity is strictly smaller, l otherwise or if r does not
+ * exist -- and source (int32, may be NULL) is that column.  A row without a status-0 pixel: NaN, source -1.
+ * Not in place: filled == d_ref and source == status are refused (filled and source hold intermediate values
+ * while the inputs are still being read); the four arrays must not overlap. */
+int stereo_lr_fill(const double *d_ref, const int32_t *status, int H, int W,
+                   double *filled, int32_t *source, char *err, size_t errcap);
+/* The same on device arrays of the caller (e.g. torch tensors), launched on `stream` (hipStream_t,
+ * NULL = default) without waiting for it. */
+int stereo_lr_check_device(const double *d_ref, const double *d_other, int H, int W, int direction,
+                           double tol, int32_t *status, double *residual, void *stream, char *err,
+                           size_t errcap);
+int stereo_lr_fill_device(const double *d_ref, const int32_t *status, int H, int W,
+                          double *filled, int32_t *source, void *stream, char *err, size_t errcap);
+/* The fill kernel splits a row into `chunks` contiguous column ranges, one wave each (1 .. 16; the results
+ * do not depend on it).  stereo_lr_fill_chunks: the number the entries above use;
+ * stereo_lr_fill_device_chunks: stereo_lr_fill_device with another one (timing, tests). */
+int stereo_lr_fill_chunks(void);
+int stereo_lr_fill_device_chunks(const double *d_ref, const int32_t *status, int H, int W,
+                                 double *filled, int32_t *source, int chunks, void *stream, char *err,
+                                 size_t errcap);
 
 /* ---- device-resident fusion moves --------------------------------------- *
  * The state of one dispmap object kept in HBM across moves: connectivity, weights, points,

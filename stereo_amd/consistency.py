@@ -1,0 +1,241 @@
+"""Left-right consistency (no reference counterpart): the cross-check of two disparity
+maps, the occlusion map it gives, the per-row fill, and ``solve_pair_ncc``, which solves both views of a
+pair in one TRW-S batch and checks each map against the other.
+
+Maps are H x W float64 arrays (any memory order on the host; the device forms take column-major
+storage, element (y, x) at y + H*x).  ``direction`` +1: the map is referenced on the left image, a pixel
+at column x with disparity d matches column x - d of the other view; -1: the right-referenced map.
+Status values: 0 consistent, 1 occluded, 2 mismatch, 3 out of view, 4 not finite.
+"""
+import ctypes as C
+import time
+
+import numpy as np
+
+from . import _lib
+from . import terms as T
+from ._lib import StereoHipError
+from .trws import TrwsBatch, TrwsPlan
+
+CONSISTENT, OCCLUDED, MISMATCH, OUT_OF_VIEW, NOT_FINITE = range(5)
+
+
+def fill_chunks():
+    """Column ranges (waves) the fill kernel splits a row into (stereo_lr_fill_chunks)."""
+    return int(_lib.lib().stereo_lr_fill_chunks())
+
+
+def _map(a, what, dtype=np.float64):
+    a = np.asarray(a)
+    if a.ndim != 2:
+        raise StereoHipError("%s must be an H x W array" % what)
+    return np.asfortranarray(a, dtype=dtype)
+
+
+def _p(a, t=C.c_double):
+    return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
+
+
+def lr_check(d_ref, d_other, direction, tol, want_residual=True):
+    """stereo_lr_check -> (status H x W int32, residual H x W float64 or None)."""
+    d_ref, d_other = _map(d_ref, "d_ref"), _map(d_other, "d_other")
+    if d_ref.shape != d_other.shape:
+        raise StereoHipError("lr_check: the two maps must have the same size")
+    H, W = d_ref.shape
+    status = np.zeros((H, W), np.int32, order="F")
+    residual = np.zeros((H, W), order="F") if want_residual else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_lr_check(_p(d_ref), _p(d_other), C.c_int(H), C.c_int(W), C.c_int(int(direction)),
+                                    C.c_double(float(tol)), _p(status, C.c_int32), _p(residual), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return status, residual
+
+
+def lr_fill(d_ref, status, want_source=True):
+    """stereo_lr_fill -> (filled H x W float64, source H x W int32 or None)."""
+    d_ref, status = _map(d_ref, "d_ref"), _map(status, "status", np.int32)
+    if d_ref.shape != status.shape:
+        raise StereoHipError("lr_fill: status must have the map's size")
+    H, W = d_ref.shape
+    filled = np.zeros((H, W), order="F")
+    source = np.zeros((H, W), np.int32, order="F") if want_source else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_lr_fill(_p(d_ref), _p(status, C.c_int32), C.c_int(H), C.c_int(W), _p(filled),
+                                   _p(source, C.c_int32), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return filled, source
+
+
+def _device_map(t, what, dtype, shape=None):
+    """A torch tensor that stores an H x W map column major: shape (W, H), contiguous, on the current device."""
+    import torch
+    want = torch.float64 if dtype is np.float64 else torch.int32
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != want or not t.is_cuda or not t.is_contiguous():
+        raise StereoHipError("%s must be a contiguous (W, H) %s tensor on the device (column-major H x W)" % (what, want))
+    if t.device.index != torch.cuda.current_device():
+        raise StereoHipError("%s must be on the current device" % what)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise StereoHipError("%s must have the map's size" % what)
+    return t
+
+
+def _stream(stream):
+    if stream is None:
+        import torch
+        return torch.cuda.current_stream().cuda_stream
+    return int(getattr(stream, "cuda_stream", stream))
+
+
+def lr_check_device(d_ref, d_other, direction, tol, status=None, residual=None, stream=None, want_residual=True):
+    """stereo_lr_check_device on torch tensors of the current device.  A map is a contiguous (W, H) tensor: the
+    column-major storage of H x W (``torch.from_numpy(m.T.copy())``, ``t.T`` on the way back).  Launched on `stream`
+    (a torch stream or a raw handle; default: torch's current stream) without waiting for it.  `status` / `residual`:
+    tensors to write into; made here otherwise.  -> (status, residual or None)."""
+    import torch
+    d_ref = _device_map(d_ref, "d_ref", np.float64)
+    d_other = _device_map(d_other, "d_other", np.float64, d_ref.shape)
+    W, H = d_ref.shape
+    status = torch.empty((W, H), dtype=torch.int32, device=d_ref.device) if status is None else _device_map(status, "status", np.int32, d_ref.shape)
+    if residual is None and want_residual:
+        residual = torch.empty((W, H), dtype=torch.float64, device=d_ref.device)
+    elif residual is not None:
+        residual = _device_map(residual, "residual", np.float64, d_ref.shape)
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_lr_check_device(vp(d_ref), vp(d_other), C.c_int(H), C.c_int(W), C.c_int(int(direction)),
+                                           C.c_double(float(tol)), vp(status), vp(residual), C.c_void_p(_stream(stream)),
+                                           err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return status, residual
+
+
+def lr_fill_device(d_ref, status, filled=None, source=None, stream=None, want_source=True, chunks=None):
+    """stereo_lr_fill_device on torch tensors, as lr_check_device takes them.  `chunks`: another number of column ranges
+    than fill_chunks() (stereo_lr_fill_device_chunks; the results do not depend on it).  -> (filled, source or None)."""
+    import torch
+    d_ref = _device_map(d_ref, "d_ref", np.float64)
+    status = _device_map(status, "status", np.int32, d_ref.shape)
+    W, H = d_ref.shape
+    filled = torch.empty((W, H), dtype=torch.float64, device=d_ref.device) if filled is None else _device_map(filled, "filled", np.float64, d_ref.shape)
+    if source is None and want_source:
+        source = torch.empty((W, H), dtype=torch.int32, device=d_ref.device)
+    elif source is not None:
+        source = _device_map(source, "source", np.int32, d_ref.shape)
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    err = _lib.errbuf()
+    L = _lib.lib()
+    if chunks is None:
+        rc = L.stereo_lr_fill_device(vp(d_ref), vp(status), C.c_int(H), C.c_int(W), vp(filled), vp(source),
+                                     C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    else:
+        rc = L.stereo_lr_fill_device_chunks(vp(d_ref), vp(status), C.c_int(H), C.c_int(W), vp(filled), vp(source),
+                                            C.c_int(int(chunks)), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return filled, source
+
+
+# ---------------------------------------------------------------- both views of a pair
+
+def flip_volume(vol, H, W):
+    """A D x (H*W) label-fastest volume with its columns x -> W - 1 - x."""
+    D = vol.shape[0]
+    return np.asfortranarray(vol.reshape((D, H, W), order="F")[:, :, ::-1].reshape((D, H * W), order="F"))
+
+
+def pair_unaries(images, disparities, unary_weight):
+    """The two D x N unary volumes unary_weight * (1 - ncc) of a pair: the left-referenced one as dispmap_ncc builds
+    it, the right-referenced one by the mirror: the same volume function on the horizontally flipped
+    images in swapped order, flipped back."""
+    im0, im1 = (np.asarray(im, dtype=np.float64) for im in images[:2])
+    H, W = im0.shape[:2]
+    left = T.ncc_volume(im0, im1, disparities, 2, layout=1)
+    right = flip_volume(T.ncc_volume(im1[:, ::-1], im0[:, ::-1], disparities, 2, layout=1), H, W)
+    return unary_weight * (1.0 - left), unary_weight * (1.0 - right)
+
+
+def occlusion_aware_unary(unary, status):
+    """`unary` (D x N) with the columns of the occluded pixels (status 1) zeroed: the data term says nothing there."""
+    u = np.array(unary, dtype=np.float64, order="F")
+    u[:, np.asarray(status).T.reshape(-1) == OCCLUDED] = 0.0
+    return u
+
+
+class ViewResult:
+    """One view of solve_pair_ncc: `labels` (N, one based), `dispmap`, `status`, `residual`, `filled`, `source`
+    (H x W), and per pass `energy`, `lower_bound`, `iterations` (lists: the first solve, then the refine pass)."""
+
+    def __init__(self):
+        self.labels = self.dispmap = self.status = self.residual = self.filled = self.source = None
+        self.energy, self.lower_bound, self.iterations = [], [], []
+
+
+class PairResult:
+    """solve_pair_ncc's result: `left` and `right` (ViewResult) and `times` (seconds per stage)."""
+
+    def __init__(self):
+        self.left, self.right = ViewResult(), ViewResult()
+        self.times = {}
+
+    @property
+    def views(self):
+        return self.left, self.right
+
+
+def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_relgap, check_tol=1.0, refine_iters=0):
+    """Both views of a rectified pair: two NCC unary volumes, two TRW-S plans on the image grid with the shared
+    positions `disparities`, iterated as one TrwsBatch; labels to maps; each map checked against the other and filled.
+    refine_iters > 0: per view, the solver state is saved, the unary columns of the occluded pixels are zeroed and
+    uploaded (which resets the plan), the state is loaded -- the warm start with other unaries of DESIGN.md 4.10 --
+    and the batch runs refine_iters more iterations; then check and fill again."""
+    disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
+    if len(images) != 2:
+        raise StereoHipError("solve_pair_ncc: images must be the two views of a pair, left first (got %d)" % len(images))
+    shapes = [np.shape(im) for im in images]
+    if shapes[0] != shapes[1] or len(shapes[0]) != 3 or shapes[0][2] != 3:
+        raise StereoHipError("solve_pair_ncc: the two images must be H x W x 3 arrays of one size (got %s and %s)" % tuple(shapes))
+    if disparities.size < 1:
+        raise StereoHipError("solve_pair_ncc: no disparities")
+    H, W = shapes[0][:2]
+    K, N = disparities.shape[0], H * W
+    out = PairResult()
+    clock = time.perf_counter
+    t0 = clock()
+    unaries = pair_unaries(images, disparities, unary_weight)
+    out.times["volumes"] = clock() - t0
+    conn = T.construct_neighborhood(H, W)
+    alphas = np.ones(conn.shape[1])
+    plans = [TrwsPlan(int(kernel), K, N, conn) for _ in range(2)]
+
+    def collect(stage):
+        t = clock()
+        for plan, view in zip(plans, out.views):
+            view.labels, en, lb, it = plan.result()
+            view.energy.append(en); view.lower_bound.append(lb); view.iterations.append(it)
+            view.dispmap = disparities[view.labels.astype(np.int64) - 1].reshape(W, H).T
+        for view, other, direction in ((out.left, out.right, 1), (out.right, out.left, -1)):
+            view.status, view.residual = lr_check(view.dispmap, other.dispmap, direction, check_tol)
+            view.filled, view.source = lr_fill(view.dispmap, view.status)
+        out.times[stage] = clock() - t
+
+    try:
+        t0 = clock()
+        for plan, unary in zip(plans, unaries):
+            plan.upload(unary, alphas, tol, positions=disparities)
+        with TrwsBatch(plans) as batch:
+            batch.iterate(maxiter, max_relgap)
+        out.times["solve"] = clock() - t0
+        collect("check_fill")
+        if refine_iters > 0:
+            t0 = clock()
+            for plan, unary, view in zip(plans, unaries, out.views):
+                state = plan.save_state()
+                plan.upload(occlusion_aware_unary(unary, view.status), alphas, tol, positions=disparities)
+                plan.load_state(state)
+            with TrwsBatch(plans) as batch:   # a fresh batch: a member that max_relgap stopped takes part again
+                batch.iterate(refine_iters, max_relgap)
+            out.times["refine"] = clock() - t0
+            collect("refine_check_fill")
+    finally:
+        for plan in plans:
+            plan.close()
+    return out

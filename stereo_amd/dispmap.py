@@ -19,6 +19,10 @@ from .trws import trws
 class dispmap_super:
     """dispmap_super.m.  Subclasses provide unary_cost()."""
 
+    # True on the object dispmap_ncc.mirrored() returns (DESIGN.md 6.1): it is referenced on the second image and works,
+    # internally, on the horizontally flipped pair; the maps that go in and out are in the un-flipped coordinates
+    _mirrored = False
+
     def __init__(self, images, kernel):
         self.images = [np.asarray(im, dtype=np.float64) for im in images]
         self.sz = self.images[0].shape[:2]
@@ -318,18 +322,43 @@ class dispmap_super:
         self.min_marginals = mm
         self.confidence = np.asarray(conf).reshape(self.sz[1], self.sz[0]).T
 
+    def _unflip(self, m):
+        """An H x W map between the object's internal columns and the image's own (the same operation both ways)."""
+        return m[:, ::-1] if self._mirrored else m
+
     def current_dispmap(self):
-        return self.disparitymap_from_assignment(self.assignment).reshape(self.sz[1], self.sz[0]).T
+        return self._unflip(self.disparitymap_from_assignment(self.assignment).reshape(self.sz[1], self.sz[0]).T)
 
     def set_disparity(self, disp):
         a = np.zeros((4, self.sz[0] * self.sz[1]))
         a[2] = 1
-        a[3] = -np.asarray(disp, np.float64).T.reshape(-1)   # column-major (:)
+        a[3] = -self._unflip(np.asarray(disp, np.float64)).T.reshape(-1)   # column-major (:)
         self.assignment = a
+
+    def cross_check(self, other, tol=1.0, fill=True):
+        """Left-right consistency of this object's map against the other view's (no reference
+        counterpart): stereo_lr_check of self.current_dispmap() against other.current_dispmap(), direction +1 unless
+        self is a mirrored object, then stereo_lr_fill.  Sets and returns self.consistency (H x W int32: 0 consistent,
+        1 occluded, 2 mismatch, 3 out of view, 4 not finite) and self.filled_dispmap (None without `fill`); the
+        residuals and the fill's source columns are kept as self.consistency_residual / self.filled_source."""
+        from . import consistency
+        for obj in (self, other):
+            if not getattr(obj, "_row_shift_views", False):
+                raise StereoHipError("cross_check: %s reaches its second view through a projection, not a row shift; "
+                                     "the left-right check is defined for dispmap_ncc" % type(obj).__name__)
+        if tuple(self.sz) != tuple(other.sz):
+            raise StereoHipError("cross_check: the two objects' sizes differ (%d x %d and %d x %d)" % (self.sz + other.sz))
+        d = self.current_dispmap()
+        self.consistency, self.consistency_residual = consistency.lr_check(d, other.current_dispmap(),
+                                                                           -1 if self._mirrored else 1, tol)
+        self.filled_dispmap, self.filled_source = consistency.lr_fill(d, self.consistency) if fill else (None, None)
+        return self.consistency, self.filled_dispmap
 
 
 class dispmap_ncc(dispmap_super):
     """dispmap_ncc.m"""
+
+    _row_shift_views = True    # the second view is the first one shifted along the rows: cross_check applies
 
     def __init__(self, images, disparities, kernel, unary_weight, tol):
         super().__init__(images, kernel)
@@ -370,13 +399,33 @@ class dispmap_ncc(dispmap_super):
         ctx.unary_ncc(self.ncc, self.disparities, self._unary_weight)
         return True
 
+    def _best_disp(self):
+        return T.ncc_best_disp(self.ncc, self.disparities)      # internal columns
+
     def best_disp_from_ncc(self):
-        return T.ncc_best_disp(self.ncc, self.disparities)
+        return self._unflip(self._best_disp())
 
     def init_solution(self):
         self.set_disparity(self.best_disp_from_ncc())
 
     restart = init_solution
+
+    def mirrored(self):
+        """A new dispmap_ncc referenced on the SECOND image, with the same disparities, kernel, unary weight and
+        tolerance (a definition, not a reference behaviour).  compute_ncc shifts one way only
+        (dispmap_ncc.m:146-149 assumes d >= 0), so the right-referenced volume is the same volume function on the
+        horizontally flipped images in swapped order, flipped back -- a mirrored conv2(..., 'same') window.  The object
+        works on the flipped pair throughout (images, ncc, planes and proposals are in flipped columns);
+        current_dispmap(), best_disp_from_ncc(), unary_volume() and set_disparity() speak in the un-flipped
+        coordinates of the right image, where a pixel at column x with disparity d matches column x + d of the left."""
+        m = dispmap_ncc([self.images[1][:, ::-1], self.images[0][:, ::-1]], self.disparities, self._kernel,
+                        self._unary_weight, self._tol)
+        m._mirrored = not self._mirrored      # (the mirror of a mirror is the first view again)
+        return m
+
+    def unary_volume(self):
+        """H x W x D: unary_weight * (1 - ncc), the unary of every fronto-parallel label, in the image's own columns."""
+        return self._unary_weight * (1.0 - (self.ncc[:, ::-1] if self._mirrored else self.ncc))
 
     # ---- proposals (dispmap_ncc.m:48-92).  Host side: a few dozen points and 3 x 3 SVDs per
     # proposal; MATLAB's svd is outside the reference tree, so this mirrors the arithmetic with
@@ -392,7 +441,7 @@ class dispmap_ncc(dispmap_super):
                 plane, _ = ctx.fit_plane(x, y, r)
                 return PlaneProposal(plane)
         pts = self.points
-        best = np.asarray(self.best_disp_from_ncc()).T.reshape(-1)      # column-major pixel order
+        best = np.asarray(self._best_disp()).T.reshape(-1)      # column-major pixel order
         ids = np.sqrt((pts[0] - x) ** 2 + (pts[1] - y) ** 2) < r
         p = self.fit_plane_to_points(np.vstack([pts[:, ids], best[ids]]))
         return np.asfortranarray(np.repeat(p.reshape(4, 1), self.sz[0] * self.sz[1], axis=1))
