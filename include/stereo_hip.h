@@ -30,8 +30,8 @@ extern "C" {
  * up to 4096 labels with one shared strictly ascending positions vector (stereo_trws_plan_path 5).  8: stereo_trws_batch_*
  * (independent plans that share one launch per sweep).  10: stereo_trws_plans_state_* (solver state: save / load),
  * stereo_trws_state_check, stereo_trws_strip_state_rows_host.  11: stereo_lr_check / stereo_lr_fill (left-right
- * consistency). */
-#define STEREO_HIP_ABI_VERSION 11
+ * consistency).  12: stereo_band_inputs / stereo_band_apply (band refinement around a solved disparity map). */
+#define STEREO_HIP_ABI_VERSION 12
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -672,6 +672,59 @@ int stereo_lr_fill_chunks(void);
 int stereo_lr_fill_device_chunks(const double *d_ref, const int32_t *status, int H, int W,
                                  double *filled, int32_t *source, int chunks, void *stream, char *err,
                                  size_t errcap);
+
+/* ---- band refinement around a solved disparity map ---------------------------------- *
+ * No reference counterpart as a call; the problem it builds is the reference's own energy restricted to
+ * fronto-parallel per-pixel labels.  From a disparity map `base` (H x W doubles, column major, N = H*W) and a
+ * strictly ascending vector `offsets` (K doubles, one of them 0.0), label k at pixel i means disparity
+ * base_i + offsets_k.  Unary and positions of label k are exactly what stereo_ncc_unary and
+ * stereo_trws_positions give for the proposal whose plane at pixel i is [0, 0, 1, -(base_i + offsets_k)];
+ * the plane -> disparity rule (dispmap_super.m:318-328) gives base_i + offsets_k for that plane exactly
+ * (with the plane's sign of zero: -0 where the sum is 0).
+ *
+ * In:  ncc          the NCC volume, layout 0 (H x W x D) or 1 (D x N, label fastest), D slices at `disparities`
+ *                   (ascending or not: both branches of the sampler's nearest-slice search), and unary_weight
+ *      conn         2 x E zero based, edge e = (i1, i2) = (conn[2e], conn[2e + 1])
+ * Out: unary        K x N, label fastest: unary(k, i) = unary_weight * (1 - sample(base_i + offsets_k)), with the
+ *                   sampler's rules (dispmap_ncc.m:222-249): ties go to the larger slice index, t2 == 1 or t2 == D
+ *                   gives the end slice, a disparity outside [min, max] of `disparities` gives -1e6.  A band label
+ *                   that leaves the volume's range therefore costs unary_weight * (1 + 1e6), as the same plane does
+ *                   in dispmap_ncc.  Nothing is clamped.
+ *      q, qprim     K x E, label fastest: q(k, e) = base_{i2} + offsets_k, qprim(k, e) = base_{i1} + offsets_k
+ *                   (the order stereo_trws_positions writes).  E = 0: conn, q and qprim may be NULL.
+ * stereo_band_apply: refined_i = base_i + offsets_{label_i - 1}, labels int32 and one based as
+ * stereo_trws_plan_result returns them: one addition.
+ *
+ * Everything is fp64 without FMA contraction and runs the code of stereo_ncc_unary (csrc/ncc_sample.h), so the
+ * outputs equal those of K calls of stereo_ncc_unary and one of stereo_trws_positions bit for bit.
+ *
+ * Refused with a message, before the device is looked for: offsets not finite, not strictly ascending or
+ * without 0.0; K < 1 or K > 512 (stereo_band_max_offsets); layout other than 0 / 1; D, H or W below 1;
+ * H*W >= 2^31; NULL for a required array.  The host entries also refuse a base entry that is not finite (the
+ * message names the pixel), a conn entry outside 0 .. N - 1 and, in apply, a label outside 1 .. K. */
+int stereo_band_max_offsets(void);
+int stereo_band_inputs(const double *ncc, int H, int W, int D, int layout, const double *disparities,
+                       double unary_weight, const double *base, const double *offsets, int K, int64_t E,
+                       const uint32_t *conn, double *unary, double *q, double *qprim, char *err,
+                       size_t errcap);
+int stereo_band_apply(const double *base, int H, int W, const int32_t *labels, const double *offsets,
+                      int K, double *refined, char *err, size_t errcap);
+/* The same on device arrays of the caller (ncc, base, conn, labels and every output), launched on `stream`
+ * (hipStream_t, NULL = default) without waiting for it.  The two short vectors are passed twice: `disparities` and
+ * `offsets` on the host (they are checked, and min / max / order of the slices come from them) and
+ * `d_disparities` / `d_offsets`, the same values in device memory, which the kernels read -- so the entries
+ * copy nothing.  `bad` (device int32, may be NULL) is set to zero on `stream` and then incremented once per
+ * pixel whose base is not finite (inputs) or whose label is outside 1 .. K (apply: that pixel's refined value
+ * is NaN).  The outputs of an offending pixel are unspecified but written.  An edge that names a pixel outside
+ * 0 .. N - 1 reads nothing; its positions are NaN. */
+int stereo_band_inputs_device(const double *ncc, int H, int W, int D, int layout, const double *disparities,
+                              const double *d_disparities, double unary_weight, const double *base,
+                              const double *offsets, const double *d_offsets, int K, int64_t E,
+                              const uint32_t *conn, double *unary, double *q, double *qprim, int32_t *bad,
+                              void *stream, char *err, size_t errcap);
+int stereo_band_apply_device(const double *base, int H, int W, const int32_t *labels, const double *offsets,
+                             const double *d_offsets, int K, double *refined, int32_t *bad, void *stream,
+                             char *err, size_t errcap);
 
 /* ---- device-resident fusion moves --------------------------------------- *
  * The state of one dispmap object kept in HBM across moves: connectivity, weights, points,

@@ -1,0 +1,293 @@
+"""Band refinement around a solved disparity map (the definition: include/stereo_hip.h).
+
+From a map ``base`` (H x W) and a strictly ascending vector ``offsets`` that contains 0.0, the TRW-S problem whose
+label k at pixel i means disparity ``base_i + offsets_k``: ``unary`` (K x N) from the NCC volume by the reference's
+sampler, ``q`` / ``qprim`` (K x E) as stereo_trws_positions gives them for the planes ``[0 0 1 -(base + offsets_k)]``.
+``refine_band`` builds these on the device, solves them level by level and applies the labels.
+
+Host forms take NumPy arrays in MATLAB shapes (volume H x W x D for layout 0, D x N for layout 1; conn 2 x E zero
+based).  Device forms take torch tensors of the current device: a map is a contiguous (W, H) tensor (the column-major
+storage of H x W, as lr_check_device takes it), the volume, ``unary``, ``q`` and ``qprim`` are flat float64 tensors in
+storage order, ``conn`` a flat int32 tensor of 2 E entries.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from . import terms as T
+from ._lib import StereoHipError
+from .consistency import _device_map, _map, _p, _stream
+from .trws import TrwsPlan
+
+
+def max_offsets():
+    return int(_lib.lib().stereo_band_max_offsets())
+
+
+def _vec(a, what):
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 1:
+        raise StereoHipError("%s must be a vector" % what)
+    return np.ascontiguousarray(a)
+
+
+def _volume(ncc, layout, H, W):
+    """The volume in the storage order the C entry reads, and D."""
+    ncc = np.asarray(ncc, dtype=np.float64)
+    if layout == 0:
+        if ncc.ndim == 2 and (H, W) == ncc.shape:
+            ncc = ncc[:, :, None]
+        if ncc.ndim != 3 or ncc.shape[:2] != (H, W):
+            raise StereoHipError("band: a layout 0 volume must be H x W x D with the map's H and W")
+        return np.asfortranarray(ncc), ncc.shape[2]
+    if layout == 1:
+        if ncc.ndim != 2 or ncc.shape[1] != H * W:
+            raise StereoHipError("band: a layout 1 volume must be D x (H*W) with the map's H and W")
+        return np.asfortranarray(ncc), ncc.shape[0]
+    return np.asfortranarray(ncc), (ncc.shape[2] if ncc.ndim == 3 else ncc.shape[0])   # (the library refuses the layout)
+
+
+def _conn(conn):
+    c = np.asarray(conn)
+    if c.ndim != 2 or c.shape[0] != 2:
+        raise StereoHipError("connectivity must be 2 x E")
+    return np.asfortranarray(c, dtype=np.uint32)
+
+
+def band_inputs(ncc, disparities, unary_weight, base, offsets, conn, layout=0):
+    """stereo_band_inputs -> (unary K x N, q K x E, qprim K x E), Fortran order."""
+    base = _map(base, "base")
+    H, W = base.shape
+    vol, D = _volume(ncc, layout, H, W)
+    disparities, offsets, conn = _vec(disparities, "disparities"), _vec(offsets, "offsets"), _conn(conn)
+    if disparities.shape[0] != D:
+        raise StereoHipError("band_inputs: %d disparities for a volume of %d slices" % (disparities.shape[0], D))
+    K, E, N = offsets.shape[0], conn.shape[1], H * W
+    unary = np.zeros((K, N), order="F")
+    q, qprim = np.zeros((K, E), order="F"), np.zeros((K, E), order="F")
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_band_inputs(_p(vol), C.c_int(H), C.c_int(W), C.c_int(D), C.c_int(int(layout)), _p(disparities),
+                                       C.c_double(float(unary_weight)), _p(base), _p(offsets), C.c_int(K), C.c_int64(E),
+                                       _p(conn, C.c_uint32), _p(unary), _p(q), _p(qprim), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return unary, q, qprim
+
+
+def _labels(labels, shape):
+    lab = np.asarray(labels)
+    if lab.ndim == 1 and lab.shape[0] == shape[0] * shape[1]:     # plan.result(): N values, column-major pixel order
+        lab = lab.reshape(shape[1], shape[0]).T
+    if lab.shape != tuple(shape):
+        raise StereoHipError("band_apply: labels must be N values or an H x W array of the map's size")
+    if not np.array_equal(lab, np.rint(lab)):
+        raise StereoHipError("band_apply: labels must be whole numbers")
+    return np.asfortranarray(lab, dtype=np.int32)
+
+
+def band_apply(base, labels, offsets):
+    """stereo_band_apply -> H x W: base + offsets[labels - 1].  `labels`: one based, N values as plan.result() returns
+    them or H x W."""
+    base = _map(base, "base")
+    H, W = base.shape
+    offsets = _vec(offsets, "offsets")
+    lab = _labels(labels, (H, W))
+    refined = np.zeros((H, W), order="F")
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_band_apply(_p(base), C.c_int(H), C.c_int(W), _p(lab, C.c_int32), _p(offsets),
+                                      C.c_int(offsets.shape[0]), _p(refined), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return refined
+
+
+# ---------------------------------------------------------------- device forms
+
+def _flat(t, what, dtype, n=None):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+        raise StereoHipError("%s must be a contiguous %s tensor on the device" % (what, dtype))
+    if t.device.index != torch.cuda.current_device():
+        raise StereoHipError("%s must be on the current device" % what)
+    if n is not None and t.numel() != n:
+        raise StereoHipError("%s must hold %d elements (got %d)" % (what, n, t.numel()))
+    return t
+
+
+def to_device_vector(v):
+    """A short host vector as a float64 tensor on the current device (what the device forms read as d_offsets)."""
+    import torch
+    return torch.from_numpy(np.array(v, dtype=np.float64)).cuda()
+
+
+def band_inputs_device(ncc, disparities, unary_weight, base, offsets, conn, layout=0, unary=None, q=None, qprim=None,
+                       bad=None, stream=None, d_disparities=None, d_offsets=None, check=True):
+    """stereo_band_inputs_device on torch tensors (module docstring), launched on `stream` (a torch stream or a raw
+    handle; default: torch's current stream).  `disparities` and `offsets` are host vectors; `d_disparities` /
+    `d_offsets`: their device copies, made here when not given.  check=True reads the count of pixels whose base is not
+    finite back (this waits for the stream) and raises; check=False leaves it in `bad` and does not wait.
+    -> (unary, q, qprim, bad): flat tensors K*N, K*E, K*E and the int32 counter."""
+    import torch
+    base = _device_map(base, "base", np.float64)
+    W, H = base.shape
+    disparities, offsets = _vec(disparities, "disparities"), _vec(offsets, "offsets")
+    D, K, N = disparities.shape[0], offsets.shape[0], H * W
+    ncc = _flat(ncc, "ncc", torch.float64, N * D)
+    conn = _flat(conn, "conn", torch.int32)
+    if conn.numel() % 2:
+        raise StereoHipError("conn must hold 2 E entries")
+    E = conn.numel() // 2
+    dev = base.device
+    made_here = d_disparities is None or d_offsets is None
+    d_disparities = to_device_vector(disparities) if d_disparities is None else _flat(d_disparities, "d_disparities", torch.float64, D)
+    d_offsets = to_device_vector(offsets) if d_offsets is None else _flat(d_offsets, "d_offsets", torch.float64, K)
+    if made_here and stream is not None:
+        torch.cuda.current_stream().synchronize()     # the copies ran on torch's current stream, the kernels will not
+    unary = torch.empty(max(K, 0) * N, dtype=torch.float64, device=dev) if unary is None else _flat(unary, "unary", torch.float64, K * N)
+    q = torch.empty(max(K, 0) * E, dtype=torch.float64, device=dev) if q is None else _flat(q, "q", torch.float64, K * E)
+    qprim = torch.empty(max(K, 0) * E, dtype=torch.float64, device=dev) if qprim is None else _flat(qprim, "qprim", torch.float64, K * E)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev) if bad is None else _flat(bad, "bad", torch.int32, 1)
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_band_inputs_device(vp(ncc), C.c_int(H), C.c_int(W), C.c_int(D), C.c_int(int(layout)), _p(disparities),
+                                              vp(d_disparities), C.c_double(float(unary_weight)), vp(base), _p(offsets),
+                                              vp(d_offsets), C.c_int(K), C.c_int64(E), vp(conn), vp(unary), vp(q), vp(qprim),
+                                              vp(bad), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    if check:
+        n = int(bad.item())
+        if n:
+            raise StereoHipError("band_inputs_device: base is not finite at %d pixel(s)" % n)
+    return unary, q, qprim, bad
+
+
+def band_apply_device(base, labels, offsets, refined=None, bad=None, stream=None, d_offsets=None, check=True):
+    """stereo_band_apply_device: `base` a (W, H) float64 map tensor, `labels` a (W, H) or flat int32 tensor, one based.
+    check=True reads the count of labels outside 1 .. K back and raises.  -> (refined (W, H), bad)."""
+    import torch
+    base = _device_map(base, "base", np.float64)
+    W, H = base.shape
+    offsets = _vec(offsets, "offsets")
+    K = offsets.shape[0]
+    labels = _flat(labels, "labels", torch.int32, H * W)
+    if d_offsets is None:
+        d_offsets = to_device_vector(offsets)
+        if stream is not None:
+            torch.cuda.current_stream().synchronize()
+    else:
+        d_offsets = _flat(d_offsets, "d_offsets", torch.float64, K)
+    refined = torch.empty((W, H), dtype=torch.float64, device=base.device) if refined is None else _device_map(refined, "refined", np.float64, base.shape)
+    bad = torch.zeros(1, dtype=torch.int32, device=base.device) if bad is None else _flat(bad, "bad", torch.int32, 1)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_band_apply_device(vp(base), C.c_int(H), C.c_int(W), vp(labels), _p(offsets), vp(d_offsets),
+                                             C.c_int(K), vp(refined), vp(bad), C.c_void_p(_stream(stream)), err,
+                                             C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    if check:
+        n = int(bad.item())
+        if n:
+            raise StereoHipError("band_apply_device: %d label(s) outside 1 .. %d" % (n, K))
+    return refined, bad
+
+
+# ---------------------------------------------------------------- levels
+
+def check_levels(levels):
+    """`levels` as a list of float64 vectors; at least one."""
+    levels = [_vec(l, "a level's offsets") for l in levels]
+    if not levels:
+        raise StereoHipError("refine_band: levels must hold at least one vector of offsets")
+    return levels
+
+
+class BandResult:
+    """refine_band's result: `dispmap` (H x W, the last level's refined map), `maps` (one per level) and per level
+    `energy`, `lower_bound`, `iterations`, `labels` (N, one based) and `paths` (the kernel family that ran,
+    TrwsPlan.path())."""
+
+    def __init__(self):
+        self.dispmap = None
+        self.maps, self.labels = [], []
+        self.energy, self.lower_bound, self.iterations, self.paths = [], [], [], []
+
+
+class BandProblem:
+    """One view's band problems on the device: the volume, the connectivity and the smoothness weights go up once;
+    build() makes a level's inputs from the current base and binds them to `plan`, apply() moves the base on."""
+
+    def __init__(self, ncc, disparities, unary_weight, base, conn, alphas=None, layout=0):
+        import torch
+        _lib.require_device()
+        base = _map(base, "base")
+        self.H, self.W = base.shape
+        vol, D = _volume(ncc, layout, self.H, self.W)
+        self.disparities = _vec(disparities, "disparities")
+        if self.disparities.shape[0] != D:
+            raise StereoHipError("refine_band: %d disparities for a volume of %d slices" % (self.disparities.shape[0], D))
+        self.layout, self.unary_weight = int(layout), float(unary_weight)
+        self.conn = _conn(conn)
+        self.N, self.E = self.H * self.W, self.conn.shape[1]
+        alphas = np.ones(self.E) if alphas is None else np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).reshape(-1))
+        if alphas.shape[0] != self.E:
+            raise StereoHipError("refine_band: alphas must hold one weight per edge")
+        self.d_ncc = torch.from_numpy(vol.reshape(-1, order="F")).cuda()
+        self.d_disparities = to_device_vector(self.disparities)
+        self.d_conn = torch.from_numpy(self.conn.reshape(-1, order="F").view(np.int32)).cuda()
+        self.d_alphas = torch.from_numpy(alphas).cuda()
+        self.d_base = torch.from_numpy(np.ascontiguousarray(base.T)).cuda()
+        self.offsets = self.d_offsets = self.d_unary = self.d_q = self.d_qprim = None
+
+    def build(self, offsets, plan, tol, zero_columns=None):
+        """The inputs of the level `offsets` around the current base, bound to `plan`.  zero_columns: a bool tensor (N,),
+        pixels whose unary column is set to zero."""
+        self.offsets = _vec(offsets, "offsets")
+        self.d_offsets = to_device_vector(self.offsets)
+        self.d_unary, self.d_q, self.d_qprim, _ = band_inputs_device(
+            self.d_ncc, self.disparities, self.unary_weight, self.d_base, self.offsets, self.d_conn, self.layout,
+            d_disparities=self.d_disparities, d_offsets=self.d_offsets)
+        if zero_columns is not None:
+            self.d_unary.view(self.N, -1)[zero_columns] = 0.0
+        import torch
+        torch.cuda.current_stream().synchronize()
+        plan.bind_device(self.d_unary.data_ptr(), self.d_alphas.data_ptr(), tol, d_q=self.d_q.data_ptr(),
+                         d_qprim=self.d_qprim.data_ptr(), keepalive=[self.d_unary, self.d_q, self.d_qprim, self.d_alphas])
+
+    def apply(self, labels):
+        """The base moved by the labels of the level built last -> the new base on the host, H x W."""
+        import torch
+        lab = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)).cuda()
+        self.d_base, _ = band_apply_device(self.d_base, lab, self.offsets, d_offsets=self.d_offsets)
+        return self.d_base.cpu().numpy().T
+
+
+def refine_band(ncc, disparities, unary_weight, base, kernel, tol, levels, maxiter, max_relgap, alphas=None, layout=0,
+                conn=None):
+    """Refines the map `base` level by level: for each vector of offsets in `levels` the band problem around the current
+    map is built on the device (stereo_band_inputs_device), bound to a TrwsPlan(kernel, K, N, conn) -- one plan per
+    distinct K -- iterated up to `maxiter` times (`max_relgap` as in trws) and applied (stereo_band_apply_device); the
+    refined map is the next level's base.  The volume goes to the device once; nothing K x N or K x E touches the host.
+    conn: 2 x E zero based, default the image grid (construct_neighborhood).  -> BandResult."""
+    levels = check_levels(levels)
+    base = _map(base, "base")
+    H, W = base.shape
+    conn = T.construct_neighborhood(H, W) if conn is None else conn
+    prob = BandProblem(ncc, disparities, unary_weight, base, conn, alphas, layout)
+    out = BandResult()
+    plans = {}
+    try:
+        for offsets in levels:
+            K = offsets.shape[0]
+            if K not in plans:
+                plans[K] = TrwsPlan(int(kernel), K, prob.N, prob.conn)
+            plan = plans[K]
+            prob.build(offsets, plan, tol)
+            plan.iterate(maxiter, max_relgap)
+            labels, en, lb, it = plan.result()
+            out.paths.append(plan.path())
+            out.labels.append(labels); out.energy.append(en); out.lower_bound.append(lb); out.iterations.append(it)
+            out.maps.append(prob.apply(labels))
+        out.dispmap = out.maps[-1]
+    finally:
+        for plan in plans.values():
+            plan.close()
+    return out

@@ -142,14 +142,20 @@ def flip_volume(vol, H, W):
     return np.asfortranarray(vol.reshape((D, H, W), order="F")[:, :, ::-1].reshape((D, H * W), order="F"))
 
 
-def pair_unaries(images, disparities, unary_weight):
-    """The two D x N unary volumes unary_weight * (1 - ncc) of a pair: the left-referenced one as dispmap_ncc builds
-    it, the right-referenced one by the mirror: the same volume function on the horizontally flipped
-    images in swapped order, flipped back."""
+def pair_volumes(images, disparities):
+    """The two D x N NCC volumes of a pair: the left-referenced one as dispmap_ncc builds it, the right-referenced one
+    by the mirror: the same volume function on the horizontally flipped images in swapped order, flipped
+    back."""
     im0, im1 = (np.asarray(im, dtype=np.float64) for im in images[:2])
     H, W = im0.shape[:2]
     left = T.ncc_volume(im0, im1, disparities, 2, layout=1)
     right = flip_volume(T.ncc_volume(im1[:, ::-1], im0[:, ::-1], disparities, 2, layout=1), H, W)
+    return left, right
+
+
+def pair_unaries(images, disparities, unary_weight, volumes=None):
+    """The two D x N unary volumes unary_weight * (1 - ncc) of a pair, from pair_volumes."""
+    left, right = pair_volumes(images, disparities) if volumes is None else volumes
     return unary_weight * (1.0 - left), unary_weight * (1.0 - right)
 
 
@@ -162,11 +168,13 @@ def occlusion_aware_unary(unary, status):
 
 class ViewResult:
     """One view of solve_pair_ncc: `labels` (N, one based), `dispmap`, `status`, `residual`, `filled`, `source`
-    (H x W), and per pass `energy`, `lower_bound`, `iterations` (lists: the first solve, then the refine pass)."""
+    (H x W), and per pass `energy`, `lower_bound`, `iterations` (lists: the first solve, then the refine pass, then one
+    entry per band level).  After band levels `labels` are the last level's band labels and `dispmap`, `status`,
+    `residual`, `filled` and `source` those of the last level's refined map; `maps` keeps the map of every pass."""
 
     def __init__(self):
         self.labels = self.dispmap = self.status = self.residual = self.filled = self.source = None
-        self.energy, self.lower_bound, self.iterations = [], [], []
+        self.energy, self.lower_bound, self.iterations, self.maps = [], [], [], []
 
 
 class PairResult:
@@ -181,12 +189,17 @@ class PairResult:
         return self.left, self.right
 
 
-def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_relgap, check_tol=1.0, refine_iters=0):
+def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_relgap, check_tol=1.0, refine_iters=0,
+                   band_levels=None):
     """Both views of a rectified pair: two NCC unary volumes, two TRW-S plans on the image grid with the shared
     positions `disparities`, iterated as one TrwsBatch; labels to maps; each map checked against the other and filled.
     refine_iters > 0: per view, the solver state is saved, the unary columns of the occluded pixels are zeroed and
     uploaded (which resets the plan), the state is loaded -- the warm start with other unaries of DESIGN.md 4.10 --
-    and the batch runs refine_iters more iterations; then check and fill again."""
+    and the batch runs refine_iters more iterations; then check and fill again.
+    band_levels: a sequence of offset vectors.  After the passes above, for every level both views build
+    the band problem around their map on the device, from their own volume, and run up to `maxiter` iterations as a
+    two-member TrwsBatch; the refined maps are checked with check_tol and filled.  With refine_iters > 0 the unary
+    columns of the pixels the preceding check found occluded are zeroed in the band as well."""
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
     if len(images) != 2:
         raise StereoHipError("solve_pair_ncc: images must be the two views of a pair, left first (got %d)" % len(images))
@@ -200,18 +213,24 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
     out = PairResult()
     clock = time.perf_counter
     t0 = clock()
-    unaries = pair_unaries(images, disparities, unary_weight)
+    if band_levels is not None:
+        from . import band
+        band_levels = band.check_levels(band_levels)
+    volumes = pair_volumes(images, disparities)
+    unaries = pair_unaries(images, disparities, unary_weight, volumes)
     out.times["volumes"] = clock() - t0
     conn = T.construct_neighborhood(H, W)
     alphas = np.ones(conn.shape[1])
     plans = [TrwsPlan(int(kernel), K, N, conn) for _ in range(2)]
+    band_plans = {}
 
-    def collect(stage):
+    def collect(stage, solved=None, to_map=None):
         t = clock()
-        for plan, view in zip(plans, out.views):
+        for i, (plan, view) in enumerate(zip(solved or plans, out.views)):
             view.labels, en, lb, it = plan.result()
             view.energy.append(en); view.lower_bound.append(lb); view.iterations.append(it)
-            view.dispmap = disparities[view.labels.astype(np.int64) - 1].reshape(W, H).T
+            view.dispmap = to_map(i, view.labels) if to_map else disparities[view.labels.astype(np.int64) - 1].reshape(W, H).T
+            view.maps.append(view.dispmap)
         for view, other, direction in ((out.left, out.right, 1), (out.right, out.left, -1)):
             view.status, view.residual = lr_check(view.dispmap, other.dispmap, direction, check_tol)
             view.filled, view.source = lr_fill(view.dispmap, view.status)
@@ -235,7 +254,23 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
                 batch.iterate(refine_iters, max_relgap)
             out.times["refine"] = clock() - t0
             collect("refine_check_fill")
+        if band_levels is not None:
+            import torch
+            problems = [band.BandProblem(vol, disparities, unary_weight, view.dispmap, conn, alphas, layout=1)
+                        for vol, view in zip(volumes, out.views)]
+            for level, offsets in enumerate(band_levels):
+                t0 = clock()
+                Kb = offsets.shape[0]
+                if Kb not in band_plans:
+                    band_plans[Kb] = [TrwsPlan(int(kernel), Kb, N, conn) for _ in range(2)]
+                for prob, plan, view in zip(problems, band_plans[Kb], out.views):
+                    occluded = torch.from_numpy(view.status.T.reshape(-1) == OCCLUDED).cuda() if refine_iters > 0 else None
+                    prob.build(offsets, plan, tol, zero_columns=occluded)
+                with TrwsBatch(band_plans[Kb]) as batch:
+                    batch.iterate(maxiter, max_relgap)
+                out.times["band_%d" % (level + 1)] = clock() - t0
+                collect("band_%d_check_fill" % (level + 1), band_plans[Kb], lambda i, labels: problems[i].apply(labels))
     finally:
-        for plan in plans:
+        for plan in plans + [p for pair in band_plans.values() for p in pair]:
             plan.close()
     return out

@@ -1,0 +1,310 @@
+// Band refinement around a solved disparity map (the definition: include/stereo_hip.h).
+// From a map `base` and K offsets, the TRW-S inputs of the problem whose label k at pixel i means the
+// fronto-parallel plane [0 0 1 -(base_i + offsets_k)]: unary (K x N) by the NCC sampler of ncc_sample.h,
+// q / qprim (K x E) by the plane -> disparity rule, and the map a labelling selects.
+//
+// All three output arrays are label fastest, and a lane is one (pixel, k) or (edge, k) element of them in
+// storage order: every wave stores 512 consecutive bytes.  The K lanes of a pixel sample neighbouring
+// slices of one volume column; in the label-fastest volume (layout 1) those are the same cache lines, so
+// the column's span comes from memory once and the lanes' three loads each are served from cache.  LDS holds the
+// D slice positions of the unary kernel and nothing else.
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "common.h"
+#include "ncc_sample.h"
+#include "stereo_hip.h"
+
+namespace {
+
+using stereo::fail;
+using stereo::HipError;
+
+constexpr int kTB = 256;
+constexpr int kMaxOffsets = 512;
+constexpr unsigned kMaxGrid = 1u << 20;   // blocks of one launch; a block strides over what is left
+
+// Element t = item * K + k of a K x M label-fastest array, for the 256 consecutive t of a block: the 64-bit
+// division is done once per block on uniform values, a lane divides a number below 256 + K.
+struct BandIndex {
+  int64_t item;
+  int k;
+};
+__device__ __forceinline__ BandIndex band_index(int64_t block_first, int K) {
+  const int64_t item0 = block_first / K;
+  const uint32_t local = (uint32_t)(block_first - item0 * K) + threadIdx.x;
+  const uint32_t up = local / (uint32_t)K;
+  return {item0 + up, (int)(local - up * (uint32_t)K)};
+}
+
+// The disparity of label k at a pixel whose base is b: plane_disp of [0 0 1 -(b + delta)].  The plane's
+// s = 0 x + 0 y is +0 at every pixel, so no pixel coordinate is formed; the value is b + delta, with the
+// sign of zero that the plane gives (-0 for b + delta == 0).
+__device__ __forceinline__ double band_disp(double b, double delta) {
+  const double pl[4] = {0.0, 0.0, 1.0, -(b + delta)};
+  return stereo::plane_disp(pl, 1.0, 1.0);
+}
+
+// kStageSlices: the block copies the D slice positions into LDS first.  The nearest-slice search and the parabola read
+// them a dozen times per lane, each read waiting for the one before (bisection); from LDS that chain is several
+// times shorter than from the vector cache (DESIGN.md 6.2 has the measurement that asked for it).
+constexpr int kMaxStagedSlices = 4096;   // 32 KiB of LDS; beyond it the kernel reads the slices where they are
+template <bool kStageSlices>
+__global__ __launch_bounds__(kTB) void band_unary_kernel(const double *__restrict__ ncc, int64_t Npx, int D, int layout,
+                                                        const double *__restrict__ dv, double dmin, double dmax,
+                                                        double unary_weight, const double *__restrict__ base,
+                                                        const double *__restrict__ offsets, int K, int ascending,
+                                                        double *__restrict__ U, int32_t *bad) {
+  extern __shared__ double staged_slices[];
+  const double *slices = dv;
+  if (kStageSlices) {
+    for (int i = threadIdx.x; i < D; i += kTB) staged_slices[i] = dv[i];
+    __syncthreads();
+    slices = staged_slices;
+  }
+  const int64_t total = Npx * K;
+  for (int64_t first = (int64_t)blockIdx.x * kTB; first < total; first += (int64_t)gridDim.x * kTB) {
+    const BandIndex ix = band_index(first, K);
+    if (ix.item >= Npx) continue;
+    const double b = base[ix.item];
+    if (bad && ix.k == 0 && !isfinite(b)) atomicAdd(bad, 1);
+    const double disp = band_disp(b, offsets[ix.k]);
+    U[first + threadIdx.x] = stereo::ncc_unary_at(ncc, Npx, D, layout, ix.item, slices, dmin, dmax, unary_weight, disp, ascending);
+  }
+}
+
+// q(k, e) = disparity of label k at the edge's second pixel, qprim(k, e) at its first (dispmap_super.m:177-183, the
+// order trws_positions_kernel writes).  An edge that names a pixel outside 0 .. N - 1 reads nothing and gets NaN.
+// This kernel writes 16 of every 18 bytes of a band problem.  A block takes kPosPerThread * 256 consecutive elements,
+// a thread kPosPerThread of them 256 apart (each wave instruction still stores 512 consecutive bytes); every load
+// is unconditional at a clamped address, so the loads of a thread's elements are in flight together, and only the
+// stores are predicated (DESIGN.md 6.1 records what a predicate per load cost the fill kernel).
+constexpr int kPosPerThread = 4;
+__global__ __launch_bounds__(kTB) void band_positions_kernel(int64_t E, int K, int64_t Npx, const uint32_t *__restrict__ conn,
+                                                            const double *__restrict__ base,
+                                                            const double *__restrict__ offsets, double *__restrict__ q,
+                                                            double *__restrict__ qprim) {
+  const int64_t total = E * K;
+  constexpr int64_t kChunk = (int64_t)kTB * kPosPerThread;
+  const double nan = __builtin_nan("");
+  for (int64_t first = (int64_t)blockIdx.x * kChunk; first < total; first += (int64_t)gridDim.x * kChunk) {
+    const int64_t item0 = first / K;                       // (uniform: once per block and chunk)
+    const uint32_t rem0 = (uint32_t)(first - item0 * K);
+    uint32_t i1[kPosPerThread], i2[kPosPerThread];
+    double delta[kPosPerThread], b1[kPosPerThread], b2[kPosPerThread];
+    bool live[kPosPerThread];
+#pragma unroll
+    for (int u = 0; u < kPosPerThread; ++u) {
+      const uint32_t off = (uint32_t)u * kTB + threadIdx.x;
+      live[u] = first + off < total;
+      const uint32_t local = rem0 + off, up = local / (uint32_t)K;
+      const int64_t e = live[u] ? item0 + up : 0;
+      i1[u] = conn[2 * e];
+      i2[u] = conn[2 * e + 1];
+      delta[u] = offsets[local - up * (uint32_t)K];
+    }
+#pragma unroll
+    for (int u = 0; u < kPosPerThread; ++u) {
+      b1[u] = base[i1[u] < Npx ? i1[u] : 0];
+      b2[u] = base[i2[u] < Npx ? i2[u] : 0];
+    }
+#pragma unroll
+    for (int u = 0; u < kPosPerThread; ++u) {
+      if (!live[u]) continue;
+      const int64_t t = first + (int64_t)u * kTB + threadIdx.x;
+      q[t] = i2[u] < Npx ? band_disp(b2[u], delta[u]) : nan;
+      qprim[t] = i1[u] < Npx ? band_disp(b1[u], delta[u]) : nan;
+    }
+  }
+}
+
+// refined_i = base_i + offsets_{label_i - 1}; a label outside 1 .. K gives NaN and counts in `bad`.
+__global__ __launch_bounds__(kTB) void band_apply_kernel(int64_t Npx, int K, const double *__restrict__ base,
+                                                        const int32_t *__restrict__ labels,
+                                                        const double *__restrict__ offsets, double *__restrict__ refined,
+                                                        int32_t *bad) {
+  for (int64_t i = (int64_t)blockIdx.x * kTB + threadIdx.x; i < Npx; i += (int64_t)gridDim.x * kTB) {
+    const int32_t l = labels[i];
+    const bool in = l >= 1 && l <= K;
+    if (bad && !in) atomicAdd(bad, 1);
+    refined[i] = in ? base[i] + offsets[l - 1] : __builtin_nan("");
+  }
+}
+
+// ---------------------------------------------------------------- argument checks (no device call)
+
+int check_offsets(const std::string &what, const double *offsets, int K, char *err, size_t errcap) {
+  if (K < 1 || K > kMaxOffsets)
+    return fail(what + ": the number of offsets must be 1 .. " + std::to_string(kMaxOffsets) + " (got " + std::to_string(K) + ")", err, errcap);
+  if (!offsets) return fail(what + ": offsets must not be NULL", err, errcap);
+  bool zero = false;
+  for (int k = 0; k < K; ++k) {
+    if (!std::isfinite(offsets[k])) return fail(what + ": offsets[" + std::to_string(k) + "] is not finite", err, errcap);
+    if (k > 0 && !(offsets[k] > offsets[k - 1]))
+      return fail(what + ": offsets must be strictly ascending (offsets[" + std::to_string(k) + "] <= offsets[" + std::to_string(k - 1) + "])", err, errcap);
+    zero = zero || offsets[k] == 0.0;
+  }
+  if (!zero) return fail(what + ": offsets must contain 0.0 (the base labelling must be one of the band's)", err, errcap);
+  return 0;
+}
+
+int check_sizes(const std::string &what, int H, int W, char *err, size_t errcap) {
+  if (H < 1 || W < 1) return fail(what + ": H and W must be at least 1", err, errcap);
+  if ((int64_t)H * (int64_t)W >= ((int64_t)1 << 31)) return fail(what + ": H * W must be below 2^31", err, errcap);
+  return 0;
+}
+
+int check_inputs(const std::string &what, const void *ncc, int H, int W, int D, int layout, const double *disparities,
+                 const void *base, const double *offsets, int K, int64_t E, const void *conn, const void *unary,
+                 const void *q, const void *qprim, char *err, size_t errcap) {
+  if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
+  if (D < 1) return fail(what + ": D must be at least 1", err, errcap);
+  if (layout != 0 && layout != 1) return fail(what + ": layout must be 0 (H x W x D) or 1 (D x N, label fastest)", err, errcap);
+  if (E < 0) return fail(what + ": E must not be negative", err, errcap);
+  if (!ncc || !disparities || !base || !unary) return fail(what + ": ncc, disparities, base and unary must not be NULL", err, errcap);
+  if (E > 0 && (!conn || !q || !qprim)) return fail(what + ": conn, q and qprim must not be NULL", err, errcap);
+  return check_offsets(what, offsets, K, err, errcap);
+}
+
+int check_apply(const std::string &what, const void *base, int H, int W, const void *labels, const double *offsets, int K,
+                const void *refined, char *err, size_t errcap) {
+  if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
+  if (!base || !labels || !refined) return fail(what + ": base, labels and refined must not be NULL", err, errcap);
+  return check_offsets(what, offsets, K, err, errcap);
+}
+
+int check_base(const std::string &what, const double *base, int H, int W, char *err, size_t errcap) {
+  for (int64_t i = 0; i < (int64_t)H * W; ++i)
+    if (!std::isfinite(base[i]))
+      return fail(what + ": base is not finite at pixel (row " + std::to_string(i % H) + ", column " + std::to_string(i / H) + ")", err, errcap);
+  return 0;
+}
+
+template <class F>
+int guarded(const char *what, char *err, size_t errcap, F f) {
+  if (stereo_hip_device_count() < 1)
+    return fail(std::string(what) + ": no HIP device available (the HIP path has no CPU fallback)", err, errcap);
+  try {
+    f();
+    return 0;
+  } catch (const HipError &e) {
+    return fail(e.msg, err, errcap);
+  } catch (const std::exception &e) {
+    return fail(std::string(what) + ": " + e.what(), err, errcap);
+  }
+}
+
+unsigned grid_for(int64_t elements) {
+  const int64_t b = (elements + kTB - 1) / kTB;
+  return (unsigned)(b < 1 ? 1 : b > (int64_t)kMaxGrid ? (int64_t)kMaxGrid : b);
+}
+
+// `disparities` / `offsets`: the host vectors (checked; min, max and the order of the slices come from them);
+// `d_disparities` / `d_offsets`: the same values in device memory, which the kernels read
+void launch_inputs(const double *ncc, int H, int W, int D, int layout, const double *disparities,
+                   const double *d_disparities, double unary_weight, const double *base, const double *d_offsets, int K,
+                   int64_t E, const uint32_t *conn, double *unary, double *q, double *qprim, int32_t *bad, hipStream_t s) {
+  const int64_t Npx = (int64_t)H * W;
+  double dmin = disparities[0], dmax = disparities[0];
+  bool ascending = disparities[0] == disparities[0];
+  for (int i = 1; i < D; ++i) {
+    dmin = disparities[i] < dmin ? disparities[i] : dmin;
+    dmax = disparities[i] > dmax ? disparities[i] : dmax;
+    ascending = ascending && disparities[i] > disparities[i - 1];
+  }
+  if (bad) STEREO_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int32_t), s));
+  if (D <= kMaxStagedSlices)
+    hipLaunchKernelGGL(band_unary_kernel<true>, dim3(grid_for(Npx * K)), dim3(kTB), (size_t)D * sizeof(double), s, ncc, Npx, D,
+                       layout, d_disparities, dmin, dmax, unary_weight, base, d_offsets, K, ascending ? 1 : 0, unary, bad);
+  else
+    hipLaunchKernelGGL(band_unary_kernel<false>, dim3(grid_for(Npx * K)), dim3(kTB), 0, s, ncc, Npx, D, layout, d_disparities,
+                       dmin, dmax, unary_weight, base, d_offsets, K, ascending ? 1 : 0, unary, bad);
+  STEREO_HIP_CHECK(hipGetLastError());
+  if (E > 0) {
+    hipLaunchKernelGGL(band_positions_kernel, dim3(grid_for((E * K + kPosPerThread - 1) / kPosPerThread)), dim3(kTB), 0, s, E, K, Npx, conn, base, d_offsets, q, qprim);
+    STEREO_HIP_CHECK(hipGetLastError());
+  }
+}
+
+void launch_apply(const double *base, int H, int W, const int32_t *labels, const double *d_offsets, int K, double *refined,
+                  int32_t *bad, hipStream_t s) {
+  const int64_t Npx = (int64_t)H * W;
+  if (bad) STEREO_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int32_t), s));
+  hipLaunchKernelGGL(band_apply_kernel, dim3(grid_for(Npx)), dim3(kTB), 0, s, Npx, K, base, labels, d_offsets, refined, bad);
+  STEREO_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+int stereo_band_max_offsets(void) { return kMaxOffsets; }
+
+int stereo_band_inputs_device(const double *ncc, int H, int W, int D, int layout, const double *disparities,
+                              const double *d_disparities, double unary_weight, const double *base, const double *offsets,
+                              const double *d_offsets, int K, int64_t E, const uint32_t *conn, double *unary, double *q,
+                              double *qprim, int32_t *bad, void *stream, char *err, size_t errcap) {
+  if (int rc = check_inputs("stereo_band_inputs_device", ncc, H, W, D, layout, disparities, base, offsets, K, E, conn, unary, q,
+                            qprim, err, errcap))
+    return rc;
+  if (!d_disparities || !d_offsets) return fail("stereo_band_inputs_device: d_disparities and d_offsets must not be NULL", err, errcap);
+  return guarded("stereo_band_inputs_device", err, errcap, [&] {
+    launch_inputs(ncc, H, W, D, layout, disparities, d_disparities, unary_weight, base, d_offsets, K, E, conn, unary, q, qprim,
+                  bad, (hipStream_t)stream);
+  });
+}
+
+int stereo_band_apply_device(const double *base, int H, int W, const int32_t *labels, const double *offsets,
+                             const double *d_offsets, int K, double *refined, int32_t *bad, void *stream, char *err,
+                             size_t errcap) {
+  if (int rc = check_apply("stereo_band_apply_device", base, H, W, labels, offsets, K, refined, err, errcap)) return rc;
+  if (!d_offsets) return fail("stereo_band_apply_device: d_offsets must not be NULL", err, errcap);
+  return guarded("stereo_band_apply_device", err, errcap,
+                 [&] { launch_apply(base, H, W, labels, d_offsets, K, refined, bad, (hipStream_t)stream); });
+}
+
+int stereo_band_inputs(const double *ncc, int H, int W, int D, int layout, const double *disparities, double unary_weight,
+                       const double *base, const double *offsets, int K, int64_t E, const uint32_t *conn, double *unary,
+                       double *q, double *qprim, char *err, size_t errcap) {
+  const std::string what = "stereo_band_inputs";
+  if (int rc = check_inputs(what, ncc, H, W, D, layout, disparities, base, offsets, K, E, conn, unary, q, qprim, err, errcap))
+    return rc;
+  if (int rc = check_base(what, base, H, W, err, errcap)) return rc;
+  const size_t n = (size_t)H * W;
+  for (int64_t e = 0; e < 2 * E; ++e)
+    if (conn[e] >= n) return fail(what + ": conn names a pixel outside 0 .. H*W - 1 (edge " + std::to_string(e / 2) + ")", err, errcap);
+  return guarded("stereo_band_inputs", err, errcap, [&] {
+    stereo::DevBuf<double> dn, db, dd, doff, du, dq, dqp;
+    stereo::DevBuf<uint32_t> dc;
+    dn.upload(ncc, n * D); db.upload(base, n); dd.upload(disparities, D); doff.upload(offsets, K); du.alloc(n * K);
+    if (E > 0) { dc.upload(conn, 2 * (size_t)E); dq.alloc((size_t)E * K); dqp.alloc((size_t)E * K); }
+    launch_inputs(dn.p, H, W, D, layout, disparities, dd.p, unary_weight, db.p, doff.p, K, E, dc.p, du.p, dq.p, dqp.p, nullptr,
+                  nullptr);
+    STEREO_HIP_CHECK(hipMemcpy(unary, du.p, n * K * sizeof(double), hipMemcpyDeviceToHost));
+    if (E > 0) {
+      STEREO_HIP_CHECK(hipMemcpy(q, dq.p, (size_t)E * K * sizeof(double), hipMemcpyDeviceToHost));
+      STEREO_HIP_CHECK(hipMemcpy(qprim, dqp.p, (size_t)E * K * sizeof(double), hipMemcpyDeviceToHost));
+    }
+  });
+}
+
+int stereo_band_apply(const double *base, int H, int W, const int32_t *labels, const double *offsets, int K, double *refined,
+                      char *err, size_t errcap) {
+  const std::string what = "stereo_band_apply";
+  if (int rc = check_apply(what, base, H, W, labels, offsets, K, refined, err, errcap)) return rc;
+  if (int rc = check_base(what, base, H, W, err, errcap)) return rc;
+  const size_t n = (size_t)H * W;
+  for (size_t i = 0; i < n; ++i)
+    if (labels[i] < 1 || labels[i] > K)
+      return fail(what + ": label " + std::to_string(labels[i]) + " at pixel " + std::to_string(i) + " is outside 1 .. " + std::to_string(K), err, errcap);
+  return guarded("stereo_band_apply", err, errcap, [&] {
+    stereo::DevBuf<double> db, doff, out;
+    stereo::DevBuf<int32_t> dl;
+    db.upload(base, n); dl.upload(labels, n); doff.upload(offsets, K); out.alloc(n);
+    launch_apply(db.p, H, W, dl.p, doff.p, K, out.p, nullptr, nullptr);
+    STEREO_HIP_CHECK(hipMemcpy(refined, out.p, n * sizeof(double), hipMemcpyDeviceToHost));
+  });
+}
+
+}  // extern "C"

@@ -354,6 +354,10 @@ class dispmap_super:
         self.filled_dispmap, self.filled_source = consistency.lr_fill(d, self.consistency) if fill else (None, None)
         return self.consistency, self.filled_dispmap
 
+    def refine_band(self, levels, maxiter=None):
+        raise StereoHipError("refine_band: %s does not take its unary from the NCC sampler; band refinement is defined "
+                             "for dispmap_ncc" % type(self).__name__)
+
 
 class dispmap_ncc(dispmap_super):
     """dispmap_ncc.m"""
@@ -426,6 +430,20 @@ class dispmap_ncc(dispmap_super):
     def unary_volume(self):
         """H x W x D: unary_weight * (1 - ncc), the unary of every fronto-parallel label, in the image's own columns."""
         return self._unary_weight * (1.0 - (self.ncc[:, ::-1] if self._mirrored else self.ncc))
+
+    def refine_band(self, levels, maxiter=None):
+        """Sub-pixel refinement of the current map (no reference counterpart): for every vector of offsets in
+        `levels` (strictly ascending, containing 0) TRW-S chooses per pixel among current disparity + offset, with this
+        object's volume, unary weight, kernel, tolerance, smoothness weights and max_relgap, up to `maxiter` (default
+        self.maxiter) iterations per level.  The result goes in through set_disparity; returns band.refine_band's
+        BandResult (its maps are in the object's internal columns: flipped for a mirrored object)."""
+        from . import band
+        base = self.disparitymap_from_assignment(self.assignment).reshape(self.sz[1], self.sz[0]).T    # internal columns
+        out = band.refine_band(self.ncc, self.disparities, self._unary_weight, base, self._kernel, self._tol, levels,
+                               self.maxiter if maxiter is None else maxiter, self._max_relgap, alphas=self.smooth_weights,
+                               conn=self.neighborhood)
+        self.set_disparity(self._unflip(out.dispmap))
+        return out
 
     # ---- proposals (dispmap_ncc.m:48-92).  Host side: a few dozen points and 3 x 3 SVDs per
     # proposal; MATLAB's svd is outside the reference tree, so this mirrors the arithmetic with
