@@ -109,7 +109,7 @@ def test_improve_matches_reference(hip, oracle):
 
 def test_improve_confined_relabelling_changes_nothing(hip, oracle, monkeypatch):
     """The relabellings inside an Improve step start from the heights of the step's starting flow and only
-    look at the tiles the step touched (qpbo.hip, `confined` / `local`); STEREO_HIP_QPBO_CONFINED=0 keeps the
+    look at the tiles the step touched (qpbo_maxflow.hip, `confined` / `local`); STEREO_HIP_QPBO_CONFINED=0 keeps the
     search from scratch over all nodes.  Same fixpoint: labels, energy and bound bit for bit, on problems
     with both kinds of ambiguous node (neither / both sides connected) and on one with several tiles."""
     if not oracle.have_ref_qpbo():
@@ -231,7 +231,7 @@ def test_large_grid_move_matches_reference(hip, oracle):
 
 
 def test_round_numbers_wrap(hip, monkeypatch):
-    """The tiled rounds' marks and the hx words carry round numbers; long launches wrap them (qpbo.hip: mark_all_dirty).
+    """The tiled rounds' marks and the hx words carry round numbers; long launches wrap them (qpbo_maxflow.hip: mark_all_dirty).
     STEREO_HIP_QPBO_WRAP_AT makes the wrap come after a handful of rounds: moves that need many tiled rounds -- a
     frustrated problem with Improve, a large move with supermodular terms -- must give the labels of the default run."""
     import ctypes
@@ -252,6 +252,38 @@ def test_round_numbers_wrap(hip, monkeypatch):
             plan.close()
         for o in out[1:]:
             assert np.array_equal(o[0], out[0][0]) and o[3] == out[0][3] and o[1] == out[0][1]
+
+
+def test_weak_persistency_full_and_compact_agree(hip, monkeypatch):
+    """Weak persistency runs on the free subgraph gathered on the device, or (STEREO_HIP_QPBO_WEAK_FULL, and graphs with
+    long arc lists) on the whole residual network fetched to the host: one DFS pass over two views of the same arcs
+    (qpbo_graph.cpp), so labels, unlabelled count, energy and bound are equal bit for bit -- on a frustrated problem, on a
+    fusion move, and with Improve behind it.  On the frustrated problem the pass must label variables that strong
+    persistency (tests/golden/rd_runs.npz, decided by the energy alone) leaves open."""
+    import ctypes
+    import os
+    from stereo_amd.rd import RdPlan
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rd_runs.npz"))
+    glass = glass_problem(208, 20, 24, 3.0, True)
+    cases = [(glass, False), (fusion_problem(204, 20, 25, kernel=1, tol=8.0, integer=True), False), (glass, True)]
+    for k, (p, improve) in enumerate(cases):
+        args = (p["U0"], p["U1"], p["E00"], p["E01"], p["E10"], p["E11"])
+        plan = RdPlan(p["U0"].shape[0], p["conn"].T)
+        out = []
+        for full in (None, "1"):
+            if full is None:
+                monkeypatch.delenv("STEREO_HIP_QPBO_WEAK_FULL", raising=False)
+            else:
+                monkeypatch.setenv("STEREO_HIP_QPBO_WEAK_FULL", full)
+            ctypes.CDLL(None).srand(7)
+            out.append(plan.solve(*args, improve=improve))
+        monkeypatch.delenv("STEREO_HIP_QPBO_WEAK_FULL")
+        plan.close()
+        assert np.array_equal(out[0][0], out[1][0]), k
+        assert out[0][3] == out[1][3] and out[0][1] == out[1][1] and out[0][2] == out[1][2], k
+        if k == 0:
+            opened = g["glass_int_20x24_strong"] < 0
+            assert opened.sum() > 0 and np.any(out[0][0][opened] >= 0)
 
 
 def test_gateway_keeps_the_plan_of_the_last_connectivity(hip, oracle, monkeypatch):

@@ -5,7 +5,8 @@ usage: isa_compare.py DIR_A DIR_B      (csrc/_build/ as build.sh leaves it, or t
 Pairs the *-hip-amdgcn-amd-amdhsa-gfx950.s files of the two directories, splits each at its function symbols (kernels
 and the device functions that are not inlined), drops .file / .loc / .ident and comment lines, and prints per function
 `same` or the first differing line, with the SGPR / VGPR / spill / scratch / LDS figures of both sides.  Exit status 1
-if anything differs or a file or symbol exists on one side only.
+if anything differs or a symbol exists on one side only.  Files that exist on one side only (a source file was split
+or renamed) are not an error by themselves: their functions are paired by demangled name across files.
 
 This is how a refactor of the sweep kernel files is checked: textual sharing must leave every kernel
 `same`.  Local labels (.LBB<function number>_<block>, ...) are renumbered in order of appearance: the number of a
@@ -48,35 +49,60 @@ def functions(txt):
     return out
 
 
+def compare(where, sym_a, sym_b, fa, fb, ra, rb):
+    """one function of either side; 1 if it differs.  Its own symbol is written <self>: a kernel whose argument types
+    changed namespace has another mangled name and the same code."""
+    name = kr.demangle(sym_a)[:140]
+    fig = [kr.figures(r[s]) if s in r else "(device function)" for r, s in ((ra, sym_a), (rb, sym_b))]
+    la, lb = [l.replace(sym_a, "<self>") for l in fa[sym_a]], [l.replace(sym_b, "<self>") for l in fb[sym_b]]
+    if la == lb and fig[0] == fig[1]:
+        print("%s: %s: same  [%s]" % (where, name, fig[0]))
+        return 0
+    i = next((i for i, (x, y) in enumerate(zip(la, lb)) if x != y), min(len(la), len(lb)))
+    print("%s: %s: DIFFERS at line %d of %d / %d" % (where, name, i, len(la), len(lb)))
+    print("    a: %s\n    b: %s" % (la[i].strip() if i < len(la) else "(end)", lb[i].strip() if i < len(lb) else "(end)"))
+    print("    a: %s\n    b: %s" % (fig[0], fig[1]))
+    return 1
+
+
+def plain_name(sym):
+    """what pairs a symbol across files: its demangled name without the anonymous namespaces"""
+    return kr.demangle(sym).replace("(anonymous namespace)::", "")
+
+
 def main(dir_a, dir_b):
     files = [{os.path.basename(f) for f in glob.glob(os.path.join(d, "*" + SUFFIX))} for d in (dir_a, dir_b)]
-    bad = 0
-    for f in sorted(files[0] ^ files[1]):
-        print("%s: only in %s" % (f, dir_a if f in files[0] else dir_b))
-        bad += 1
-    total = 0
+    bad = total = 0
     for f in sorted(files[0] & files[1]):
         txt = [open(os.path.join(d, f)).read() for d in (dir_a, dir_b)]
         fa, fb = functions(txt[0]), functions(txt[1])
         ra, rb = kr.kernels(txt[0]), kr.kernels(txt[1])
         for sym in sorted(set(fa) | set(fb)):
             total += 1
-            name = kr.demangle(sym)[:140]
             if sym not in fa or sym not in fb:
-                print("%s: %s: only in %s" % (f[:-len(SUFFIX)], name, dir_a if sym in fa else dir_b))
+                print("%s: %s: only in %s" % (f[:-len(SUFFIX)], kr.demangle(sym)[:140], dir_a if sym in fa else dir_b))
                 bad += 1
                 continue
-            fig = [kr.figures(r[sym]) if sym in r else "(device function)" for r in (ra, rb)]
-            la, lb = fa[sym], fb[sym]
-            if la == lb and fig[0] == fig[1]:
-                print("%s: %s: same  [%s]" % (f[:-len(SUFFIX)], name, fig[0]))
-                continue
+            bad += compare(f[:-len(SUFFIX)], sym, sym, fa, fb, ra, rb)
+    # files of one side only (a file was split or renamed): their functions are paired by name, whatever file they are in
+    loose = []
+    for d, only in ((dir_a, files[0] - files[1]), (dir_b, files[1] - files[0])):
+        fn, res, names = {}, {}, {}
+        for f in sorted(only):
+            txt = open(os.path.join(d, f)).read()
+            fn.update(functions(txt)); res.update(kr.kernels(txt))
+        for sym in fn:
+            names[plain_name(sym)] = sym
+        loose.append((fn, res, names))
+    (fa, ra, na), (fb, rb, nb) = loose
+    for name in sorted(set(na) | set(nb)):
+        total += 1
+        if name not in na or name not in nb:
+            print("(by name) %s: only in %s" % (name[:140], dir_a if name in na else dir_b))
             bad += 1
-            i = next((i for i, (x, y) in enumerate(zip(la, lb)) if x != y), min(len(la), len(lb)))
-            print("%s: %s: DIFFERS at line %d of %d / %d" % (f[:-len(SUFFIX)], name, i, len(la), len(lb)))
-            print("    a: %s\n    b: %s" % (la[i].strip() if i < len(la) else "(end)", lb[i].strip() if i < len(lb) else "(end)"))
-            print("    a: %s\n    b: %s" % (fig[0], fig[1]))
-    print("%d functions in %d files, %d differ or are missing" % (total, len(files[0] & files[1]), bad))
+            continue
+        bad += compare("(by name)", na[name], nb[name], fa, fb, ra, rb)
+    print("%d functions, %d differ or are missing" % (total, bad))
     return 1 if bad else 0
 
 
