@@ -30,8 +30,9 @@ extern "C" {
  * up to 4096 labels with one shared strictly ascending positions vector (stereo_trws_plan_path 5).  8: stereo_trws_batch_*
  * (independent plans that share one launch per sweep).  10: stereo_trws_plans_state_* (solver state: save / load),
  * stereo_trws_state_check, stereo_trws_strip_state_rows_host.  11: stereo_lr_check / stereo_lr_fill (left-right
- * consistency).  12: stereo_band_inputs / stereo_band_apply (band refinement around a solved disparity map). */
-#define STEREO_HIP_ABI_VERSION 12
+ * consistency).  12: stereo_band_inputs / stereo_band_apply (band refinement around a solved disparity map).
+ * 13: stereo_plane_band_inputs_ncc / _globalstereo / stereo_plane_band_apply (band refinement around a solved plane map). */
+#define STEREO_HIP_ABI_VERSION 13
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -725,6 +726,66 @@ int stereo_band_inputs_device(const double *ncc, int H, int W, int D, int layout
 int stereo_band_apply_device(const double *base, int H, int W, const int32_t *labels, const double *offsets,
                              const double *d_offsets, int K, double *refined, int32_t *bad, void *stream,
                              char *err, size_t errcap);
+
+/* ---- band refinement around a solved plane map ----------------------------------------- *
+ * No reference counterpart as a call; the problem it builds is the reference's own energy restricted to K
+ * per-pixel labels.  From `planes` (4 x N column major, N = H*W: an object's assignment [a b c d] per pixel) and a
+ * strictly ascending vector `offsets` (K doubles, one of them 0.0, in the planes' own disparity units), label k
+ * at pixel i means pixel i's own plane moved by offsets_k along the disparity axis:
+ *     [a_i, b_i, c_i, d_i - c_i * offsets_k]      (one fp64 multiplication, one fp64 subtraction, no contraction)
+ * In exact arithmetic its disparity at any point is plane i's disparity plus offsets_k; two pixels on one slanted
+ * plane keep q == qprim for every label, which the fronto-parallel band above gives up.
+ *
+ * Everything else is the library's existing code on those K proposals: unary(k, i) is what stereo_ncc_unary
+ * (_ncc) or stereo_globalstereo_unary (_globalstereo) gives for proposal k; q(k, e), qprim(k, e) for
+ * e = (i1, i2) = (conn[2e], conn[2e + 1]) are what stereo_trws_positions gives -- q the shifted plane of i2 at the
+ * point of i2, qprim the shifted plane of i1 at the point of i2 -- with d_min = d_step = 0 for _ncc and the
+ * (v - d_min) / d_step rescaling for _globalstereo.  A pixel's point is [id / H + 1, id % H + 1], formed in the
+ * kernel.  unary is K x N, q and qprim are K x E, label fastest; E = 0: conn, q and qprim may be NULL.  The outputs
+ * equal those of K calls of the unary entry and one of stereo_trws_positions bit for bit (csrc/ncc_sample.h,
+ * csrc/gs_sample.h: one copy of each sampler).
+ * stereo_plane_band_apply: refined_i = [a_i, b_i, c_i, d_i - c_i * offsets_{label_i - 1}], 4 x N, labels int32 and
+ * one based as stereo_trws_plan_result returns them.
+ *
+ * Refused with a message, before the device is looked for: the offset rules of the band above and K outside
+ * 1 .. stereo_band_max_offsets(); layout other than 0 / 1; D, H, W or C below 1 (apply: N below 1); H*W >= 2^31
+ * (apply: N >= 2^31); NULL for a required array; d_step == 0 for _globalstereo.  The host entries also refuse a plane
+ * with c == 0 ("Infinite disparity", dispmap_super.m:323-325) or a component that is not finite, a conn entry
+ * outside 0 .. N - 1 and, in apply, a label outside 1 .. K; the message names the pixel. */
+int stereo_plane_band_inputs_ncc(const double *ncc, int H, int W, int D, int layout, const double *disparities,
+                                 double unary_weight, const double *planes, const double *offsets, int K,
+                                 int64_t E, const uint32_t *conn, double *unary, double *q, double *qprim,
+                                 char *err, size_t errcap);
+int stereo_plane_band_inputs_globalstereo(const double *im0, const double *im1, int H, int W, int C,
+                                          const double *P2, double d_min, double d_step, double col_thresh,
+                                          const double *planes, const double *offsets, int K, int64_t E,
+                                          const uint32_t *conn, double *unary, double *q, double *qprim,
+                                          char *err, size_t errcap);
+int stereo_plane_band_apply(const double *planes, int64_t N, const int32_t *labels, const double *offsets,
+                            int K, double *refined, char *err, size_t errcap);
+/* The same on device arrays of the caller (ncc / im0 / im1, planes, conn, labels and every output), launched on
+ * `stream` (hipStream_t, NULL = default) without waiting for it, with the conventions of stereo_band_inputs_device:
+ * the short vectors are passed twice, on the host (checked) and in device memory (read by the kernels); P2 is
+ * 12 host doubles and travels as a kernel argument.  `bad` (device int32, may be NULL) is set to zero on `stream`
+ * and then incremented once per pixel whose plane has c == 0 or a component that is not finite (inputs) or, in
+ * apply, such a plane or a label outside 1 .. K: that pixel's refined plane is four NaN.  The outputs of an
+ * offending pixel are unspecified but written.  An edge that names a pixel outside 0 .. N - 1 reads nothing; its
+ * positions are NaN. */
+int stereo_plane_band_inputs_ncc_device(const double *ncc, int H, int W, int D, int layout,
+                                        const double *disparities, const double *d_disparities,
+                                        double unary_weight, const double *planes, const double *offsets,
+                                        const double *d_offsets, int K, int64_t E, const uint32_t *conn,
+                                        double *unary, double *q, double *qprim, int32_t *bad, void *stream,
+                                        char *err, size_t errcap);
+int stereo_plane_band_inputs_globalstereo_device(const double *im0, const double *im1, int H, int W, int C,
+                                                 const double *P2, double d_min, double d_step,
+                                                 double col_thresh, const double *planes, const double *offsets,
+                                                 const double *d_offsets, int K, int64_t E, const uint32_t *conn,
+                                                 double *unary, double *q, double *qprim, int32_t *bad,
+                                                 void *stream, char *err, size_t errcap);
+int stereo_plane_band_apply_device(const double *planes, int64_t N, const int32_t *labels, const double *offsets,
+                                   const double *d_offsets, int K, double *refined, int32_t *bad, void *stream,
+                                   char *err, size_t errcap);
 
 /* ---- device-resident fusion moves --------------------------------------- *
  * The state of one dispmap object kept in HBM across moves: connectivity, weights, points,

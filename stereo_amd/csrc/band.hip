@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <string>
 
+#include "band_common.h"
 #include "common.h"
 #include "ncc_sample.h"
 #include "stereo_hip.h"
@@ -19,24 +20,7 @@
 namespace {
 
 using stereo::fail;
-using stereo::HipError;
-
-constexpr int kTB = 256;
-constexpr int kMaxOffsets = 512;
-constexpr unsigned kMaxGrid = 1u << 20;   // blocks of one launch; a block strides over what is left
-
-// Element t = item * K + k of a K x M label-fastest array, for the 256 consecutive t of a block: the 64-bit
-// division is done once per block on uniform values, a lane divides a number below 256 + K.
-struct BandIndex {
-  int64_t item;
-  int k;
-};
-__device__ __forceinline__ BandIndex band_index(int64_t block_first, int K) {
-  const int64_t item0 = block_first / K;
-  const uint32_t local = (uint32_t)(block_first - item0 * K) + threadIdx.x;
-  const uint32_t up = local / (uint32_t)K;
-  return {item0 + up, (int)(local - up * (uint32_t)K)};
-}
+using namespace stereo::band;   // kTB, kMaxOffsets, band_index, check_offsets, check_sizes, guarded, grid_for
 
 // The disparity of label k at a pixel whose base is b: plane_disp of [0 0 1 -(b + delta)].  The plane's
 // s = 0 x + 0 y is +0 at every pixel, so no pixel coordinate is formed; the value is b + delta, with the
@@ -134,27 +118,6 @@ __global__ __launch_bounds__(kTB) void band_apply_kernel(int64_t Npx, int K, con
 
 // ---------------------------------------------------------------- argument checks (no device call)
 
-int check_offsets(const std::string &what, const double *offsets, int K, char *err, size_t errcap) {
-  if (K < 1 || K > kMaxOffsets)
-    return fail(what + ": the number of offsets must be 1 .. " + std::to_string(kMaxOffsets) + " (got " + std::to_string(K) + ")", err, errcap);
-  if (!offsets) return fail(what + ": offsets must not be NULL", err, errcap);
-  bool zero = false;
-  for (int k = 0; k < K; ++k) {
-    if (!std::isfinite(offsets[k])) return fail(what + ": offsets[" + std::to_string(k) + "] is not finite", err, errcap);
-    if (k > 0 && !(offsets[k] > offsets[k - 1]))
-      return fail(what + ": offsets must be strictly ascending (offsets[" + std::to_string(k) + "] <= offsets[" + std::to_string(k - 1) + "])", err, errcap);
-    zero = zero || offsets[k] == 0.0;
-  }
-  if (!zero) return fail(what + ": offsets must contain 0.0 (the base labelling must be one of the band's)", err, errcap);
-  return 0;
-}
-
-int check_sizes(const std::string &what, int H, int W, char *err, size_t errcap) {
-  if (H < 1 || W < 1) return fail(what + ": H and W must be at least 1", err, errcap);
-  if ((int64_t)H * (int64_t)W >= ((int64_t)1 << 31)) return fail(what + ": H * W must be below 2^31", err, errcap);
-  return 0;
-}
-
 int check_inputs(const std::string &what, const void *ncc, int H, int W, int D, int layout, const double *disparities,
                  const void *base, const double *offsets, int K, int64_t E, const void *conn, const void *unary,
                  const void *q, const void *qprim, char *err, size_t errcap) {
@@ -179,25 +142,6 @@ int check_base(const std::string &what, const double *base, int H, int W, char *
     if (!std::isfinite(base[i]))
       return fail(what + ": base is not finite at pixel (row " + std::to_string(i % H) + ", column " + std::to_string(i / H) + ")", err, errcap);
   return 0;
-}
-
-template <class F>
-int guarded(const char *what, char *err, size_t errcap, F f) {
-  if (stereo_hip_device_count() < 1)
-    return fail(std::string(what) + ": no HIP device available (the HIP path has no CPU fallback)", err, errcap);
-  try {
-    f();
-    return 0;
-  } catch (const HipError &e) {
-    return fail(e.msg, err, errcap);
-  } catch (const std::exception &e) {
-    return fail(std::string(what) + ": " + e.what(), err, errcap);
-  }
-}
-
-unsigned grid_for(int64_t elements) {
-  const int64_t b = (elements + kTB - 1) / kTB;
-  return (unsigned)(b < 1 ? 1 : b > (int64_t)kMaxGrid ? (int64_t)kMaxGrid : b);
 }
 
 // `disparities` / `offsets`: the host vectors (checked; min, max and the order of the slices come from them);

@@ -26,6 +26,7 @@
 
 #include "../../include/stereo_hip.h"
 #include "common.h"
+#include "gs_sample.h"
 #include "ncc_sample.h"
 
 namespace stereo {
@@ -554,47 +555,7 @@ __global__ __launch_bounds__(kTB) void globalstereo_unary_kernel(const double *i
   const int64_t Npx = (int64_t)H * W;
   if (px >= Npx) return;
   const double x = (double)(px / H + 1), y = (double)(px % H + 1);
-  const double dhat = (plane_disp(assign + 4 * (size_t)px, x, y) - d_min) / d_step;
-  const double disp = d_step * (dhat + d_min);  // dispmap_globalstereo.m:356 (sic)
-  double T[3];
-  for (int k = 0; k < 3; ++k)
-    T[k] = (x * P2[4 * k] + y * P2[4 * k + 1]) + (1.0 * P2[4 * k + 2] + disp * P2[4 * k + 3]);
-  const double Nn = 1.0 / T[2];
-  const double X = T[0] * Nn, Y = T[1] * Nn;
-  const double oobv = -1000.0, dw = (double)W, dh = (double)H;
-  double ssd = 0;
-  for (int c = 0; c < C; ++c) {
-    const double *A = im1 + (size_t)c * Npx;
-    double o = oobv;
-    if (X >= 1 && Y >= 1) {  // vgg_interp2.cxx:260-317
-      if (X < dw) {
-        if (Y < dh) {
-          const int xi = (int)X, yi = (int)Y;
-          const double u = X - xi, v = Y - yi;
-          const size_t k = (size_t)H * (xi - 1) + yi - 1;
-          o = A[k] + (A[k + H] - A[k]) * u;
-          o += ((A[k + 1] - o) + (A[k + H + 1] - A[k + 1]) * u) * v;
-        } else if (Y == dh) {
-          const int xi = (int)X;
-          const double u = X - xi;
-          const size_t k = (size_t)H * xi - 1;
-          o = A[k] + (A[k + H] - A[k]) * u;
-        }
-      } else if (X == dw) {
-        if (Y < dh) {
-          const int yi = (int)Y;
-          const double v = Y - yi;
-          const size_t k = (size_t)H * (W - 1) + yi - 1;
-          o = A[k] + (A[k + 1] - A[k]) * v;
-        } else if (Y == dh) {
-          o = A[(size_t)H * W - 1];
-        }
-      }
-    }
-    const double m = o - im0[(size_t)c * Npx + px];
-    ssd = ssd + m * m;
-  }
-  U[px] = log(2.0) - log(exp(ssd * (-1.0 / (col_thresh * C))) + 1.0);
+  U[px] = gs_unary_at(im0, im1, H, W, C, P2, d_min, d_step, col_thresh, px, x, y, plane_disp(assign + 4 * (size_t)px, x, y));
 }
 
 // ---- device-resident fusion moves (stereo_fusion_*) -----------------------------------------

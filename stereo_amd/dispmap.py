@@ -359,6 +359,32 @@ class dispmap_super:
                              "for dispmap_ncc" % type(self).__name__)
 
 
+    def _plane_band_source(self):
+        """The hook of refine_plane_band: (the object's unary source, the factor from the units of `levels` to the
+        planes' disparity units or None for 'as they are')."""
+        raise StereoHipError("refine_plane_band: %s names no unary source" % type(self).__name__)
+
+    def refine_plane_band(self, levels, maxiter=None):
+        """Sub-pixel refinement that keeps each pixel's plane (no reference counterpart): for every
+        vector of offsets in `levels` (strictly ascending, containing 0) TRW-S chooses per pixel among the pixel's own
+        plane moved by an offset along the disparity axis, [a b c d - c offset], with this object's unary, kernel,
+        tolerance, smoothness weights, rescaling and max_relgap, up to `maxiter` (default self.maxiter) iterations per
+        level.  The levels are in the units of the object's smoothness term: disparities for dispmap_ncc, the rescaled
+        units in which disp_thresh lives for dispmap_globalstereo.  The result goes in through the assignment setter;
+        returns plane_band.refine_plane_band's PlaneBandResult (planes in the object's internal columns)."""
+        from . import plane_band
+        levels = plane_band.check_levels(levels)
+        source, unit = self._plane_band_source()
+        if unit is not None:
+            levels = [l * unit for l in levels]
+        out = plane_band.refine_plane_band(source, self.assignment, self._kernel, self.tol, levels,
+                                           self.maxiter if maxiter is None else maxiter, self._max_relgap,
+                                           alphas=self.smooth_weights, conn=self.neighborhood, d_min=self.d_min,
+                                           d_step=self.d_step)
+        self.assignment = out.planes
+        return out
+
+
 class dispmap_ncc(dispmap_super):
     """dispmap_ncc.m"""
 
@@ -444,6 +470,10 @@ class dispmap_ncc(dispmap_super):
                                conn=self.neighborhood)
         self.set_disparity(self._unflip(out.dispmap))
         return out
+
+    def _plane_band_source(self):
+        from . import plane_band
+        return plane_band.NccSource(self.ncc, self.disparities, self._unary_weight), None
 
     # ---- proposals (dispmap_ncc.m:48-92).  Host side: a few dozen points and 3 x 3 SVDs per
     # proposal; MATLAB's svd is outside the reference tree, so this mirrors the arithmetic with
@@ -569,6 +599,10 @@ class dispmap_globalstereo(dispmap_super):
 
     def init_solution(self):
         self.set_disparity(self.start_disparity)
+
+    def _plane_band_source(self):
+        from . import plane_band
+        return plane_band.GlobalstereoSource(self.images[0], self.images[1], self.P2, self.options["col_thresh"]), self.d_step
 
     # ---- proposals (dispmap_globalstereo.m:60-201)
     def segpln_wta(self):
