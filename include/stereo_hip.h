@@ -31,8 +31,9 @@ extern "C" {
  * (independent plans that share one launch per sweep).  10: stereo_trws_plans_state_* (solver state: save / load),
  * stereo_trws_state_check, stereo_trws_strip_state_rows_host.  11: stereo_lr_check / stereo_lr_fill (left-right
  * consistency).  12: stereo_band_inputs / stereo_band_apply (band refinement around a solved disparity map).
- * 13: stereo_plane_band_inputs_ncc / _globalstereo / stereo_plane_band_apply (band refinement around a solved plane map). */
-#define STEREO_HIP_ABI_VERSION 13
+ * 13: stereo_plane_band_inputs_ncc / _globalstereo / stereo_plane_band_apply (band refinement around a solved plane map).
+ * 14: stereo_pyramid_reduce / stereo_pyramid_expand (image pyramid: box reduction, map expansion). */
+#define STEREO_HIP_ABI_VERSION 14
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -786,6 +787,46 @@ int stereo_plane_band_inputs_globalstereo_device(const double *im0, const double
 int stereo_plane_band_apply_device(const double *planes, int64_t N, const int32_t *labels, const double *offsets,
                                    const double *d_offsets, int K, double *refined, int32_t *bad, void *stream,
                                    char *err, size_t errcap);
+
+/* ---- image pyramid: box reduction and map expansion ---------------------------------- *
+ * No reference counterpart.  An image is H x W x C doubles and a map H x W doubles, column major: element
+ * (y, x, c) at y + H*(x + W*c), zero based.  The coarse size of H x W is Hc = (H + 1) / 2, Wc = (W + 1) / 2.
+ * Everything is fp64 without FMA contraction in the order written here, so the outputs are those of the same
+ * lines in any language, bit for bit.
+ *
+ * stereo_pyramid_reduce: out (Hc x Wc x C):
+ *     out(yc, xc, c) = 0.25 * (((a00 + a10) + a01) + a11),  a_ij = im(min(2 yc + i, H - 1), min(2 xc + j, W - 1), c)
+ * (i the row offset, j the column offset): the 2 x 2 box, the last row / column replicated at an odd size.  A coarse
+ * pixel covers the fine columns 2 xc and 2 xc + 1 in both views of a rectified pair, so a fine disparity d is d / 2
+ * at the coarse scale, without an offset.
+ *
+ * stereo_pyramid_expand: out (H x W) and source (int32, H x W, may be NULL) from d_coarse (Hc x Wc).  For the fine
+ * pixel (y, x): parent (yc, xc) = (y >> 1, x >> 1); ny = yc + 1 for an odd y, yc - 1 for an even one, clamped to
+ * 0 .. Hc - 1; nx the same from x and Wc.  Candidates, in this order: 0 (yc, xc), 1 (ny, xc), 2 (yc, nx), 3 (ny, nx):
+ * the coarse pixels of the fine pixel's bilinear footprint under the box reduction.
+ *   mode 0 (nearest): out = 2 * d_coarse(candidate 0) whatever that value is, source = 0; im_fine and im_coarse are
+ *     not read and may be NULL.
+ *   mode 1 (guided by the view's own image, im_fine H x W x C and im_coarse Hc x Wc x C): a candidate whose
+ *     disparity is not finite is skipped; a remaining candidate's distance is ((e0*e0 + e1*e1) + ...) over the
+ *     channels in order, e_c = im_fine(y, x, c) - im_coarse(candidate, c); the first remaining candidate is the best
+ *     until a later one has a strictly smaller distance (ties and NaN distances keep the earlier one);
+ *     out = 2 * d_coarse(best), source = its number.  No candidate remains: out = NaN, source = -1.
+ * The map is never interpolated.
+ *
+ * Refused with a message, before the device is looked for: H, W or C below 1; H*W >= 2^31; NULL for a required
+ * array; Hc, Wc that are not the coarse size of H, W; a mode other than 0 / 1; an output that is an input (out ==
+ * im, out or source == d_coarse / im_fine / im_coarse, source == out). */
+int stereo_pyramid_reduce(const double *im, int H, int W, int C, double *out, char *err, size_t errcap);
+int stereo_pyramid_expand(const double *d_coarse, int Hc, int Wc, int H, int W, int mode,
+                          const double *im_fine, const double *im_coarse, int C, double *out,
+                          int32_t *source, char *err, size_t errcap);
+/* The same on device arrays of the caller, launched on `stream` (hipStream_t, NULL = default) without waiting
+ * for it. */
+int stereo_pyramid_reduce_device(const double *im, int H, int W, int C, double *out, void *stream, char *err,
+                                 size_t errcap);
+int stereo_pyramid_expand_device(const double *d_coarse, int Hc, int Wc, int H, int W, int mode,
+                                 const double *im_fine, const double *im_coarse, int C, double *out,
+                                 int32_t *source, void *stream, char *err, size_t errcap);
 
 /* ---- device-resident fusion moves --------------------------------------- *
  * The state of one dispmap object kept in HBM across moves: connectivity, weights, points,

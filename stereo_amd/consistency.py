@@ -170,11 +170,14 @@ class ViewResult:
     """One view of solve_pair_ncc: `labels` (N, one based), `dispmap`, `status`, `residual`, `filled`, `source`
     (H x W), and per pass `energy`, `lower_bound`, `iterations` (lists: the first solve, then the refine pass, then one
     entry per band level).  After band levels `labels` are the last level's band labels and `dispmap`, `status`,
-    `residual`, `filled` and `source` those of the last level's refined map; `maps` keeps the map of every pass."""
+    `residual`, `filled` and `source` those of the last level's refined map; `maps` keeps the map of every pass and
+    `paths` the kernel family that ran it (TrwsPlan.path()).  A pyramid level that starts from an expanded map
+     keeps that map and the expansion's candidate numbers as `expanded` and `expand_source`."""
 
     def __init__(self):
         self.labels = self.dispmap = self.status = self.residual = self.filled = self.source = None
-        self.energy, self.lower_bound, self.iterations, self.maps = [], [], [], []
+        self.expanded = self.expand_source = None
+        self.energy, self.lower_bound, self.iterations, self.maps, self.paths = [], [], [], [], []
 
 
 class PairResult:
@@ -189,8 +192,48 @@ class PairResult:
         return self.left, self.right
 
 
+def collect_views(out, plans, to_map, check_tol, stage):
+    """One pass of a pair solve into `out` (PairResult): per view the plan's labels, energy, bound, iterations and
+    kernel family, the map `to_map(view index, labels)`; then each map checked against the other and filled."""
+    t = time.perf_counter()
+    for i, (plan, view) in enumerate(zip(plans, out.views)):
+        view.labels, en, lb, it = plan.result()
+        view.energy.append(en); view.lower_bound.append(lb); view.iterations.append(it)
+        view.paths.append(plan.path())
+        view.dispmap = to_map(i, view.labels)
+        view.maps.append(view.dispmap)
+    for view, other, direction in ((out.left, out.right, 1), (out.right, out.left, -1)):
+        view.status, view.residual = lr_check(view.dispmap, other.dispmap, direction, check_tol)
+        view.filled, view.source = lr_fill(view.dispmap, view.status)
+    out.times[stage] = time.perf_counter() - t
+
+
+def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
+                    zero_occluded=False):
+    """The band passes of a pair solve: for every vector of offsets both views (`problems`: one band.BandProblem each,
+    standing around the view's current map) build their band problem on the device and run up to `maxiter` iterations
+    as a two-member TrwsBatch; the labels are applied, the refined maps checked with `check_tol` and filled
+    (collect_views).  band_plans: {K: [plan, plan]}, filled here, closed by the caller.  zero_occluded: the unary
+    columns of the pixels the preceding check found occluded are zeroed."""
+    import torch
+    N = problems[0].N
+    for level, offsets in enumerate(band_levels):
+        t0 = time.perf_counter()
+        Kb = offsets.shape[0]
+        if Kb not in band_plans:
+            band_plans[Kb] = [TrwsPlan(int(kernel), Kb, N, conn) for _ in range(2)]
+        for prob, plan, view in zip(problems, band_plans[Kb], out.views):
+            occluded = torch.from_numpy(view.status.T.reshape(-1) == OCCLUDED).cuda() if zero_occluded else None
+            prob.build(offsets, plan, tol, zero_columns=occluded)
+        with TrwsBatch(band_plans[Kb]) as batch:
+            batch.iterate(maxiter, max_relgap)
+        out.times["band_%d" % (level + 1)] = time.perf_counter() - t0
+        collect_views(out, band_plans[Kb], lambda i, labels: problems[i].apply(labels), check_tol,
+                      "band_%d_check_fill" % (level + 1))
+
+
 def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_relgap, check_tol=1.0, refine_iters=0,
-                   band_levels=None):
+                   band_levels=None, smooth_weight=1.0):
     """Both views of a rectified pair: two NCC unary volumes, two TRW-S plans on the image grid with the shared
     positions `disparities`, iterated as one TrwsBatch; labels to maps; each map checked against the other and filled.
     refine_iters > 0: per view, the solver state is saved, the unary columns of the occluded pixels are zeroed and
@@ -199,7 +242,8 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
     band_levels: a sequence of offset vectors.  After the passes above, for every level both views build
     the band problem around their map on the device, from their own volume, and run up to `maxiter` iterations as a
     two-member TrwsBatch; the refined maps are checked with check_tol and filled.  With refine_iters > 0 the unary
-    columns of the pixels the preceding check found occluded are zeroed in the band as well."""
+    columns of the pixels the preceding check found occluded are zeroed in the band as well.
+    smooth_weight: the weight of every edge (a pyramid level's model)."""
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
     if len(images) != 2:
         raise StereoHipError("solve_pair_ncc: images must be the two views of a pair, left first (got %d)" % len(images))
@@ -220,21 +264,10 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
     unaries = pair_unaries(images, disparities, unary_weight, volumes)
     out.times["volumes"] = clock() - t0
     conn = T.construct_neighborhood(H, W)
-    alphas = np.ones(conn.shape[1])
+    alphas = np.ones(conn.shape[1]) * float(smooth_weight)
     plans = [TrwsPlan(int(kernel), K, N, conn) for _ in range(2)]
     band_plans = {}
-
-    def collect(stage, solved=None, to_map=None):
-        t = clock()
-        for i, (plan, view) in enumerate(zip(solved or plans, out.views)):
-            view.labels, en, lb, it = plan.result()
-            view.energy.append(en); view.lower_bound.append(lb); view.iterations.append(it)
-            view.dispmap = to_map(i, view.labels) if to_map else disparities[view.labels.astype(np.int64) - 1].reshape(W, H).T
-            view.maps.append(view.dispmap)
-        for view, other, direction in ((out.left, out.right, 1), (out.right, out.left, -1)):
-            view.status, view.residual = lr_check(view.dispmap, other.dispmap, direction, check_tol)
-            view.filled, view.source = lr_fill(view.dispmap, view.status)
-        out.times[stage] = clock() - t
+    by_index = lambda i, labels: disparities[labels.astype(np.int64) - 1].reshape(W, H).T
 
     try:
         t0 = clock()
@@ -243,7 +276,7 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
         with TrwsBatch(plans) as batch:
             batch.iterate(maxiter, max_relgap)
         out.times["solve"] = clock() - t0
-        collect("check_fill")
+        collect_views(out, plans, by_index, check_tol, "check_fill")
         if refine_iters > 0:
             t0 = clock()
             for plan, unary, view in zip(plans, unaries, out.views):
@@ -253,23 +286,12 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
             with TrwsBatch(plans) as batch:   # a fresh batch: a member that max_relgap stopped takes part again
                 batch.iterate(refine_iters, max_relgap)
             out.times["refine"] = clock() - t0
-            collect("refine_check_fill")
+            collect_views(out, plans, by_index, check_tol, "refine_check_fill")
         if band_levels is not None:
-            import torch
             problems = [band.BandProblem(vol, disparities, unary_weight, view.dispmap, conn, alphas, layout=1)
                         for vol, view in zip(volumes, out.views)]
-            for level, offsets in enumerate(band_levels):
-                t0 = clock()
-                Kb = offsets.shape[0]
-                if Kb not in band_plans:
-                    band_plans[Kb] = [TrwsPlan(int(kernel), Kb, N, conn) for _ in range(2)]
-                for prob, plan, view in zip(problems, band_plans[Kb], out.views):
-                    occluded = torch.from_numpy(view.status.T.reshape(-1) == OCCLUDED).cuda() if refine_iters > 0 else None
-                    prob.build(offsets, plan, tol, zero_columns=occluded)
-                with TrwsBatch(band_plans[Kb]) as batch:
-                    batch.iterate(maxiter, max_relgap)
-                out.times["band_%d" % (level + 1)] = clock() - t0
-                collect("band_%d_check_fill" % (level + 1), band_plans[Kb], lambda i, labels: problems[i].apply(labels))
+            run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
+                            zero_occluded=refine_iters > 0)
     finally:
         for plan in plans + [p for pair in band_plans.values() for p in pair]:
             plan.close()

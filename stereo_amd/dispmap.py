@@ -358,6 +358,9 @@ class dispmap_super:
         raise StereoHipError("refine_band: %s does not take its unary from the NCC sampler; band refinement is defined "
                              "for dispmap_ncc" % type(self).__name__)
 
+    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided"):
+        raise StereoHipError("solve_pyramid: %s reaches its second view through a projection, and its refinement is the "
+                             "plane band; the image pyramid is defined for dispmap_ncc" % type(self).__name__)
 
     def _plane_band_source(self):
         """The hook of refine_plane_band: (the object's unary source, the factor from the units of `levels` to the
@@ -468,6 +471,24 @@ class dispmap_ncc(dispmap_super):
         out = band.refine_band(self.ncc, self.disparities, self._unary_weight, base, self._kernel, self._tol, levels,
                                self.maxiter if maxiter is None else maxiter, self._max_relgap, alphas=self.smooth_weights,
                                conn=self.neighborhood)
+        self.set_disparity(self._unflip(out.dispmap))
+        return out
+
+    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided"):
+        """The map from the image pyramid (no reference counterpart): this view solved at the scale
+        2^levels with the level model of this object's kernel, unary weight and tolerance, carried up one scale at a time
+        (`expand`: 'guided' by the reference image, or 'nearest') and refined at every finer level l by the band levels
+        bands[l] (default one band, [-2 .. 2]); `maxiter` (default self.maxiter) is a scalar or one value per scale, level
+        0 first; max_relgap is the object's.  A level's edges all weigh s^(k - 1): an object with other smooth_weights
+        is refused.  A mirrored object works in its own flipped columns.  The result goes in through set_disparity;
+        returns pyramid.solve_view_ncc_pyramid's ViewPyramidResult (maps in the object's internal columns)."""
+        from . import pyramid
+        if not np.all(self.smooth_weights == 1.0):
+            raise StereoHipError("solve_pyramid: the level model gives every edge one weight; smooth_weights other than 1 "
+                                 "do not carry to another scale")
+        out = pyramid.solve_view_ncc_pyramid(self.images, self.disparities, self._kernel, self._unary_weight, self._tol,
+                                             levels, self.maxiter if maxiter is None else maxiter, self._max_relgap,
+                                             bands=bands, expand=expand)
         self.set_disparity(self._unflip(out.dispmap))
         return out
 

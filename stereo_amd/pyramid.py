@@ -1,0 +1,392 @@
+"""Image pyramid (no reference counterpart; the definitions: include/stereo_hip.h): the 2 x 2 box
+reduction of an image, the expansion of a coarse disparity map to the next finer scale, the model of a pyramid level
+and ``solve_pair_ncc_pyramid``: the pair solved at the coarsest scale, the maps carried up one scale at a time, band
+levels at every finer scale.
+
+Host forms take NumPy arrays: an image H x W x C (or H x W), a map H x W, any memory order.  Device forms take torch
+tensors of the current device in column-major storage: a map is a contiguous (W, H) tensor as lr_check_device takes
+it, an image a contiguous (C, W, H) tensor (``torch.from_numpy(np.ascontiguousarray(im.transpose(2, 1, 0)))``).
+"""
+import ctypes as C
+import math
+import time
+
+import numpy as np
+
+from . import _lib
+from . import band
+from . import consistency
+from . import terms as T
+from ._lib import StereoHipError
+from .consistency import _device_map, _map, _p, _stream
+from .trws import TrwsPlan
+
+MODES = {"nearest": 0, "guided": 1}
+MAX_LEVELS = 5
+DEFAULT_BAND = (-2.0, -1.0, 0.0, 1.0, 2.0)
+
+
+def coarse_size(H, W):
+    return (H + 1) // 2, (W + 1) // 2
+
+
+def _image(im, what):
+    im = np.asarray(im, dtype=np.float64)
+    if im.ndim == 2:
+        im = im[:, :, None]
+    if im.ndim != 3:
+        raise StereoHipError("%s must be an H x W x C array" % what)
+    return np.asfortranarray(im)
+
+
+def _mode(mode):
+    if mode in MODES:
+        return MODES[mode]
+    if isinstance(mode, (int, np.integer)) and not isinstance(mode, bool):
+        return int(mode)        # (the library refuses a number other than 0 / 1)
+    raise StereoHipError("expand must be 'nearest' or 'guided' (got %r)" % (mode,))
+
+
+def reduce(im):
+    """stereo_pyramid_reduce -> the (H + 1) // 2 x (W + 1) // 2 x C image (H x W in, H x W out)."""
+    flat = np.ndim(im) == 2
+    im = _image(im, "im")
+    H, W, Cn = im.shape
+    Hc, Wc = coarse_size(H, W)
+    out = np.zeros((max(Hc, 0), max(Wc, 0), max(Cn, 0)), order="F")
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_pyramid_reduce(_p(im), C.c_int(H), C.c_int(W), C.c_int(Cn), _p(out), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return out[:, :, 0] if flat else out
+
+
+def expand(d_coarse, shape, mode="guided", im_fine=None, im_coarse=None, want_source=True):
+    """stereo_pyramid_expand: the coarse map to the fine size `shape` = (H, W) -> (out H x W float64, source H x W
+    int32 or None).  mode 'nearest' / 0 needs no images; 'guided' / 1 takes the view's own image at both scales."""
+    mode = _mode(mode)
+    d_coarse = _map(d_coarse, "d_coarse")
+    H, W = (int(v) for v in shape)
+    Hc, Wc = d_coarse.shape
+    Cn = 1
+    if mode == 1:
+        if im_fine is None or im_coarse is None:
+            raise StereoHipError("expand: the guided mode needs im_fine and im_coarse")
+        im_fine, im_coarse = _image(im_fine, "im_fine"), _image(im_coarse, "im_coarse")
+        Cn = im_fine.shape[2]
+        if im_fine.shape != (H, W, Cn) or im_coarse.shape != (Hc, Wc, Cn):
+            raise StereoHipError("expand: im_fine must be H x W x C and im_coarse of d_coarse's size with the same C "
+                                 "(got %s and %s)" % (im_fine.shape, im_coarse.shape))
+    else:
+        im_fine = im_coarse = None
+    out = np.zeros((max(H, 0), max(W, 0)), order="F")
+    source = np.zeros((max(H, 0), max(W, 0)), np.int32, order="F") if want_source else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_pyramid_expand(_p(d_coarse), C.c_int(Hc), C.c_int(Wc), C.c_int(H), C.c_int(W), C.c_int(mode),
+                                          _p(im_fine), _p(im_coarse), C.c_int(Cn), _p(out), _p(source, C.c_int32), err,
+                                          C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return out, source
+
+
+# ---------------------------------------------------------------- device forms
+
+def _device_image(t, what, shape=None):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+        raise StereoHipError("%s must be a contiguous (C, W, H) float64 tensor on the device (column-major H x W x C)" % what)
+    if t.device.index != torch.cuda.current_device():
+        raise StereoHipError("%s must be on the current device" % what)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise StereoHipError("%s must have the size (C, W, H) = %s (got %s)" % (what, tuple(shape), tuple(t.shape)))
+    return t
+
+
+def image_to_device(im):
+    """An H x W x C host image as the (C, W, H) tensor the device forms take."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(_image(im, "im").transpose(2, 1, 0))).cuda()
+
+
+def image_to_host(t):
+    return t.cpu().numpy().transpose(2, 1, 0)
+
+
+def reduce_device(im, out=None, stream=None):
+    """stereo_pyramid_reduce_device on a (C, W, H) tensor, launched on `stream` (a torch stream or a raw handle; default:
+    torch's current stream) without waiting for it -> the (C, Wc, Hc) tensor."""
+    import torch
+    im = _device_image(im, "im")
+    Cn, W, H = im.shape
+    Hc, Wc = coarse_size(H, W)
+    out = torch.empty((Cn, Wc, Hc), dtype=torch.float64, device=im.device) if out is None else _device_image(out, "out", (Cn, Wc, Hc))
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_pyramid_reduce_device(C.c_void_p(im.data_ptr()), C.c_int(H), C.c_int(W), C.c_int(Cn),
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(_stream(stream)), err,
+                                                 C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return out
+
+
+def expand_device(d_coarse, shape, mode="guided", im_fine=None, im_coarse=None, out=None, source=None, stream=None,
+                  want_source=True):
+    """stereo_pyramid_expand_device: `d_coarse` a (Wc, Hc) map tensor, the images (C, W, H) / (C, Wc, Hc) tensors,
+    `shape` = (H, W) -> (out (W, H) float64, source (W, H) int32 or None)."""
+    import torch
+    mode = _mode(mode)
+    d_coarse = _device_map(d_coarse, "d_coarse", np.float64)
+    H, W = (int(v) for v in shape)
+    Wc, Hc = d_coarse.shape
+    Cn = 1
+    if mode == 1:
+        if im_fine is None or im_coarse is None:
+            raise StereoHipError("expand_device: the guided mode needs im_fine and im_coarse")
+        im_fine = _device_image(im_fine, "im_fine")
+        Cn = im_fine.shape[0]
+        _device_image(im_fine, "im_fine", (Cn, W, H))
+        im_coarse = _device_image(im_coarse, "im_coarse", (Cn, Wc, Hc))
+    else:
+        im_fine = im_coarse = None
+    out = torch.empty((W, H), dtype=torch.float64, device=d_coarse.device) if out is None else _device_map(out, "out", np.float64, (W, H))
+    if source is None and want_source:
+        source = torch.empty((W, H), dtype=torch.int32, device=d_coarse.device)
+    elif source is not None:
+        source = _device_map(source, "source", np.int32, (W, H))
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_pyramid_expand_device(vp(d_coarse), C.c_int(Hc), C.c_int(Wc), C.c_int(H), C.c_int(W), C.c_int(mode),
+                                                 vp(im_fine), vp(im_coarse), C.c_int(Cn), vp(out), vp(source),
+                                                 C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return out, source
+
+
+# ---------------------------------------------------------------- the level model
+
+def level_model(kernel, tol, level):
+    """(tol_l, edge weight) of level `level` (scale s = 2^level) in coarse disparity units: tol / s^k and s^(k - 1),
+    k = 1 or 2 the smoothness kernel's exponent.  The unary weight is the caller's at every level."""
+    k = int(kernel)
+    if k not in (1, 2):
+        raise StereoHipError("the level model is defined for the smoothness kernels 1 and 2 (got %r)" % (kernel,))
+    s = float(1 << int(level))
+    return float(tol) / s ** k, s ** (k - 1)
+
+
+def level_disparities(disparities, level):
+    """The slices of a level: the caller's at level 0, arange(floor(min / s), ceil(max / s) + 1) above."""
+    disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
+    if level == 0:
+        return disparities
+    s = float(1 << int(level))
+    return np.arange(math.floor(disparities.min() / s), math.ceil(disparities.max() / s) + 1, dtype=np.float64)
+
+
+def _check_offsets(v):
+    if not (np.isfinite(v).all() and (np.diff(v) > 0).all() and (v == 0.0).any()):
+        raise StereoHipError("bands: a vector of offsets must be finite, strictly ascending and contain 0 (got %s)" % (v.tolist(),))
+
+
+def check_plan(levels, maxiter, bands, expand):
+    """The checked arguments of a pyramid solve -> (levels, maxiter per level 0 .. levels, bands per level 0 .. levels - 1
+    as lists of float64 vectors, the expand mode's number)."""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 1 <= levels <= MAX_LEVELS:
+        raise StereoHipError("pyramid: levels (the number of reductions) must be 1 .. %d (got %r)" % (MAX_LEVELS, levels))
+    levels = int(levels)
+    if expand not in MODES:
+        raise StereoHipError("pyramid: expand must be 'nearest' or 'guided' (got %r)" % (expand,))
+    if np.ndim(maxiter) == 0:
+        maxiter = [int(maxiter)] * (levels + 1)
+    else:
+        maxiter = [int(m) for m in maxiter]
+        if len(maxiter) != levels + 1:
+            raise StereoHipError("pyramid: maxiter must be a scalar or one value per scale, level 0 first (%d values, got %d)"
+                                 % (levels + 1, len(maxiter)))
+    if bands is None:
+        bands = [[DEFAULT_BAND]] * levels
+    try:
+        n = len(bands)
+    except TypeError:
+        raise StereoHipError("pyramid: bands must hold one sequence of offset vectors per level 0 .. levels - 1")
+    if n != levels or isinstance(bands, dict):
+        raise StereoHipError("pyramid: bands must hold one sequence of offset vectors per level 0 .. levels - 1 "
+                             "(%d, got %d)" % (levels, n))
+    checked = []
+    for l, vectors in enumerate(bands):
+        try:
+            vectors = band.check_levels(vectors)
+        except (TypeError, ValueError):
+            raise StereoHipError("pyramid: bands[%d] must be a sequence of offset vectors" % l)
+        for v in vectors:
+            _check_offsets(v)
+        checked.append(vectors)
+    return levels, maxiter, checked, MODES[expand]
+
+
+def reduce_images(images, levels):
+    """Every image reduced `levels` times on the device -> per level 0 .. levels the list of host images (level 0: the
+    inputs as float64) and the list of their device tensors."""
+    host = [[np.asarray(im, dtype=np.float64) for im in images]]
+    dev = [[image_to_device(im) for im in host[0]]]
+    for _ in range(levels):
+        dev.append([reduce_device(t) for t in dev[-1]])
+        host.append([image_to_host(t) for t in dev[-1]])
+    return host, dev
+
+
+def _expand_view(dispmap, shape, mode, d_fine, d_coarse):
+    """One view's map to the next finer scale with the view's device images -> (map, source) on the host."""
+    import torch
+    d = torch.from_numpy(np.ascontiguousarray(np.asarray(dispmap, dtype=np.float64).T)).cuda()
+    out, source = expand_device(d, shape, mode, d_fine, d_coarse)
+    return out.cpu().numpy().T, source.cpu().numpy().T
+
+
+class PyramidResult:
+    """solve_pair_ncc_pyramid's result.  `levels[l]`, l = 0 (the input's size) .. the number of reductions, is that
+    scale's PairResult: per view the maps, labels, energies, bounds, iterations and kernel families of its passes (at the
+    coarsest scale the solve, below it one pass per offset vector), status, residual, filled and source of its last
+    check, and below the coarsest scale `expanded` / `expand_source`, the map the level started from and the
+    expansion's candidate numbers; `levels[l].times` has the level's seconds per stage.  `disparities[l]`, `tol[l]`,
+    `smooth_weight[l]`: the level's model.  `left` / `right` are the views of level 0; `times` the seconds of the
+    stages outside a level (`reduce`) and per level (`level_<l>`)."""
+
+    def __init__(self):
+        self.levels, self.disparities, self.tol, self.smooth_weight = [], [], [], []
+        self.times = {}
+
+    @property
+    def left(self):
+        return self.levels[0].left
+
+    @property
+    def right(self):
+        return self.levels[0].right
+
+    @property
+    def views(self):
+        return self.levels[0].views
+
+
+def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, levels, maxiter, max_relgap, bands=None,
+                           expand="guided", check_tol=1.0):
+    """Both views of a rectified pair, coarse to fine.  Both images are reduced `levels` times (1 .. 5)
+    on the device; solve_pair_ncc runs at the coarsest scale with that level's model (level_model, level_disparities);
+    then for each finer level l each view's map is expanded with the view's own images of the two scales (`expand`:
+    'guided' or 'nearest'), and for every vector of offsets in bands[l] (default: one band, [-2 .. 2]; one coarse label
+    is two fine pixels) both views run their band problem around the current map as a two-member TrwsBatch
+    (consistency.run_band_levels, the loop of solve_pair_ncc(band_levels=)), with the level's volume from pair_volumes
+    on the level's images; every pass ends in a cross-check with check_tol / 2^l and a fill.  The caller's sub-pixel
+    levels are further vectors in bands[0].  maxiter: a scalar, or one value per scale with level 0 first.
+    -> PyramidResult."""
+    levels, maxiter, bands, mode = check_plan(levels, maxiter, bands, expand)
+    disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
+    if len(images) != 2:
+        raise StereoHipError("solve_pair_ncc_pyramid: images must be the two views of a pair, left first (got %d)" % len(images))
+    shapes = [np.shape(im) for im in images]
+    if shapes[0] != shapes[1] or len(shapes[0]) != 3 or shapes[0][2] != 3:
+        raise StereoHipError("solve_pair_ncc_pyramid: the two images must be H x W x 3 arrays of one size (got %s and %s)" % tuple(shapes))
+    if disparities.size < 1:
+        raise StereoHipError("solve_pair_ncc_pyramid: no disparities")
+    level_model(kernel, tol, 0)
+    _lib.require_device()
+    clock = time.perf_counter
+    out = PyramidResult()
+    t0 = clock()
+    host, dev = reduce_images(images, levels)
+    out.times["reduce"] = clock() - t0
+    out.levels = [None] * (levels + 1)
+    for l in range(levels + 1):
+        tol_l, w_l = level_model(kernel, tol, l)
+        out.disparities.append(level_disparities(disparities, l))
+        out.tol.append(tol_l); out.smooth_weight.append(w_l)
+
+    t0 = clock()
+    L = levels
+    out.levels[L] = consistency.solve_pair_ncc(host[L], out.disparities[L], kernel, unary_weight, out.tol[L], maxiter[L],
+                                               max_relgap, check_tol=check_tol / (1 << L), smooth_weight=out.smooth_weight[L])
+    out.times["level_%d" % L] = clock() - t0
+    for l in range(levels - 1, -1, -1):
+        t0 = clock()
+        H, W = host[l][0].shape[:2]
+        res = out.levels[l] = consistency.PairResult()
+        for i, (view, coarse) in enumerate(zip(res.views, out.levels[l + 1].views)):
+            view.expanded, view.expand_source = _expand_view(coarse.dispmap, (H, W), mode, dev[l][i], dev[l + 1][i])
+            view.dispmap = view.expanded
+        res.times["expand"] = clock() - t0
+        t1 = clock()
+        volumes = consistency.pair_volumes(host[l], out.disparities[l])
+        res.times["volumes"] = clock() - t1
+        conn = T.construct_neighborhood(H, W)
+        alphas = np.ones(conn.shape[1]) * out.smooth_weight[l]
+        band_plans = {}
+        try:
+            problems = [band.BandProblem(vol, out.disparities[l], unary_weight, view.dispmap, conn, alphas, layout=1)
+                        for vol, view in zip(volumes, res.views)]
+            consistency.run_band_levels(res, problems, bands[l], band_plans, kernel, conn, out.tol[l], maxiter[l], max_relgap,
+                                        check_tol / (1 << l))
+        finally:
+            for plan in (p for pair in band_plans.values() for p in pair):
+                plan.close()
+        out.times["level_%d" % l] = clock() - t0
+    return out
+
+
+# ---------------------------------------------------------------- one view (dispmap_ncc.solve_pyramid)
+
+class ViewPyramidResult:
+    """solve_view_ncc_pyramid's result: `dispmap` (level 0's last map) and per level l, index l: `maps` (the maps of the
+    level's passes), `expanded` / `expand_source` (None at the coarsest level), `labels`, `energy`, `lower_bound`,
+    `iterations`, `paths` (lists per pass), `disparities`, `tol`, `smooth_weight`."""
+
+    def __init__(self, n):
+        self.dispmap = None
+        for name in ("maps", "labels", "energy", "lower_bound", "iterations", "paths"):
+            setattr(self, name, [[] for _ in range(n)])
+        self.expanded, self.expand_source = [None] * n, [None] * n
+        self.disparities, self.tol, self.smooth_weight = [], [], []
+
+
+def solve_view_ncc_pyramid(images, disparities, kernel, unary_weight, tol, levels, maxiter, max_relgap, bands=None,
+                           expand="guided"):
+    """One view, coarse to fine: `images` = (the reference image, the other one), a pixel at column x with disparity d
+    matching column x - d of the other.  The steps of solve_pair_ncc_pyramid for one view with solo plans: the volume
+    of a level is terms.ncc_volume on the level's images, the coarsest level one TrwsPlan on the level's slices, every
+    finer level band.refine_band around the expanded map.  No cross-check.  -> ViewPyramidResult."""
+    levels, maxiter, bands, mode = check_plan(levels, maxiter, bands, expand)
+    disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
+    level_model(kernel, tol, 0)
+    _lib.require_device()
+    host, dev = reduce_images(images[:2], levels)
+    out = ViewPyramidResult(levels + 1)
+    for l in range(levels + 1):
+        tol_l, w_l = level_model(kernel, tol, l)
+        out.disparities.append(level_disparities(disparities, l))
+        out.tol.append(tol_l); out.smooth_weight.append(w_l)
+    L = levels
+    H, W = host[L][0].shape[:2]
+    conn = T.construct_neighborhood(H, W)
+    vol = T.ncc_volume(host[L][0], host[L][1], out.disparities[L], 2, layout=1)
+    plan = TrwsPlan(int(kernel), out.disparities[L].shape[0], H * W, conn)
+    try:
+        plan.upload(unary_weight * (1.0 - vol), np.ones(conn.shape[1]) * out.smooth_weight[L], out.tol[L],
+                    positions=out.disparities[L])
+        plan.iterate(maxiter[L], max_relgap)
+        labels, en, lb, it = plan.result()
+        out.paths[L].append(plan.path())
+    finally:
+        plan.close()
+    out.labels[L].append(labels); out.energy[L].append(en); out.lower_bound[L].append(lb); out.iterations[L].append(it)
+    current = out.disparities[L][labels.astype(np.int64) - 1].reshape(W, H).T
+    out.maps[L].append(current)
+    for l in range(levels - 1, -1, -1):
+        H, W = host[l][0].shape[:2]
+        out.expanded[l], out.expand_source[l] = _expand_view(current, (H, W), mode, dev[l][0], dev[l + 1][0])
+        conn = T.construct_neighborhood(H, W)
+        vol = T.ncc_volume(host[l][0], host[l][1], out.disparities[l], 2, layout=1)
+        r = band.refine_band(vol, out.disparities[l], unary_weight, out.expanded[l], kernel, out.tol[l], bands[l], maxiter[l],
+                             max_relgap, alphas=np.ones(conn.shape[1]) * out.smooth_weight[l], layout=1, conn=conn)
+        out.maps[l], out.labels[l], out.energy[l] = r.maps, r.labels, r.energy
+        out.lower_bound[l], out.iterations[l], out.paths[l] = r.lower_bound, r.iterations, r.paths
+        current = r.dispmap
+    out.dispmap = current
+    return out
