@@ -4,12 +4,20 @@ solved coarse to fine (solve_pair_ncc_pyramid) and at full size (solve_pair_ncc)
 iteration budget per solve (max_relgap 0: every solve runs `--maxiter` iterations).
 
     python examples/example_pyramid.py [--levels 2] [--maxiter 30] [--expand guided] [--kernel 1] [--drop-slice]
+                                       [--carry [--record out.txt]]
 
 Per pair and method it prints the wall time per stage, the kernel family of every solve (TrwsPlan.path(): 2 is the
 K <= 64 Pipe family), the energy of the final left map in the full-size model (one dispmap_ncc, set_disparity +
 update_energy), the share of consistent pixels at check tolerances 0.5 and 1.0, and the share of pixels where the two
 methods' left maps differ by more than 1.  --drop-slice leaves out the coarsest level's last slice where that level has
 65 (one past the Pipe family), as a caller who wants the coarse solve in that family would.
+
+--carry measures instead what carrying the messages from stage to stage buys.  On the left view with
+solo plans, per band of every level, around the map the cold chain produced: the cold band's energy and bound after
+--maxiter iterations and, from the carried band's trace, the first iteration at which its energy is at or below the cold
+energy and the first at which its bound is at or above the cold bound (the first band of a level carries from the scale
+above, the others from the band before).  Then the pair pyramid end to end with max_relgap 1e-4 for carry 'none',
+'levels' and 'scales': iterations per pass, the energy of the final left map in the full-size model, wall time.
 """
 import argparse
 import os
@@ -25,6 +33,78 @@ PAIRS = (("teddy", "teddy_pair.npz", 60), ("baby2", "baby2_pair.npz", 86))
 UNARY_WEIGHT, TOL = 40.0, 8.0
 
 
+def measure_carry(name, images, disparities, args, say):
+    import stereo_amd
+    from stereo_amd import band, carry, pyramid, terms as T
+    from stereo_amd.trws import TrwsPlan
+    NEVER = -1e300
+    L = args.levels
+    bands = [[np.array(pyramid.DEFAULT_BAND)]] * L
+    bands[0] = bands[0] + [np.arange(-4, 5) / 4.0]             # level 0: the band, then a quarter-pixel level
+    host, dev = pyramid.reduce_images(images, L)
+    disp = [pyramid.level_disparities(disparities, l) for l in range(L + 1)]
+    model = [pyramid.level_model(args.kernel, TOL, l) for l in range(L + 1)]
+    H, W = host[L][0].shape[:2]
+    conn = T.construct_neighborhood(H, W)
+    vol = T.ncc_volume(host[L][0], host[L][1], disp[L], 2, layout=1)
+    plan = TrwsPlan(args.kernel, disp[L].shape[0], H * W, conn)
+    plan.upload(UNARY_WEIGHT * (1.0 - vol), np.ones(conn.shape[1]) * model[L][1], model[L][0], positions=disp[L])
+    plan.iterate(args.maxiter, NEVER)
+    labels, en, lb, _ = plan.result()
+    say("%s level %d (%d x %d, %d slices), left view, %d iterations: energy %.4f bound %.4f" % (name, L, H, W, disp[L].shape[0], args.maxiter, en, lb))
+    stage = carry.full_range_stage(plan, disp[L], conn, (H, W))
+    plan.close()
+    current = disp[L][labels.astype(np.int64) - 1].reshape(W, H).T
+    for l in range(L - 1, -1, -1):
+        H, W = host[l][0].shape[:2]
+        conn = T.construct_neighborhood(H, W)
+        expanded, _ = pyramid._expand_view(current, (H, W), pyramid.MODES[args.expand], dev[l][0], dev[l + 1][0])
+        vol = T.ncc_volume(host[l][0], host[l][1], disp[l], 2, layout=1)
+        alphas = np.ones(conn.shape[1]) * model[l][1]
+        cold = band.BandProblem(vol, disp[l], UNARY_WEIGHT, expanded, conn, alphas, layout=1)
+        warm = band.BandProblem(vol, disp[l], UNARY_WEIGHT, expanded, conn, alphas, layout=1)
+        for b, offsets in enumerate(bands[l]):
+            pa, pb = TrwsPlan(args.kernel, len(offsets), H * W, conn), TrwsPlan(args.kernel, len(offsets), H * W, conn)
+            cold.build(offsets, pa, model[l][0])
+            pa.iterate(args.maxiter, NEVER)
+            labels, en, lb, _ = pa.result()
+            t0 = time.perf_counter()
+            warm.build(offsets, pb, model[l][0], carry=warm.carry_from(stage, scales=b == 0))
+            t_build = time.perf_counter() - t0
+            first_en = first_lb = None
+            trace = []
+            for it in range(1, args.maxiter + 1):
+                pb.iterate(1, NEVER)
+                _, wen, wlb, _ = pb.result(want_labels=False)
+                trace.append((wen, wlb))
+                if first_en is None and wen <= en:
+                    first_en = it
+                if first_lb is None and wlb >= lb:
+                    first_lb = it
+            say("%s level %d band %d (%d x %d, offsets %+g .. %+g by %g): cold after %d iterations energy %.4f bound %.4f"
+                % (name, l, b + 1, H, W, offsets[0], offsets[-1], offsets[1] - offsets[0], args.maxiter, en, lb))
+            say("%s level %d band %d carried from %s: energy %.4f bound %.4f after 1 iteration, %.4f / %.4f after %d; energy at or "
+                "below the cold one first at iteration %s, bound at or above the cold one first at iteration %s (build + transfer "
+                "+ load %.3f s)" % (name, l, b + 1, "the scale above" if b == 0 else "the band before", trace[0][0], trace[0][1],
+                                    trace[-1][0], trace[-1][1], args.maxiter, first_en, first_lb, t_build))
+            stage = cold.stage(pa)                  # both chains go on around the cold chain's map
+            current = cold.apply(labels)
+            warm.apply(labels)
+            pa.close()
+            pb.close()
+    dm = stereo_amd.dispmap_ncc(images, disparities, args.kernel, UNARY_WEIGHT, TOL)
+    solve_args = (images, disparities, args.kernel, UNARY_WEIGHT, TOL, L, args.maxiter, 1e-4)
+    for mode in ("none", "levels", "scales", "none", "levels", "scales"):
+        t0 = time.perf_counter()
+        out = stereo_amd.solve_pair_ncc_pyramid(*solve_args, bands=bands, expand=args.expand, carry=mode)
+        seconds = time.perf_counter() - t0
+        dm.set_disparity(out.left.dispmap)
+        dm.update_energy()
+        say("%s pair pyramid, max_relgap 1e-4, carry %-6s: left iterations per level %s; energy of the final left map in the "
+            "full-size model %.4f; end to end %.3f s"
+            % (name, mode, {l: [int(i) for i in out.levels[l].left.iterations] for l in range(L, -1, -1)}, dm.energy(), seconds))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--levels", type=int, default=2)
@@ -32,6 +112,8 @@ def main():
     ap.add_argument("--expand", default="guided")
     ap.add_argument("--kernel", type=int, default=1)
     ap.add_argument("--drop-slice", action="store_true")
+    ap.add_argument("--carry", action="store_true", help="measure what carried messages buy (DESIGN.md 6.5)")
+    ap.add_argument("--record", help="with --carry: append the measurement's lines to this file")
     args = ap.parse_args()
     import stereo_amd
     from stereo_amd import pyramid
@@ -45,6 +127,21 @@ def main():
             disparities = disparities[:s * 63 + 1]
         print("%s %d x %d, %d disparities, kernel %d, unary weight %g, tol %g, %d iterations per solve, %d reductions, expand %s"
               % (name, H, W, disparities.shape[0], args.kernel, UNARY_WEIGHT, TOL, args.maxiter, args.levels, args.expand))
+        if args.carry:
+            lines = []
+
+            def say(line):
+                print(line, flush=True)
+                lines.append(line)
+
+            say("example_pyramid.py --carry --levels %d --maxiter %d --expand %s --kernel %d%s: %s %d x %d, %d disparities"
+                % (args.levels, args.maxiter, args.expand, args.kernel, " --drop-slice" if args.drop_slice else "", name, H, W,
+                   disparities.shape[0]))
+            measure_carry(name, images, disparities, args, say)
+            if args.record:
+                with open(args.record, "a") as f:
+                    f.write("\n".join(lines) + "\n")
+            continue
         solve_args = (images, disparities, args.kernel, UNARY_WEIGHT, TOL)
         stereo_amd.solve_pair_ncc_pyramid(*solve_args, args.levels, 1, 0.0, expand=args.expand)      # warm-up: code objects
         t0 = time.perf_counter()

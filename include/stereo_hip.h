@@ -32,8 +32,10 @@ extern "C" {
  * stereo_trws_state_check, stereo_trws_strip_state_rows_host.  11: stereo_lr_check / stereo_lr_fill (left-right
  * consistency).  12: stereo_band_inputs / stereo_band_apply (band refinement around a solved disparity map).
  * 13: stereo_plane_band_inputs_ncc / _globalstereo / stereo_plane_band_apply (band refinement around a solved plane map).
- * 14: stereo_pyramid_reduce / stereo_pyramid_expand (image pyramid: box reduction, map expansion). */
-#define STEREO_HIP_ABI_VERSION 14
+ * 14: stereo_pyramid_reduce / stereo_pyramid_expand (image pyramid: box reduction, map expansion).
+ * 15: stereo_band_carry / stereo_band_carry_device (messages carried from one band level or pyramid scale to the
+ * next), stereo_trws_state_receivers_host. */
+#define STEREO_HIP_ABI_VERSION 15
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -727,6 +729,57 @@ int stereo_band_inputs_device(const double *ncc, int H, int W, int D, int layout
 int stereo_band_apply_device(const double *base, int H, int W, const int32_t *labels, const double *offsets,
                              const double *d_offsets, int K, double *refined, int32_t *bad, void *stream,
                              char *err, size_t errcap);
+
+/* ---- messages carried from one band level or pyramid scale to the next --------------- *
+ * No reference counterpart.  A chain of band problems solves every level around the map the level before produced;
+ * this operator turns the messages that level left (M_old: E_old x K_old doubles, label fastest, a solver state's
+ * layout) into messages on the next level's label grid (M_new: E_new x K_new), so that the next level starts from
+ * them instead of from zero.  Any message array is a valid reparametrisation: a level that starts from carried
+ * messages still reports a true lower bound, only its speed depends on them.
+ *
+ * A message row is a function on the labels of its RECEIVING node (stereo_trws_state_receivers_host).  Old label i
+ * of a node lies at off_old[i] on that node's offset axis, new label j of node r at shift[r] + stretch * off_new[j]
+ * on the old axis of the node r inherits from.  For every new edge e, in fp64 without contraction, in this order:
+ *   s = edge_src ? edge_src[e] : e;  r = receiver_new[e];  t = shift[r]
+ *   s < 0 or t not finite: the row is all zeros.  Otherwise for j = 0 .. K_new - 1:
+ *     u = t + stretch * off_new[j]                                  (the multiply first)
+ *     u <= off_old[0]:          v_j = M_old[s][0]
+ *     u >= off_old[K_old - 1]:  v_j = M_old[s][K_old - 1]           (flat outside the old range, as a truncated
+ *                                                                    pairwise term makes messages there)
+ *     else, i the largest index with off_old[i] <= u and w = (u - off_old[i]) / (off_old[i + 1] - off_old[i]):
+ *                               v_j = M_old[s][i] + w * (M_old[s][i + 1] - M_old[s][i])
+ *   m = min_j v_j, the first minimum (strict <, so a NaN never wins);  M_new[e][j] = gain * (v_j - m)
+ * An edge_src entry >= E_old or a receiver_new entry outside 0 .. N_new - 1 reads nothing: its row is zero and it
+ * counts once in `bad`.
+ *
+ * off_old: K_old doubles, strictly ascending, need not contain 0 (1 <= K_old <= 4096: a full-range solve with shared
+ * positions may be the source, its disparities the offsets).  off_new: K_new doubles, strictly ascending,
+ * 1 <= K_new <= stereo_band_max_offsets().  shift: N_new doubles.  edge_src, receiver_new: E_new int32; edge_src may
+ * be NULL (s = e), then E_old == E_new is required.  E_old, E_new < 2^31.
+ *
+ * Refused with a message that names the argument, before the device is looked for: a NULL required array; a K out of
+ * range; offsets not finite or not strictly ascending; stretch or gain not finite or not positive; E_old != E_new
+ * without edge_src; an output (M_new, bad) that is also an input.
+ *
+ * stereo_band_carry: host arrays in and out, the count of offending edges in *bad (may be NULL).
+ * stereo_band_carry_device: device arrays of the caller, launched on `stream` (hipStream_t, NULL = default) without
+ * waiting for it; the offsets are passed twice as in stereo_band_inputs_device (host: checked; device: read by the
+ * kernel); `bad` (device int32, may be NULL) is set to zero on `stream` first. */
+int stereo_band_carry(const double *M_old, int64_t E_old, int K_old, const double *off_old, const int32_t *edge_src,
+                      const int32_t *receiver_new, int64_t N_new, const double *shift, double stretch, double gain,
+                      const double *off_new, int K_new, int64_t E_new, double *M_new, int64_t *bad, char *err,
+                      size_t errcap);
+int stereo_band_carry_device(const double *M_old, int64_t E_old, int K_old, const double *off_old,
+                             const double *d_off_old, const int32_t *edge_src, const int32_t *receiver_new,
+                             int64_t N_new, const double *shift, double stretch, double gain, const double *off_new,
+                             const double *d_off_new, int K_new, int64_t E_new, double *M_new, int32_t *bad,
+                             void *stream, char *err, size_t errcap);
+/* Host only (no device): receiver[e] = the node on whose labels the message row of edge e is indexed in a solver
+ * state of `phase` of a plan created with (N, E, conn, message_mode): the endpoint LATER in the
+ * plan's node order in phases 1 and 2 (`head` of stereo_trws_analyze), the EARLIER one (`tail`) in phase 0.
+ * STEREO_TRWS_ORDER_INDEX in message_mode is honoured. */
+int stereo_trws_state_receivers_host(int64_t N, int64_t E, const uint32_t *conn, int message_mode, int phase,
+                                     int32_t *receiver, char *err, size_t errcap);
 
 /* ---- band refinement around a solved plane map ----------------------------------------- *
  * No reference counterpart as a call; the problem it builds is the reference's own energy restricted to K

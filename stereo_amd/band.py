@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import carry as carry_mod
 from . import terms as T
 from ._lib import StereoHipError
 from .consistency import _device_map, _map, _p, _stream
@@ -202,13 +203,13 @@ def check_levels(levels):
 
 class BandResult:
     """refine_band's result: `dispmap` (H x W, the last level's refined map), `maps` (one per level) and per level
-    `energy`, `lower_bound`, `iterations`, `labels` (N, one based) and `paths` (the kernel family that ran,
-    TrwsPlan.path())."""
+    `energy`, `lower_bound`, `iterations`, `labels` (N, one based), `paths` (the kernel family that ran,
+    TrwsPlan.path()) and `carried` (the level started from the previous level's messages)."""
 
     def __init__(self):
-        self.dispmap = None
+        self.dispmap = self.stage = None
         self.maps, self.labels = [], []
-        self.energy, self.lower_bound, self.iterations, self.paths = [], [], [], []
+        self.energy, self.lower_bound, self.iterations, self.paths, self.carried = [], [], [], [], []
 
 
 class BandProblem:
@@ -236,12 +237,29 @@ class BandProblem:
         self.d_alphas = torch.from_numpy(alphas).cuda()
         self.d_base = torch.from_numpy(np.ascontiguousarray(base.T)).cuda()
         self.offsets = self.d_offsets = self.d_unary = self.d_q = self.d_qprim = None
+        self.d_receiver = self.h_receiver = self.d_built_base = None
 
-    def build(self, offsets, plan, tol, zero_columns=None):
+    def receiver(self):
+        """The receiving node of every edge's message row in a plan at rest (phase 1), on the device: what the transfer
+        of carried messages indexes `shift` with.  Worked out once (plans of this problem use the default node order)."""
+        import torch
+        if self.d_receiver is None:
+            self.d_receiver = torch.from_numpy(self.receiver_host()).cuda()
+        return self.d_receiver
+
+    def receiver_host(self):
+        if self.h_receiver is None:
+            self.h_receiver = carry_mod.receivers(self.N, self.conn, 1)
+        return self.h_receiver
+
+    def build(self, offsets, plan, tol, zero_columns=None, carry=None):
         """The inputs of the level `offsets` around the current base, bound to `plan`.  zero_columns: a bool tensor (N,),
-        pixels whose unary column is set to zero."""
+        pixels whose unary column is set to zero.  carry: a carry.Carry of the previous stage (whose messages were saved
+        BEFORE this call: a plan is reused for equal K and the bind wipes it); the plan then starts from the transferred
+        messages as a state of phase 1 with 0 iterations, not from zero."""
         self.offsets = _vec(offsets, "offsets")
         self.d_offsets = to_device_vector(self.offsets)
+        self.d_built_base = self.d_base
         self.d_unary, self.d_q, self.d_qprim, _ = band_inputs_device(
             self.d_ncc, self.disparities, self.unary_weight, self.d_base, self.offsets, self.d_conn, self.layout,
             d_disparities=self.d_disparities, d_offsets=self.d_offsets)
@@ -251,6 +269,23 @@ class BandProblem:
         torch.cuda.current_stream().synchronize()
         plan.bind_device(self.d_unary.data_ptr(), self.d_alphas.data_ptr(), tol, d_q=self.d_q.data_ptr(),
                          d_qprim=self.d_qprim.data_ptr(), keepalive=[self.d_unary, self.d_q, self.d_qprim, self.d_alphas])
+        if carry is not None:
+            carry_mod.load_carried(plan, carry, self.offsets, self.receiver(), self.N, self.d_offsets)
+
+    def stage(self, plan):
+        """What the level built last leaves for the stage after it (carry.Stage): `plan`'s messages, saved on the device
+        now (the next build may bind the same plan, which wipes it), the level's offsets and the base they were measured
+        from.  To be called before or after apply().  None where the plan's state cannot be carried."""
+        d_m = carry_mod.save_messages(plan, self.N)
+        if d_m is None:
+            return None
+        return carry_mod.Stage(d_m, self.offsets, self.d_built_base.reshape(-1), self.conn, self.receiver_host(), (self.H, self.W))
+
+    def carry_from(self, stage, scales=False):
+        """The carry.Carry from `stage` into the next level around the current base (None without a stage).  The shift
+        is taken on the device from the two bases, so a base filled or otherwise edited in between is handled as well.
+        scales=True: the stage is the scale above (one box reduction coarser)."""
+        return carry_mod.carry_between(stage, self.d_base.reshape(-1), self.conn, self.receiver_host(), (self.H, self.W), scales)
 
     def apply(self, labels):
         """The base moved by the labels of the level built last -> the new base on the host, H x W."""
@@ -261,12 +296,15 @@ class BandProblem:
 
 
 def refine_band(ncc, disparities, unary_weight, base, kernel, tol, levels, maxiter, max_relgap, alphas=None, layout=0,
-                conn=None):
+                conn=None, carry=False, carry_start=None):
     """Refines the map `base` level by level: for each vector of offsets in `levels` the band problem around the current
     map is built on the device (stereo_band_inputs_device), bound to a TrwsPlan(kernel, K, N, conn) -- one plan per
     distinct K -- iterated up to `maxiter` times (`max_relgap` as in trws) and applied (stereo_band_apply_device); the
     refined map is the next level's base.  The volume goes to the device once; nothing K x N or K x E touches the host.
-    conn: 2 x E zero based, default the image grid (construct_neighborhood).  -> BandResult."""
+    conn: 2 x E zero based, default the image grid (construct_neighborhood).  carry=True: every level after the first
+    starts from the previous level's messages, moved onto its own offsets, not from zero; the last
+    level's carry.Stage is then kept as the result's `stage`.  carry_start: (a carry.Stage, scales) the first level
+    starts from -- a solve on this grid, or with scales=True on the grid one box reduction coarser.  -> BandResult."""
     levels = check_levels(levels)
     base = _map(base, "base")
     H, W = base.shape
@@ -274,18 +312,22 @@ def refine_band(ncc, disparities, unary_weight, base, kernel, tol, levels, maxit
     prob = BandProblem(ncc, disparities, unary_weight, base, conn, alphas, layout)
     out = BandResult()
     plans = {}
+    previous = prob.carry_from(carry_start[0], carry_start[1]) if carry_start is not None else None
     try:
         for offsets in levels:
             K = offsets.shape[0]
             if K not in plans:
                 plans[K] = TrwsPlan(int(kernel), K, prob.N, prob.conn)
             plan = plans[K]
-            prob.build(offsets, plan, tol)
+            prob.build(offsets, plan, tol, carry=previous)
+            out.carried.append(previous is not None)
             plan.iterate(maxiter, max_relgap)
             labels, en, lb, it = plan.result()
             out.paths.append(plan.path())
             out.labels.append(labels); out.energy.append(en); out.lower_bound.append(lb); out.iterations.append(it)
             out.maps.append(prob.apply(labels))
+            out.stage = prob.stage(plan) if carry else None
+            previous = prob.carry_from(out.stage)
         out.dispmap = out.maps[-1]
     finally:
         for plan in plans.values():

@@ -172,20 +172,23 @@ class ViewResult:
     entry per band level).  After band levels `labels` are the last level's band labels and `dispmap`, `status`,
     `residual`, `filled` and `source` those of the last level's refined map; `maps` keeps the map of every pass and
     `paths` the kernel family that ran it (TrwsPlan.path()).  A pyramid level that starts from an expanded map
-     keeps that map and the expansion's candidate numbers as `expanded` and `expand_source`."""
+     keeps that map and the expansion's candidate numbers as `expanded` and `expand_source`.  `carried`
+    has one entry per pass: the pass started from the previous stage's messages."""
 
     def __init__(self):
         self.labels = self.dispmap = self.status = self.residual = self.filled = self.source = None
         self.expanded = self.expand_source = None
-        self.energy, self.lower_bound, self.iterations, self.maps, self.paths = [], [], [], [], []
+        self.energy, self.lower_bound, self.iterations, self.maps, self.paths, self.carried = [], [], [], [], [], []
 
 
 class PairResult:
-    """solve_pair_ncc's result: `left` and `right` (ViewResult) and `times` (seconds per stage)."""
+    """solve_pair_ncc's result: `left` and `right` (ViewResult) and `times` (seconds per stage); with carry, `stages`:
+    per view what the last pass leaves for a stage after it (carry.Stage, or None)."""
 
     def __init__(self):
         self.left, self.right = ViewResult(), ViewResult()
         self.times = {}
+        self.stages = [None, None]
 
     @property
     def views(self):
@@ -209,31 +212,40 @@ def collect_views(out, plans, to_map, check_tol, stage):
 
 
 def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
-                    zero_occluded=False):
+                    zero_occluded=False, carry=False, stages=None, scales=False):
     """The band passes of a pair solve: for every vector of offsets both views (`problems`: one band.BandProblem each,
     standing around the view's current map) build their band problem on the device and run up to `maxiter` iterations
     as a two-member TrwsBatch; the labels are applied, the refined maps checked with `check_tol` and filled
     (collect_views).  band_plans: {K: [plan, plan]}, filled here, closed by the caller.  zero_occluded: the unary
-    columns of the pixels the preceding check found occluded are zeroed."""
+    columns of the pixels the preceding check found occluded are zeroed.
+    carry: every level after the first starts from the view's previous level's messages; the members
+    take them as batch members take any state.  stages: per view the carry.Stage the FIRST level starts from (None:
+    from zero) -- a solve on this grid, or with scales=True on the grid one box reduction coarser.  out.stages: per
+    view the Stage of the last level (with carry)."""
     import torch
     N = problems[0].N
+    previous = [prob.carry_from(st, scales) for prob, st in zip(problems, stages)] if stages is not None else [None, None]
     for level, offsets in enumerate(band_levels):
         t0 = time.perf_counter()
         Kb = offsets.shape[0]
         if Kb not in band_plans:
             band_plans[Kb] = [TrwsPlan(int(kernel), Kb, N, conn) for _ in range(2)]
-        for prob, plan, view in zip(problems, band_plans[Kb], out.views):
+        for prob, plan, view, prev in zip(problems, band_plans[Kb], out.views, previous):
             occluded = torch.from_numpy(view.status.T.reshape(-1) == OCCLUDED).cuda() if zero_occluded else None
-            prob.build(offsets, plan, tol, zero_columns=occluded)
+            prob.build(offsets, plan, tol, zero_columns=occluded, carry=prev)
+            view.carried.append(prev is not None)
         with TrwsBatch(band_plans[Kb]) as batch:
             batch.iterate(maxiter, max_relgap)
+        if carry:
+            out.stages = [prob.stage(plan) for prob, plan in zip(problems, band_plans[Kb])]
         out.times["band_%d" % (level + 1)] = time.perf_counter() - t0
         collect_views(out, band_plans[Kb], lambda i, labels: problems[i].apply(labels), check_tol,
                       "band_%d_check_fill" % (level + 1))
+        previous = [prob.carry_from(st) for prob, st in zip(problems, out.stages)] if carry else [None, None]
 
 
 def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_relgap, check_tol=1.0, refine_iters=0,
-                   band_levels=None, smooth_weight=1.0):
+                   band_levels=None, smooth_weight=1.0, carry=False):
     """Both views of a rectified pair: two NCC unary volumes, two TRW-S plans on the image grid with the shared
     positions `disparities`, iterated as one TrwsBatch; labels to maps; each map checked against the other and filled.
     refine_iters > 0: per view, the solver state is saved, the unary columns of the occluded pixels are zeroed and
@@ -243,7 +255,10 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
     the band problem around their map on the device, from their own volume, and run up to `maxiter` iterations as a
     two-member TrwsBatch; the refined maps are checked with check_tol and filled.  With refine_iters > 0 the unary
     columns of the pixels the preceding check found occluded are zeroed in the band as well.
-    smooth_weight: the weight of every edge (a pyramid level's model)."""
+    smooth_weight: the weight of every edge (a pyramid level's model).
+    carry=True: the first band level starts from the full-range solve's messages (its disparities are the old offsets,
+    the old base is zero), every later one from the level before it; the result's `stages` keeps what
+    the last pass leaves.  The full-range passes themselves are what they are without it."""
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
     if len(images) != 2:
         raise StereoHipError("solve_pair_ncc: images must be the two views of a pair, left first (got %d)" % len(images))
@@ -277,6 +292,8 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
             batch.iterate(maxiter, max_relgap)
         out.times["solve"] = clock() - t0
         collect_views(out, plans, by_index, check_tol, "check_fill")
+        for view in out.views:
+            view.carried.append(False)
         if refine_iters > 0:
             t0 = clock()
             for plan, unary, view in zip(plans, unaries, out.views):
@@ -287,11 +304,16 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
                 batch.iterate(refine_iters, max_relgap)
             out.times["refine"] = clock() - t0
             collect_views(out, plans, by_index, check_tol, "refine_check_fill")
+            for view in out.views:
+                view.carried.append(False)
+        if carry:
+            from . import carry as carry_mod
+            out.stages = [carry_mod.full_range_stage(plan, disparities, conn, (H, W)) for plan in plans]
         if band_levels is not None:
             problems = [band.BandProblem(vol, disparities, unary_weight, view.dispmap, conn, alphas, layout=1)
                         for vol, view in zip(volumes, out.views)]
             run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
-                            zero_occluded=refine_iters > 0)
+                            zero_occluded=refine_iters > 0, carry=carry, stages=out.stages if carry else None)
     finally:
         for plan in plans + [p for pair in band_plans.values() for p in pair]:
             plan.close()

@@ -354,11 +354,11 @@ class dispmap_super:
         self.filled_dispmap, self.filled_source = consistency.lr_fill(d, self.consistency) if fill else (None, None)
         return self.consistency, self.filled_dispmap
 
-    def refine_band(self, levels, maxiter=None):
+    def refine_band(self, levels, maxiter=None, carry=False):
         raise StereoHipError("refine_band: %s does not take its unary from the NCC sampler; band refinement is defined "
                              "for dispmap_ncc" % type(self).__name__)
 
-    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided"):
+    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none"):
         raise StereoHipError("solve_pyramid: %s reaches its second view through a projection, and its refinement is the "
                              "plane band; the image pyramid is defined for dispmap_ncc" % type(self).__name__)
 
@@ -367,13 +367,14 @@ class dispmap_super:
         planes' disparity units or None for 'as they are')."""
         raise StereoHipError("refine_plane_band: %s names no unary source" % type(self).__name__)
 
-    def refine_plane_band(self, levels, maxiter=None):
+    def refine_plane_band(self, levels, maxiter=None, carry=False):
         """Sub-pixel refinement that keeps each pixel's plane (no reference counterpart): for every
         vector of offsets in `levels` (strictly ascending, containing 0) TRW-S chooses per pixel among the pixel's own
         plane moved by an offset along the disparity axis, [a b c d - c offset], with this object's unary, kernel,
         tolerance, smoothness weights, rescaling and max_relgap, up to `maxiter` (default self.maxiter) iterations per
         level.  The levels are in the units of the object's smoothness term: disparities for dispmap_ncc, the rescaled
-        units in which disp_thresh lives for dispmap_globalstereo.  The result goes in through the assignment setter;
+        units in which disp_thresh lives for dispmap_globalstereo.  carry=True: every level after the first starts from
+        the previous level's messages (DESIGN.md 6.5).  The result goes in through the assignment setter;
         returns plane_band.refine_plane_band's PlaneBandResult (planes in the object's internal columns)."""
         from . import plane_band
         levels = plane_band.check_levels(levels)
@@ -383,7 +384,7 @@ class dispmap_super:
         out = plane_band.refine_plane_band(source, self.assignment, self._kernel, self.tol, levels,
                                            self.maxiter if maxiter is None else maxiter, self._max_relgap,
                                            alphas=self.smooth_weights, conn=self.neighborhood, d_min=self.d_min,
-                                           d_step=self.d_step)
+                                           d_step=self.d_step, carry=carry)
         self.assignment = out.planes
         return out
 
@@ -460,27 +461,29 @@ class dispmap_ncc(dispmap_super):
         """H x W x D: unary_weight * (1 - ncc), the unary of every fronto-parallel label, in the image's own columns."""
         return self._unary_weight * (1.0 - (self.ncc[:, ::-1] if self._mirrored else self.ncc))
 
-    def refine_band(self, levels, maxiter=None):
+    def refine_band(self, levels, maxiter=None, carry=False):
         """Sub-pixel refinement of the current map (no reference counterpart): for every vector of offsets in
         `levels` (strictly ascending, containing 0) TRW-S chooses per pixel among current disparity + offset, with this
         object's volume, unary weight, kernel, tolerance, smoothness weights and max_relgap, up to `maxiter` (default
-        self.maxiter) iterations per level.  The result goes in through set_disparity; returns band.refine_band's
+        self.maxiter) iterations per level.  carry=True: every level after the first starts from the previous level's
+        messages.  The result goes in through set_disparity; returns band.refine_band's
         BandResult (its maps are in the object's internal columns: flipped for a mirrored object)."""
         from . import band
         base = self.disparitymap_from_assignment(self.assignment).reshape(self.sz[1], self.sz[0]).T    # internal columns
         out = band.refine_band(self.ncc, self.disparities, self._unary_weight, base, self._kernel, self._tol, levels,
                                self.maxiter if maxiter is None else maxiter, self._max_relgap, alphas=self.smooth_weights,
-                               conn=self.neighborhood)
+                               conn=self.neighborhood, carry=carry)
         self.set_disparity(self._unflip(out.dispmap))
         return out
 
-    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided"):
+    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none"):
         """The map from the image pyramid (no reference counterpart): this view solved at the scale
         2^levels with the level model of this object's kernel, unary weight and tolerance, carried up one scale at a time
         (`expand`: 'guided' by the reference image, or 'nearest') and refined at every finer level l by the band levels
         bands[l] (default one band, [-2 .. 2]); `maxiter` (default self.maxiter) is a scalar or one value per scale, level
         0 first; max_relgap is the object's.  A level's edges all weigh s^(k - 1): an object with other smooth_weights
-        is refused.  A mirrored object works in its own flipped columns.  The result goes in through set_disparity;
+        is refused.  A mirrored object works in its own flipped columns.  carry: 'none', 'levels' or 'scales'
+        (pyramid.check_carry, DESIGN.md 6.5).  The result goes in through set_disparity;
         returns pyramid.solve_view_ncc_pyramid's ViewPyramidResult (maps in the object's internal columns)."""
         from . import pyramid
         if not np.all(self.smooth_weights == 1.0):
@@ -488,7 +491,7 @@ class dispmap_ncc(dispmap_super):
                                  "do not carry to another scale")
         out = pyramid.solve_view_ncc_pyramid(self.images, self.disparities, self._kernel, self._unary_weight, self._tol,
                                              levels, self.maxiter if maxiter is None else maxiter, self._max_relgap,
-                                             bands=bands, expand=expand)
+                                             bands=bands, expand=expand, carry=carry)
         self.set_disparity(self._unflip(out.dispmap))
         return out
 

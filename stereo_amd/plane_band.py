@@ -17,6 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import carry as carry_mod
 from . import terms as T
 from ._lib import StereoHipError
 from .band import _conn, _flat, _vec, _volume, check_levels, to_device_vector
@@ -245,12 +246,13 @@ def plane_band_apply_device(planes, labels, offsets, refined=None, bad=None, str
 
 class PlaneBandResult:
     """refine_plane_band's result: `planes` (4 x N, the last level's refined planes), `plane_maps` (one per level) and per
-    level `energy`, `lower_bound`, `iterations`, `labels` (N, one based) and `paths` (TrwsPlan.path())."""
+    level `energy`, `lower_bound`, `iterations`, `labels` (N, one based), `paths` (TrwsPlan.path()) and `carried` (the
+    level started from the previous level's messages)."""
 
     def __init__(self):
         self.planes = None
         self.plane_maps, self.labels = [], []
-        self.energy, self.lower_bound, self.iterations, self.paths = [], [], [], []
+        self.energy, self.lower_bound, self.iterations, self.paths, self.carried = [], [], [], [], []
 
 
 class PlaneBandProblem:
@@ -273,10 +275,30 @@ class PlaneBandProblem:
         self.d_conn = torch.from_numpy(self.conn.reshape(-1, order="F").view(np.int32)).cuda()
         self.d_alphas = torch.from_numpy(alphas).cuda()
         self.d_planes = torch.from_numpy(np.array(planes.T, order="C")).cuda()       # (N, 4): 4 x N column major, a copy
-        self.offsets = self.d_offsets = self.d_unary = self.d_q = self.d_qprim = None
+        self.offsets = self.d_offsets = self.d_unary = self.d_q = self.d_qprim = self.d_receiver = None
 
-    def build(self, offsets, plan, tol):
-        """The inputs of the level `offsets` around the current planes, bound to `plan`."""
+    def receiver(self):
+        """The receiving node of every edge's message row in a plan at rest (phase 1), on the device (carry.receivers)."""
+        import torch
+        if self.d_receiver is None:
+            self.d_receiver = torch.from_numpy(carry_mod.receivers(self.N, self.conn, 1)).cuda()
+        return self.d_receiver
+
+    def carry_from(self, plan, labels):
+        """The carry.Carry from the level built last (solved by `plan` with `labels`, one based) into the next one; to
+        be called before the next build.  A plane moved along the disparity axis moves its own pixel's disparity by
+        exactly that offset, so the new level's offset 0 at pixel r lies at offsets[labels_r - 1] on the old axis.  None
+        where the plan's state cannot be carried."""
+        import torch
+        d_m = carry_mod.save_messages(plan, self.N)
+        if d_m is None:
+            return None
+        index = torch.from_numpy(np.asarray(labels).reshape(-1).astype(np.int64) - 1).cuda()
+        return carry_mod.Carry(d_m, self.offsets, self.d_offsets[index].contiguous())
+
+    def build(self, offsets, plan, tol, carry=None):
+        """The inputs of the level `offsets` around the current planes, bound to `plan`.  carry: a carry.Carry of the
+        previous level; the plan then starts from the transferred messages, not from zero."""
         import torch
         self.offsets = _vec(offsets, "offsets")
         self.d_offsets = to_device_vector(self.offsets)
@@ -285,6 +307,8 @@ class PlaneBandProblem:
         torch.cuda.current_stream().synchronize()
         plan.bind_device(self.d_unary.data_ptr(), self.d_alphas.data_ptr(), tol, d_q=self.d_q.data_ptr(),
                          d_qprim=self.d_qprim.data_ptr(), keepalive=[self.d_unary, self.d_q, self.d_qprim, self.d_alphas])
+        if carry is not None:
+            carry_mod.load_carried(plan, carry, self.offsets, self.receiver(), self.N, self.d_offsets)
 
     def apply(self, labels):
         """The planes moved by the labels of the level built last -> the new planes on the host, 4 x N."""
@@ -294,31 +318,36 @@ class PlaneBandProblem:
         return np.asfortranarray(self.d_planes.cpu().numpy().T)
 
 
-def refine_plane_band(source, planes, kernel, tol, levels, maxiter, max_relgap, alphas=None, conn=None, d_min=0.0, d_step=0.0):
+def refine_plane_band(source, planes, kernel, tol, levels, maxiter, max_relgap, alphas=None, conn=None, d_min=0.0, d_step=0.0,
+                      carry=False):
     """Refines the plane map `planes` (4 x N) level by level: for each vector of offsets in `levels` (the planes' own
     disparity units) the plane-band problem around the current planes is built on the device
     (stereo_plane_band_inputs_*_device), bound to a TrwsPlan(kernel, K, N, conn) -- one plan per distinct K -- iterated up
     to `maxiter` times (`max_relgap` as in trws) and applied (stereo_plane_band_apply_device); the refined planes are
     the next level's.  The source's data goes to the device once; nothing K x N or K x E touches the host.  conn: 2 x E
     zero based, default the image grid (construct_neighborhood); d_min / d_step: the rescaling of the positions and of
-    the globalstereo unary.  -> PlaneBandResult."""
+    the globalstereo unary.  carry=True: every level after the first starts from the previous level's messages, moved
+    onto its own offsets, not from zero.  -> PlaneBandResult."""
     levels = check_levels(levels)
     source = _source(source)
     conn = T.construct_neighborhood(source.H, source.W) if conn is None else conn
     prob = PlaneBandProblem(source, planes, conn, alphas, d_min, d_step)
     out = PlaneBandResult()
     plans = {}
+    previous = None
     try:
         for offsets in levels:
             K = offsets.shape[0]
             if K not in plans:
                 plans[K] = TrwsPlan(int(kernel), K, prob.N, prob.conn)
             plan = plans[K]
-            prob.build(offsets, plan, tol)
+            prob.build(offsets, plan, tol, carry=previous)
+            out.carried.append(previous is not None)
             plan.iterate(maxiter, max_relgap)
             labels, en, lb, it = plan.result()
             out.paths.append(plan.path())
             out.labels.append(labels); out.energy.append(en); out.lower_bound.append(lb); out.iterations.append(it)
+            previous = prob.carry_from(plan, labels) if carry else None
             out.plane_maps.append(prob.apply(labels))
         out.planes = out.plane_maps[-1]
     finally:

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from . import band
+from . import carry as carry_mod
 from . import consistency
 from . import terms as T
 from ._lib import StereoHipError
@@ -222,6 +223,17 @@ def check_plan(levels, maxiter, bands, expand):
     return levels, maxiter, checked, MODES[expand]
 
 
+CARRY = ("none", "levels", "scales")
+
+
+def check_carry(carry):
+    """'none': every stage starts from zero messages; 'levels': the bands of one scale carry from one to the next;
+    'scales': also the last stage of a scale into the first band of the next finer one."""
+    if carry not in CARRY:
+        raise StereoHipError("pyramid: carry must be 'none', 'levels' or 'scales' (got %r)" % (carry,))
+    return carry
+
+
 def reduce_images(images, levels):
     """Every image reduced `levels` times on the device -> per level 0 .. levels the list of host images (level 0: the
     inputs as float64) and the list of their device tensors."""
@@ -268,7 +280,7 @@ class PyramidResult:
 
 
 def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, levels, maxiter, max_relgap, bands=None,
-                           expand="guided", check_tol=1.0):
+                           expand="guided", check_tol=1.0, carry="none"):
     """Both views of a rectified pair, coarse to fine.  Both images are reduced `levels` times (1 .. 5)
     on the device; solve_pair_ncc runs at the coarsest scale with that level's model (level_model, level_disparities);
     then for each finer level l each view's map is expanded with the view's own images of the two scales (`expand`:
@@ -277,8 +289,11 @@ def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
     (consistency.run_band_levels, the loop of solve_pair_ncc(band_levels=)), with the level's volume from pair_volumes
     on the level's images; every pass ends in a cross-check with check_tol / 2^l and a fill.  The caller's sub-pixel
     levels are further vectors in bands[0].  maxiter: a scalar, or one value per scale with level 0 first.
+    carry (check_carry): 'levels' carries the messages between the bands of one scale, 'scales' also from the last stage
+    of a scale into the first band of the next finer one; every view's `carried` says per pass whether it was.
     -> PyramidResult."""
     levels, maxiter, bands, mode = check_plan(levels, maxiter, bands, expand)
+    carry = check_carry(carry)
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
     if len(images) != 2:
         raise StereoHipError("solve_pair_ncc_pyramid: images must be the two views of a pair, left first (got %d)" % len(images))
@@ -303,7 +318,8 @@ def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
     t0 = clock()
     L = levels
     out.levels[L] = consistency.solve_pair_ncc(host[L], out.disparities[L], kernel, unary_weight, out.tol[L], maxiter[L],
-                                               max_relgap, check_tol=check_tol / (1 << L), smooth_weight=out.smooth_weight[L])
+                                               max_relgap, check_tol=check_tol / (1 << L), smooth_weight=out.smooth_weight[L],
+                                               carry=carry == "scales")
     out.times["level_%d" % L] = clock() - t0
     for l in range(levels - 1, -1, -1):
         t0 = clock()
@@ -323,7 +339,8 @@ def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
             problems = [band.BandProblem(vol, out.disparities[l], unary_weight, view.dispmap, conn, alphas, layout=1)
                         for vol, view in zip(volumes, res.views)]
             consistency.run_band_levels(res, problems, bands[l], band_plans, kernel, conn, out.tol[l], maxiter[l], max_relgap,
-                                        check_tol / (1 << l))
+                                        check_tol / (1 << l), carry=carry != "none",
+                                        stages=out.levels[l + 1].stages if carry == "scales" else None, scales=True)
         finally:
             for plan in (p for pair in band_plans.values() for p in pair):
                 plan.close()
@@ -336,23 +353,25 @@ def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
 class ViewPyramidResult:
     """solve_view_ncc_pyramid's result: `dispmap` (level 0's last map) and per level l, index l: `maps` (the maps of the
     level's passes), `expanded` / `expand_source` (None at the coarsest level), `labels`, `energy`, `lower_bound`,
-    `iterations`, `paths` (lists per pass), `disparities`, `tol`, `smooth_weight`."""
+    `iterations`, `paths`, `carried` (lists per pass), `disparities`, `tol`, `smooth_weight`."""
 
     def __init__(self, n):
         self.dispmap = None
-        for name in ("maps", "labels", "energy", "lower_bound", "iterations", "paths"):
+        for name in ("maps", "labels", "energy", "lower_bound", "iterations", "paths", "carried"):
             setattr(self, name, [[] for _ in range(n)])
         self.expanded, self.expand_source = [None] * n, [None] * n
         self.disparities, self.tol, self.smooth_weight = [], [], []
 
 
 def solve_view_ncc_pyramid(images, disparities, kernel, unary_weight, tol, levels, maxiter, max_relgap, bands=None,
-                           expand="guided"):
+                           expand="guided", carry="none"):
     """One view, coarse to fine: `images` = (the reference image, the other one), a pixel at column x with disparity d
     matching column x - d of the other.  The steps of solve_pair_ncc_pyramid for one view with solo plans: the volume
     of a level is terms.ncc_volume on the level's images, the coarsest level one TrwsPlan on the level's slices, every
-    finer level band.refine_band around the expanded map.  No cross-check.  -> ViewPyramidResult."""
+    finer level band.refine_band around the expanded map.  No cross-check.  carry: as in solve_pair_ncc_pyramid.
+    -> ViewPyramidResult."""
     levels, maxiter, bands, mode = check_plan(levels, maxiter, bands, expand)
+    carry = check_carry(carry)
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
     level_model(kernel, tol, 0)
     _lib.require_device()
@@ -373,6 +392,8 @@ def solve_view_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
         plan.iterate(maxiter[L], max_relgap)
         labels, en, lb, it = plan.result()
         out.paths[L].append(plan.path())
+        out.carried[L].append(False)
+        stage = carry_mod.full_range_stage(plan, out.disparities[L], conn, (H, W)) if carry == "scales" else None
     finally:
         plan.close()
     out.labels[L].append(labels); out.energy[L].append(en); out.lower_bound[L].append(lb); out.iterations[L].append(it)
@@ -384,8 +405,10 @@ def solve_view_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
         conn = T.construct_neighborhood(H, W)
         vol = T.ncc_volume(host[l][0], host[l][1], out.disparities[l], 2, layout=1)
         r = band.refine_band(vol, out.disparities[l], unary_weight, out.expanded[l], kernel, out.tol[l], bands[l], maxiter[l],
-                             max_relgap, alphas=np.ones(conn.shape[1]) * out.smooth_weight[l], layout=1, conn=conn)
-        out.maps[l], out.labels[l], out.energy[l] = r.maps, r.labels, r.energy
+                             max_relgap, alphas=np.ones(conn.shape[1]) * out.smooth_weight[l], layout=1, conn=conn,
+                             carry=carry != "none", carry_start=(stage, True) if carry == "scales" else None)
+        stage = r.stage
+        out.maps[l], out.labels[l], out.energy[l], out.carried[l] = r.maps, r.labels, r.energy, r.carried
         out.lower_bound[l], out.iterations[l], out.paths[l] = r.lower_bound, r.iterations, r.paths
         current = r.dispmap
     out.dispmap = current
