@@ -34,8 +34,9 @@ extern "C" {
  * 13: stereo_plane_band_inputs_ncc / _globalstereo / stereo_plane_band_apply (band refinement around a solved plane map).
  * 14: stereo_pyramid_reduce / stereo_pyramid_expand (image pyramid: box reduction, map expansion).
  * 15: stereo_band_carry / stereo_band_carry_device (messages carried from one band level or pyramid scale to the
- * next), stereo_trws_state_receivers_host. */
-#define STEREO_HIP_ABI_VERSION 15
+ * next), stereo_trws_state_receivers_host.  16: stereo_pyramid_reduce_volume / _device (image pyramid: a coarser
+ * level's NCC volume as the block mean of the finer one). */
+#define STEREO_HIP_ABI_VERSION 16
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -880,6 +881,35 @@ int stereo_pyramid_reduce_device(const double *im, int H, int W, int C, double *
 int stereo_pyramid_expand_device(const double *d_coarse, int Hc, int Wc, int H, int W, int mode,
                                  const double *im_fine, const double *im_coarse, int C, double *out,
                                  int32_t *source, void *stream, char *err, size_t errcap);
+
+/* ---- image pyramid: a level's volume as the block mean of the finer volume ------------ *
+ * No reference counterpart.  `ncc` is an NCC volume of H x W pixels and D slices at `disparities`, layout 0
+ * (H x W x D, element (y, x, k) at y + H*(x + W*k)) or 1 (D x N, element (y, x, k) at k + D*(y + H*x)), as
+ * elsewhere.  Hc = (H + 1) / 2, Wc = (W + 1) / 2.  v(y, x, j) is the NCC sampler's value (dispmap_ncc.m:222-249,
+ * as stereo_ncc_unary evaluates it before the weighting) at pixel (y, x) and disparity sample_at[j]: the nearest
+ * slice with ties to the larger index, the parabola through it and its two neighbours, the slice itself at the first
+ * and the last one, -1e6 outside [min, max] of `disparities`.  Then
+ *     out(yc, xc, j) = 0.25 * (((v00 + v10) + v01) + v11),  v_ik = v(min(2 yc + i, H - 1), min(2 xc + k, W - 1), j)
+ * (i the row offset, k the column offset): stereo_pyramid_reduce's order and replication.  `out` has the input's
+ * layout with the sizes Hc, Wc, Kc: layout 0 (yc, xc, j) at yc + Hc*(xc + Wc*j), layout 1 at j + Kc*(yc + Hc*xc).
+ * fp64 without FMA contraction in the order written here: bit for bit the same lines in any language.
+ * With sample_at = 2 * (the coarser level's slices), clipped to the finer range, a coarse pixel's value is the mean
+ * over its fine pixels at the doubled disparity, so unary_weight * (1 - out) is the mean of their unaries: the level
+ * model's unary half.
+ *
+ * Refused with a message, before the device is looked for: H, W, D or Kc below 1; H*W >= 2^31; Hc*Wc*Kc or H*W*D
+ * >= 2^63 / 8; a layout other than 0 / 1; NULL for a required array; a value of `disparities` or `sample_at` that
+ * is not finite; out == ncc. */
+int stereo_pyramid_reduce_volume(const double *ncc, int H, int W, int D, int layout, const double *disparities,
+                                 const double *sample_at, int Kc, double *out, char *err, size_t errcap);
+/* The same on device arrays of the caller, launched on `stream` (hipStream_t, NULL = default) without waiting for
+ * it.  The two short vectors are passed twice, as stereo_band_inputs_device takes its own: on the host
+ * (`disparities`, `sample_at`: checked; min, max and the order of the slices are taken from them) and in device
+ * memory (`d_disparities`, `d_sample_at`: the same values, which the kernels read). */
+int stereo_pyramid_reduce_volume_device(const double *ncc, int H, int W, int D, int layout, const double *disparities,
+                                        const double *d_disparities, const double *sample_at,
+                                        const double *d_sample_at, int Kc, double *out, void *stream, char *err,
+                                        size_t errcap);
 
 /* ---- device-resident fusion moves --------------------------------------- *
  * The state of one dispmap object kept in HBM across moves: connectivity, weights, points,

@@ -245,7 +245,7 @@ def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, m
 
 
 def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_relgap, check_tol=1.0, refine_iters=0,
-                   band_levels=None, smooth_weight=1.0, carry=False):
+                   band_levels=None, smooth_weight=1.0, carry=False, volumes=None):
     """Both views of a rectified pair: two NCC unary volumes, two TRW-S plans on the image grid with the shared
     positions `disparities`, iterated as one TrwsBatch; labels to maps; each map checked against the other and filled.
     refine_iters > 0: per view, the solver state is saved, the unary columns of the occluded pixels are zeroed and
@@ -258,7 +258,9 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
     smooth_weight: the weight of every edge (a pyramid level's model).
     carry=True: the first band level starts from the full-range solve's messages (its disparities are the old offsets,
     the old base is zero), every later one from the level before it; the result's `stages` keeps what
-    the last pass leaves.  The full-range passes themselves are what they are without it."""
+    the last pass leaves.  The full-range passes themselves are what they are without it.
+    volumes: the two D x N NCC volumes (left, right) to take in place of pair_volumes(images, disparities) -- a pyramid
+    level's block volumes."""
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
     if len(images) != 2:
         raise StereoHipError("solve_pair_ncc: images must be the two views of a pair, left first (got %d)" % len(images))
@@ -275,7 +277,12 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
     if band_levels is not None:
         from . import band
         band_levels = band.check_levels(band_levels)
-    volumes = pair_volumes(images, disparities)
+    if volumes is None:
+        volumes = pair_volumes(images, disparities)
+    else:
+        volumes = [np.asarray(v, dtype=np.float64) for v in volumes]
+        if len(volumes) != 2 or any(v.shape != (K, N) for v in volumes):
+            raise StereoHipError("solve_pair_ncc: volumes must be the two D x N volumes of the pair (%d x %d)" % (K, N))
     unaries = pair_unaries(images, disparities, unary_weight, volumes)
     out.times["volumes"] = clock() - t0
     conn = T.construct_neighborhood(H, W)

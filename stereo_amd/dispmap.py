@@ -358,7 +358,7 @@ class dispmap_super:
         raise StereoHipError("refine_band: %s does not take its unary from the NCC sampler; band refinement is defined "
                              "for dispmap_ncc" % type(self).__name__)
 
-    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none"):
+    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none", unary="images"):
         raise StereoHipError("solve_pyramid: %s reaches its second view through a projection, and its refinement is the "
                              "plane band; the image pyramid is defined for dispmap_ncc" % type(self).__name__)
 
@@ -476,22 +476,26 @@ class dispmap_ncc(dispmap_super):
         self.set_disparity(self._unflip(out.dispmap))
         return out
 
-    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none"):
+    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none", unary="images"):
         """The map from the image pyramid (no reference counterpart): this view solved at the scale
         2^levels with the level model of this object's kernel, unary weight and tolerance, carried up one scale at a time
         (`expand`: 'guided' by the reference image, or 'nearest') and refined at every finer level l by the band levels
         bands[l] (default one band, [-2 .. 2]); `maxiter` (default self.maxiter) is a scalar or one value per scale, level
         0 first; max_relgap is the object's.  A level's edges all weigh s^(k - 1): an object with other smooth_weights
         is refused.  A mirrored object works in its own flipped columns.  carry: 'none', 'levels' or 'scales'
-        (pyramid.check_carry, DESIGN.md 6.5).  The result goes in through set_disparity;
+        (pyramid.check_carry).  unary: 'images' (a level's volume is the NCC of the reduced images) or
+        'blocks' (the block means of this object's own volume; nothing is recomputed).  The result goes
+        in through set_disparity;
         returns pyramid.solve_view_ncc_pyramid's ViewPyramidResult (maps in the object's internal columns)."""
         from . import pyramid
+        unary = pyramid.check_unary(unary)
         if not np.all(self.smooth_weights == 1.0):
             raise StereoHipError("solve_pyramid: the level model gives every edge one weight; smooth_weights other than 1 "
                                  "do not carry to another scale")
         out = pyramid.solve_view_ncc_pyramid(self.images, self.disparities, self._kernel, self._unary_weight, self._tol,
                                              levels, self.maxiter if maxiter is None else maxiter, self._max_relgap,
-                                             bands=bands, expand=expand, carry=carry)
+                                             bands=bands, expand=expand, carry=carry, unary=unary,
+                                             volume=self.ncc if unary == "blocks" else None)
         self.set_disparity(self._unflip(out.dispmap))
         return out
 

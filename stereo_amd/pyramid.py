@@ -1,7 +1,9 @@
 """Image pyramid (no reference counterpart; the definitions: include/stereo_hip.h): the 2 x 2 box
 reduction of an image, the expansion of a coarse disparity map to the next finer scale, the model of a pyramid level
 and ``solve_pair_ncc_pyramid``: the pair solved at the coarsest scale, the maps carried up one scale at a time, band
-levels at every finer scale.
+levels at every finer scale.  ``reduce_volume`` / ``level_volumes`` make a coarser
+level's NCC volume as the 2 x 2 block mean of the finer one (``unary="blocks"``) where the default takes the NCC of the
+reduced images.
 
 Host forms take NumPy arrays: an image H x W x C (or H x W), a map H x W, any memory order.  Device forms take torch
 tensors of the current device in column-major storage: a map is a contiguous (W, H) tensor as lr_check_device takes
@@ -161,6 +163,66 @@ def expand_device(d_coarse, shape, mode="guided", im_fine=None, im_coarse=None, 
     return out, source
 
 
+# ---------------------------------------------------------------- a level's volume from the finer one
+
+def _short(v, what):
+    v = np.asarray(v, dtype=np.float64)
+    if v.ndim != 1:
+        raise StereoHipError("%s must be a vector" % what)
+    return np.ascontiguousarray(v)
+
+
+def _coarse_volume_shape(Hc, Wc, Kc, layout):
+    return (Hc, Wc, Kc) if layout == 0 else (Kc, Hc * Wc)
+
+
+def reduce_volume(vol, shape, disparities, sample_at, layout=0):
+    """stereo_pyramid_reduce_volume: the NCC volume `vol` of `shape` = (H, W) pixels with slices at `disparities`
+    (layout 0: H x W x D, layout 1: D x N) -> the volume of the coarse size whose slice j is the 2 x 2 block mean of the
+    sampler's values at the disparity sample_at[j], in the input's layout (Hc x Wc x Kc or Kc x Nc, Fortran order)."""
+    H, W = (int(v) for v in shape)
+    vol, D = band._volume(vol, layout, H, W)
+    disparities, sample_at = _short(disparities, "disparities"), _short(sample_at, "sample_at")
+    if disparities.shape[0] != D:
+        raise StereoHipError("reduce_volume: %d disparities for a volume of %d slices" % (disparities.shape[0], D))
+    Hc, Wc = coarse_size(H, W)
+    Kc = sample_at.shape[0]
+    out = np.zeros(_coarse_volume_shape(max(Hc, 0), max(Wc, 0), Kc, 0 if layout == 0 else 1), order="F")
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_pyramid_reduce_volume(_p(vol), C.c_int(H), C.c_int(W), C.c_int(D), C.c_int(int(layout)),
+                                                 _p(disparities), _p(sample_at), C.c_int(Kc), _p(out), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return out
+
+
+def reduce_volume_device(vol, shape, disparities, sample_at, layout=0, out=None, stream=None, d_disparities=None,
+                         d_sample_at=None):
+    """stereo_pyramid_reduce_volume_device: `vol` a flat float64 tensor of H * W * D elements in storage order, launched
+    on `stream` (a torch stream or a raw handle; default: torch's current stream) without waiting for it.  `disparities`
+    and `sample_at` are host vectors; `d_disparities` / `d_sample_at`: their device copies, made here when not given.
+    -> the flat tensor of Hc * Wc * Kc elements."""
+    import torch
+    H, W = (int(v) for v in shape)
+    disparities, sample_at = _short(disparities, "disparities"), _short(sample_at, "sample_at")
+    D, Kc = disparities.shape[0], sample_at.shape[0]
+    Hc, Wc = coarse_size(H, W)
+    vol = band._flat(vol, "vol", torch.float64, H * W * D)
+    made_here = d_disparities is None or d_sample_at is None
+    d_disparities = band.to_device_vector(disparities) if d_disparities is None else band._flat(d_disparities, "d_disparities", torch.float64, D)
+    d_sample_at = band.to_device_vector(sample_at) if d_sample_at is None else band._flat(d_sample_at, "d_sample_at", torch.float64, Kc)
+    if made_here and stream is not None:
+        torch.cuda.current_stream().synchronize()     # the copies ran on torch's current stream, the kernel will not
+    out = torch.empty(Hc * Wc * Kc, dtype=torch.float64, device=vol.device) if out is None else band._flat(out, "out", torch.float64, Hc * Wc * Kc)
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_pyramid_reduce_volume_device(vp(vol), C.c_int(H), C.c_int(W), C.c_int(D), C.c_int(int(layout)),
+                                                        _p(disparities), vp(d_disparities), _p(sample_at), vp(d_sample_at),
+                                                        C.c_int(Kc), vp(out), C.c_void_p(_stream(stream)), err,
+                                                        C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return out
+
+
 # ---------------------------------------------------------------- the level model (DESIGN.md 6.4)
 
 def level_model(kernel, tol, level):
@@ -180,6 +242,42 @@ def level_disparities(disparities, level):
         return disparities
     s = float(1 << int(level))
     return np.arange(math.floor(disparities.min() / s), math.ceil(disparities.max() / s) + 1, dtype=np.float64)
+
+
+def level_sample_at(finer, coarser):
+    """The finer level's disparities its coarser level's slices stand for: twice the slice, and for a slice whose doubled
+    value leaves the finer range the nearest end of it (so the sampler's -1e6 never enters a level's volume)."""
+    finer = np.asarray(finer, dtype=np.float64).reshape(-1)
+    return np.clip(2.0 * np.asarray(coarser, dtype=np.float64).reshape(-1), finer.min(), finer.max())
+
+
+def level_volumes(volume, shape, disparities, levels, layout=0):
+    """The NCC volumes of the levels 0 .. `levels` from the full-size one (`shape` = (H, W), slices `disparities`): each
+    level by reduce_volume_device from the one below it, as the images are reduced, with the slices of level_disparities
+    and the sample positions of level_sample_at.  A level's device buffer is released once the next one is made.
+    -> the list of host volumes in the input's layout, level 0 first (the input itself)."""
+    import torch
+    H, W = (int(v) for v in shape)
+    vol, _ = band._volume(volume, layout, H, W)
+    out = [vol]
+    d_vol = torch.from_numpy(vol.reshape(-1, order="F")).cuda()
+    for l in range(1, levels + 1):
+        finer, coarser = level_disparities(disparities, l - 1), level_disparities(disparities, l)
+        d_vol = reduce_volume_device(d_vol, (H, W), finer, level_sample_at(finer, coarser), layout)
+        H, W = coarse_size(H, W)
+        out.append(d_vol.cpu().numpy().reshape(_coarse_volume_shape(H, W, coarser.shape[0], layout), order="F"))
+    return out
+
+
+UNARY = ("images", "blocks")
+
+
+def check_unary(unary):
+    """'images': a level's volume is the NCC of the reduced images; 'blocks': the block mean of the
+    finer level's volume, the level model's own unary."""
+    if not isinstance(unary, str) or unary not in UNARY:
+        raise StereoHipError("pyramid: unary must be 'images' or 'blocks' (got %r)" % (unary,))
+    return unary
 
 
 def _check_offsets(v):
@@ -260,11 +358,13 @@ class PyramidResult:
     check, and below the coarsest scale `expanded` / `expand_source`, the map the level started from and the
     expansion's candidate numbers; `levels[l].times` has the level's seconds per stage.  `disparities[l]`, `tol[l]`,
     `smooth_weight[l]`: the level's model.  `left` / `right` are the views of level 0; `times` the seconds of the
-    stages outside a level (`reduce`) and per level (`level_<l>`)."""
+    stages outside a level (`reduce`; with unary 'blocks' also `volumes`: the full-size volumes and their reductions) and
+    per level (`level_<l>`); `unary`: where the levels' volumes came from (check_unary)."""
 
     def __init__(self):
         self.levels, self.disparities, self.tol, self.smooth_weight = [], [], [], []
         self.times = {}
+        self.unary = "images"
 
     @property
     def left(self):
@@ -280,7 +380,7 @@ class PyramidResult:
 
 
 def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, levels, maxiter, max_relgap, bands=None,
-                           expand="guided", check_tol=1.0, carry="none"):
+                           expand="guided", check_tol=1.0, carry="none", unary="images"):
     """Both views of a rectified pair, coarse to fine.  Both images are reduced `levels` times (1 .. 5)
     on the device; solve_pair_ncc runs at the coarsest scale with that level's model (level_model, level_disparities);
     then for each finer level l each view's map is expanded with the view's own images of the two scales (`expand`:
@@ -291,9 +391,12 @@ def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
     levels are further vectors in bands[0].  maxiter: a scalar, or one value per scale with level 0 first.
     carry (check_carry): 'levels' carries the messages between the bands of one scale, 'scales' also from the last stage
     of a scale into the first band of the next finer one; every view's `carried` says per pass whether it was.
+    unary (check_unary): 'blocks' takes pair_volumes once, at full size, and every level's volumes from level_volumes
+    (DESIGN.md 6.6); the images are reduced all the same, for the guided expansion.
     -> PyramidResult."""
     levels, maxiter, bands, mode = check_plan(levels, maxiter, bands, expand)
     carry = check_carry(carry)
+    unary = check_unary(unary)
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
     if len(images) != 2:
         raise StereoHipError("solve_pair_ncc_pyramid: images must be the two views of a pair, left first (got %d)" % len(images))
@@ -310,16 +413,24 @@ def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
     host, dev = reduce_images(images, levels)
     out.times["reduce"] = clock() - t0
     out.levels = [None] * (levels + 1)
+    out.unary = unary
     for l in range(levels + 1):
         tol_l, w_l = level_model(kernel, tol, l)
         out.disparities.append(level_disparities(disparities, l))
         out.tol.append(tol_l); out.smooth_weight.append(w_l)
+    block_volumes = None                      # per view the volumes of the levels 0 .. levels
+    if unary == "blocks":
+        t0 = clock()
+        block_volumes = [level_volumes(vol, shapes[0][:2], disparities, levels, layout=1)
+                         for vol in consistency.pair_volumes(host[0], disparities)]
+        out.times["volumes"] = clock() - t0
 
     t0 = clock()
     L = levels
     out.levels[L] = consistency.solve_pair_ncc(host[L], out.disparities[L], kernel, unary_weight, out.tol[L], maxiter[L],
                                                max_relgap, check_tol=check_tol / (1 << L), smooth_weight=out.smooth_weight[L],
-                                               carry=carry == "scales")
+                                               carry=carry == "scales",
+                                               volumes=None if block_volumes is None else [v[L] for v in block_volumes])
     out.times["level_%d" % L] = clock() - t0
     for l in range(levels - 1, -1, -1):
         t0 = clock()
@@ -330,7 +441,7 @@ def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
             view.dispmap = view.expanded
         res.times["expand"] = clock() - t0
         t1 = clock()
-        volumes = consistency.pair_volumes(host[l], out.disparities[l])
+        volumes = consistency.pair_volumes(host[l], out.disparities[l]) if block_volumes is None else [v[l] for v in block_volumes]
         res.times["volumes"] = clock() - t1
         conn = T.construct_neighborhood(H, W)
         alphas = np.ones(conn.shape[1]) * out.smooth_weight[l]
@@ -353,10 +464,12 @@ def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
 class ViewPyramidResult:
     """solve_view_ncc_pyramid's result: `dispmap` (level 0's last map) and per level l, index l: `maps` (the maps of the
     level's passes), `expanded` / `expand_source` (None at the coarsest level), `labels`, `energy`, `lower_bound`,
-    `iterations`, `paths`, `carried` (lists per pass), `disparities`, `tol`, `smooth_weight`."""
+    `iterations`, `paths`, `carried` (lists per pass), `disparities`, `tol`, `smooth_weight`; `unary`: where the levels'
+    volumes came from (check_unary), `times["volumes"]`: the seconds spent making them."""
 
     def __init__(self, n):
         self.dispmap = None
+        self.unary, self.times = "images", {}
         for name in ("maps", "labels", "energy", "lower_bound", "iterations", "paths", "carried"):
             setattr(self, name, [[] for _ in range(n)])
         self.expanded, self.expand_source = [None] * n, [None] * n
@@ -364,27 +477,52 @@ class ViewPyramidResult:
 
 
 def solve_view_ncc_pyramid(images, disparities, kernel, unary_weight, tol, levels, maxiter, max_relgap, bands=None,
-                           expand="guided", carry="none"):
+                           expand="guided", carry="none", unary="images", volume=None):
     """One view, coarse to fine: `images` = (the reference image, the other one), a pixel at column x with disparity d
     matching column x - d of the other.  The steps of solve_pair_ncc_pyramid for one view with solo plans: the volume
     of a level is terms.ncc_volume on the level's images, the coarsest level one TrwsPlan on the level's slices, every
     finer level band.refine_band around the expanded map.  No cross-check.  carry: as in solve_pair_ncc_pyramid.
-    -> ViewPyramidResult."""
+    unary (check_unary): with 'blocks' every level's volume comes from level_volumes on the full-size volume, which is
+    `volume` where given (H x W x D, or D x N: told apart by the number of dimensions) and terms.ncc_volume on the
+    images otherwise.  -> ViewPyramidResult."""
     levels, maxiter, bands, mode = check_plan(levels, maxiter, bands, expand)
     carry = check_carry(carry)
+    unary = check_unary(unary)
+    if volume is not None and unary != "blocks":
+        raise StereoHipError("pyramid: a volume is taken with unary='blocks' only ('images' makes every level's own)")
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
     level_model(kernel, tol, 0)
     _lib.require_device()
     host, dev = reduce_images(images[:2], levels)
     out = ViewPyramidResult(levels + 1)
+    out.unary = unary
     for l in range(levels + 1):
         tol_l, w_l = level_model(kernel, tol, l)
         out.disparities.append(level_disparities(disparities, l))
         out.tol.append(tol_l); out.smooth_weight.append(w_l)
+    out.times["volumes"] = 0.0
+    layout, volumes = 1, None
+
+    def level_volume(l):
+        """Level l's volume: a block volume, or ('images') made here from the level's images, one level at a time."""
+        t0 = time.perf_counter()
+        vol = volumes[l] if volumes is not None else T.ncc_volume(host[l][0], host[l][1], out.disparities[l], 2, layout=1)
+        out.times["volumes"] += time.perf_counter() - t0
+        return vol
+
+    if unary == "blocks":
+        t0 = time.perf_counter()
+        if volume is None:
+            volume = T.ncc_volume(host[0][0], host[0][1], disparities, 2, layout=1)
+        layout = 0 if np.ndim(volume) == 3 else 1
+        volumes = level_volumes(volume, host[0][0].shape[:2], disparities, levels, layout)
+        out.times["volumes"] = time.perf_counter() - t0
     L = levels
     H, W = host[L][0].shape[:2]
     conn = T.construct_neighborhood(H, W)
-    vol = T.ncc_volume(host[L][0], host[L][1], out.disparities[L], 2, layout=1)
+    vol = level_volume(L)
+    if layout == 0:
+        vol = vol.reshape((H * W, -1), order="F").T           # D x N for the upload
     plan = TrwsPlan(int(kernel), out.disparities[L].shape[0], H * W, conn)
     try:
         plan.upload(unary_weight * (1.0 - vol), np.ones(conn.shape[1]) * out.smooth_weight[L], out.tol[L],
@@ -403,9 +541,8 @@ def solve_view_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
         H, W = host[l][0].shape[:2]
         out.expanded[l], out.expand_source[l] = _expand_view(current, (H, W), mode, dev[l][0], dev[l + 1][0])
         conn = T.construct_neighborhood(H, W)
-        vol = T.ncc_volume(host[l][0], host[l][1], out.disparities[l], 2, layout=1)
-        r = band.refine_band(vol, out.disparities[l], unary_weight, out.expanded[l], kernel, out.tol[l], bands[l], maxiter[l],
-                             max_relgap, alphas=np.ones(conn.shape[1]) * out.smooth_weight[l], layout=1, conn=conn,
+        r = band.refine_band(level_volume(l), out.disparities[l], unary_weight, out.expanded[l], kernel, out.tol[l], bands[l], maxiter[l],
+                             max_relgap, alphas=np.ones(conn.shape[1]) * out.smooth_weight[l], layout=layout, conn=conn,
                              carry=carry != "none", carry_start=(stage, True) if carry == "scales" else None)
         stage = r.stage
         out.maps[l], out.labels[l], out.energy[l], out.carried[l] = r.maps, r.labels, r.energy, r.carried
