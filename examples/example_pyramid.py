@@ -5,6 +5,7 @@ iteration budget per solve (max_relgap 0: every solve runs `--maxiter` iteration
 
     python examples/example_pyramid.py [--levels 2] [--maxiter 30] [--expand guided] [--kernel 1] [--drop-slice]
                                        [--unary images|blocks|both] [--carry] [--record out.txt]
+                                       [--propagate] [--propagate-passes 1]
 
 Per pair and method it prints the wall time per stage, the kernel family of every solve (TrwsPlan.path(): 2 is the
 K <= 64 Pipe family), the energy of the final left map in the full-size model (one dispmap_ncc, set_disparity +
@@ -12,6 +13,10 @@ update_energy), the share of consistent pixels at check tolerances 0.5 and 1.0, 
 methods' left maps differ by more than 1.  --unary chooses where a level's volume comes from: the NCC
 of the reduced images, the block means of the full-size volume, or both side by side.  --drop-slice leaves out the coarsest level's last slice where that level has
 65 (one past the Pipe family), as a caller who wants the coarse solve in that family would.
+
+--propagate adds, next to every pyramid, the same pyramid with candidate passes before each level's bands:
+--propagate-passes passes per level, each with the offsets -1, 0, 1 and the current map and the level's winner-take-all
+map at the 12 taps 1, 2 and 4 pixels away along the rows and the columns (K = 27).
 
 --carry measures instead what carrying the messages from stage to stage buys.  On the left view with
 solo plans, per band of every level, around the map the cold chain produced: the cold band's energy and bound after
@@ -106,6 +111,13 @@ def measure_carry(name, images, disparities, args, say):
             % (name, mode, {l: [int(i) for i in out.levels[l].left.iterations] for l in range(L, -1, -1)}, dm.energy(), seconds))
 
 
+PROPAGATE_TAPS = [(dy * r, dx * r) for r in (1, 2, 4) for dy, dx in ((-1, 0), (1, 0), (0, -1), (0, 1))]
+
+
+def propagate_levels(levels, passes):
+    return [[dict(offsets=[-1.0, 0.0, 1.0], taps=PROPAGATE_TAPS, sources=["base", "wta"])] * passes for _ in range(levels)]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--levels", type=int, default=2)
@@ -117,6 +129,8 @@ def main():
     ap.add_argument("--record", help="append the printed lines to this file")
     ap.add_argument("--unary", default="images", choices=("images", "blocks", "both"),
                     help="where a level's volume comes from (DESIGN.md 6.6); both: the two choices side by side")
+    ap.add_argument("--propagate", action="store_true", help="also run every pyramid with candidate passes (DESIGN.md 6.7)")
+    ap.add_argument("--propagate-passes", type=int, default=1, help="candidate passes per level")
     args = ap.parse_args()
     import stereo_amd
     from stereo_amd import pyramid
@@ -154,11 +168,17 @@ def main():
             continue
         solve_args = (images, disparities, args.kernel, UNARY_WEIGHT, TOL)
         pyramids = []
+        variants = []
         for unary in unaries:
-            stereo_amd.solve_pair_ncc_pyramid(*solve_args, args.levels, 1, 0.0, expand=args.expand, unary=unary)   # warm-up: code objects
+            variants.append(("pyramid, unary %s" % unary, dict(unary=unary)))
+            if args.propagate:
+                variants.append(("pyramid, unary %s, propagate x %d" % (unary, args.propagate_passes),
+                                 dict(unary=unary, propagate=propagate_levels(args.levels, args.propagate_passes))))
+        for what, kw in variants:
+            stereo_amd.solve_pair_ncc_pyramid(*solve_args, args.levels, 1, 0.0, expand=args.expand, **kw)   # warm-up: code objects
             t0 = time.perf_counter()
-            pyr = stereo_amd.solve_pair_ncc_pyramid(*solve_args, args.levels, args.maxiter, 0.0, expand=args.expand, unary=unary)
-            pyramids.append(("pyramid, unary %s" % unary, pyr, time.perf_counter() - t0))
+            pyr = stereo_amd.solve_pair_ncc_pyramid(*solve_args, args.levels, args.maxiter, 0.0, expand=args.expand, **kw)
+            pyramids.append((what, pyr, time.perf_counter() - t0))
         t0 = time.perf_counter()
         full = stereo_amd.solve_pair_ncc(*solve_args, args.maxiter, 0.0)
         t_full = time.perf_counter() - t0
@@ -183,7 +203,7 @@ def main():
         for what, result in [(w, p) for w, p, _ in pyramids] + [("full size", full)]:
             dm.set_disparity(result.left.dispmap)
             dm.update_energy()
-            line = "  %-24s left map in the full-size model: energy %.3f" % (what, dm.energy())
+            line = "  %-40s left map in the full-size model: energy %.3f" % (what, dm.energy())
             for tol in (0.5, 1.0):
                 status, _ = stereo_amd.lr_check(result.left.dispmap, result.right.dispmap, 1, tol)
                 line += ";  consistent at %.1f: %.4f" % (tol, float((status == 0).mean()))

@@ -35,8 +35,9 @@ extern "C" {
  * 14: stereo_pyramid_reduce / stereo_pyramid_expand (image pyramid: box reduction, map expansion).
  * 15: stereo_band_carry / stereo_band_carry_device (messages carried from one band level or pyramid scale to the
  * next), stereo_trws_state_receivers_host.  16: stereo_pyramid_reduce_volume / _device (image pyramid: a coarser
- * level's NCC volume as the block mean of the finer one). */
-#define STEREO_HIP_ABI_VERSION 16
+ * level's NCC volume as the block mean of the finer one).  17: stereo_candidates_gather / _inputs / _apply (candidate
+ * bands: per-pixel label sets propagated from neighbours). */
+#define STEREO_HIP_ABI_VERSION 17
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -730,6 +731,73 @@ int stereo_band_inputs_device(const double *ncc, int H, int W, int D, int layout
 int stereo_band_apply_device(const double *base, int H, int W, const int32_t *labels, const double *offsets,
                              const double *d_offsets, int K, double *refined, int32_t *bad, void *stream,
                              char *err, size_t errcap);
+
+/* ---- candidate bands: per-pixel label sets propagated from neighbours ------------------ *
+ * No reference counterpart as a call; the problem is the reference's own energy restricted to K fronto-parallel
+ * labels per pixel, as the band's is, but label k at pixel i means an arbitrary per-pixel disparity cand[k, i], not
+ * base_i plus a shared offset.  A pixel whose base is wrong by more than a band's half-width has no band label that
+ * is right; if a neighbour at one of the taps, or another map such as the volume's winner-take-all map, is right
+ * there, the candidate set holds the right value.
+ *
+ * The candidate table `cand` is K x N doubles, label fastest (element (k, i) at k + K*i), pixels column major
+ * (pixel (y, x) is i = y + H*x, zero based), N = H*W.
+ *
+ * stereo_candidates_gather builds a table from
+ *      base         H x W doubles, column major
+ *      offsets      Ko >= 1 doubles under the band's rules: finite, strictly ascending, containing 0.0
+ *      sources      M >= 0 maps, H x W doubles each, one after the other (source m starts at sources + m*N)
+ *      taps         T >= 0 pairs of int32, (dy_t, dx_t) at taps[2t], taps[2t + 1], |dy|, |dx| < 2^15
+ * as
+ *      cand[k, i]                      = base_i + offsets_k                                        for k < Ko
+ *      cand[Ko + m*T + t, (y, x)]      = src_m[clamp(y + dy_t, 0, H - 1), clamp(x + dx_t, 0, W - 1)]
+ * (the value is copied, nothing is added), K = Ko + M*T, 1 <= K <= stereo_band_max_offsets().  Duplicates are allowed
+ * and are not removed -- the tap (0, 0), taps clamped at a border, neighbours with equal values: TRW-S's first-minimum
+ * rule decides among equal labels, and the applied value is the same either way.  With M*T == 0 sources and taps may
+ * be NULL and the table is the band's.
+ *
+ * stereo_candidates_inputs takes a table (this one or any other the caller brings), not the recipe.  Label k at
+ * pixel i is the plane [0, 0, 1, -cand[k, i]]; unary and positions are exactly what stereo_ncc_unary and
+ * stereo_trws_positions give for those K proposals, byte for byte:
+ *      unary        K x N, label fastest: unary(k, i) = unary_weight * (1 - sample(cand[k, i])) with every rule of the
+ *                   sampler as listed for stereo_band_inputs; a candidate outside the volume's range costs
+ *                   unary_weight * (1 + 1e6).  Nothing is clamped.
+ *      q, qprim     K x E, label fastest: q(k, e) = cand[k, i2], qprim(k, e) = cand[k, i1] for edge e = (i1, i2) =
+ *                   (conn[2e], conn[2e + 1]), through the plane -> disparity rule (dispmap_super.m:318-328), which
+ *                   gives the candidate itself with the plane's sign of zero (-0 for a candidate of 0).  E = 0: conn, q
+ *                   and qprim may be NULL.
+ * stereo_candidates_apply: out_i = cand[label_i - 1, i], labels int32 and one based; the value is copied.
+ *
+ * Everything is fp64 without FMA contraction and runs the code of stereo_ncc_unary (csrc/ncc_sample.h).
+ *
+ * Refused with a message, before the device is looked for: the band's refusals (offsets not finite, not strictly
+ * ascending or without 0.0; Ko < 1; layout other than 0 / 1; D, H or W below 1; H*W >= 2^31; NULL for a required
+ * array); K outside 1 .. stereo_band_max_offsets(); M < 0 or T < 0; M*T > 0 with NULL sources or taps; |dy| or
+ * |dx| >= 2^15.  The host entries also refuse a base, source or candidate value that is not finite (the message names
+ * the pixel, and for a candidate the label), a conn entry outside 0 .. N - 1 and, in apply, a label outside 1 .. K. */
+int stereo_candidates_gather(const double *base, int H, int W, const double *offsets, int Ko, const double *sources,
+                             int M, const int32_t *taps, int T, double *cand, char *err, size_t errcap);
+int stereo_candidates_inputs(const double *ncc, int H, int W, int D, int layout, const double *disparities,
+                             double unary_weight, const double *cand, int K, int64_t E, const uint32_t *conn,
+                             double *unary, double *q, double *qprim, char *err, size_t errcap);
+int stereo_candidates_apply(const double *cand, int H, int W, int K, const int32_t *labels, double *out, char *err,
+                            size_t errcap);
+/* The same on device arrays of the caller (base, sources, cand, ncc, conn, labels and every output), launched on
+ * `stream` (hipStream_t, NULL = default) without waiting for it, with the conventions of stereo_band_inputs_device:
+ * the short vectors are passed twice, on the host (`offsets`, `taps`, `disparities`: checked) and on the device
+ * (`d_offsets`, `d_taps`, `d_disparities`: read by the kernels), so the entries copy nothing.  `bad` (device int32,
+ * may be NULL) is set to zero on `stream` and then incremented once per offending pixel: in gather a pixel at which
+ * the base or one of the sources is not finite, in inputs a pixel with a candidate that is not finite, in apply a pixel
+ * whose label is outside 1 .. K (its value is NaN).  The outputs of an offending pixel are unspecified but written.
+ * An edge that names a pixel outside 0 .. N - 1 reads nothing of that pixel; its positions are NaN. */
+int stereo_candidates_gather_device(const double *base, int H, int W, const double *offsets, const double *d_offsets,
+                                    int Ko, const double *sources, int M, const int32_t *taps, const int32_t *d_taps,
+                                    int T, double *cand, int32_t *bad, void *stream, char *err, size_t errcap);
+int stereo_candidates_inputs_device(const double *ncc, int H, int W, int D, int layout, const double *disparities,
+                                    const double *d_disparities, double unary_weight, const double *cand, int K,
+                                    int64_t E, const uint32_t *conn, double *unary, double *q, double *qprim,
+                                    int32_t *bad, void *stream, char *err, size_t errcap);
+int stereo_candidates_apply_device(const double *cand, int H, int W, int K, const int32_t *labels, double *out,
+                                   int32_t *bad, void *stream, char *err, size_t errcap);
 
 /* ---- messages carried from one band level or pyramid scale to the next --------------- *
  * No reference counterpart.  A chain of band problems solves every level around the map the level before produced;

@@ -252,6 +252,11 @@ class BandProblem:
             self.h_receiver = carry_mod.receivers(self.N, self.conn, 1)
         return self.h_receiver
 
+    @staticmethod
+    def labels_of(level):
+        """K of the level `level` (here: a vector of offsets), before it is built."""
+        return level.shape[0]
+
     def build(self, offsets, plan, tol, zero_columns=None, carry=None):
         """The inputs of the level `offsets` around the current base, bound to `plan`.  zero_columns: a bool tensor (N,),
         pixels whose unary column is set to zero.  carry: a carry.Carry of the previous stage (whose messages were saved

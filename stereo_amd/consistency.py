@@ -212,12 +212,15 @@ def collect_views(out, plans, to_map, check_tol, stage):
 
 
 def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
-                    zero_occluded=False, carry=False, stages=None, scales=False):
+                    zero_occluded=False, carry=False, stages=None, scales=False, name="band"):
     """The band passes of a pair solve: for every vector of offsets both views (`problems`: one band.BandProblem each,
     standing around the view's current map) build their band problem on the device and run up to `maxiter` iterations
     as a two-member TrwsBatch; the labels are applied, the refined maps checked with `check_tol` and filled
     (collect_views).  band_plans: {K: [plan, plan]}, filled here, closed by the caller.  zero_occluded: the unary
     columns of the pixels the preceding check found occluded are zeroed.
+    The problems may as well be candidates.CandidateProblem: a level is then a candidate level, not a
+    vector of offsets (the problem's labels_of says how many labels it has), carry must be off, and `name`, the prefix of
+    the passes' entries in out.times, tells the two kinds apart.
     carry: every level after the first starts from the view's previous level's messages; the members
     take them as batch members take any state.  stages: per view the carry.Stage the FIRST level starts from (None:
     from zero) -- a solve on this grid, or with scales=True on the grid one box reduction coarser.  out.stages: per
@@ -227,7 +230,7 @@ def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, m
     previous = [prob.carry_from(st, scales) for prob, st in zip(problems, stages)] if stages is not None else [None, None]
     for level, offsets in enumerate(band_levels):
         t0 = time.perf_counter()
-        Kb = offsets.shape[0]
+        Kb = problems[0].labels_of(offsets)
         if Kb not in band_plans:
             band_plans[Kb] = [TrwsPlan(int(kernel), Kb, N, conn) for _ in range(2)]
         for prob, plan, view, prev in zip(problems, band_plans[Kb], out.views, previous):
@@ -238,9 +241,9 @@ def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, m
             batch.iterate(maxiter, max_relgap)
         if carry:
             out.stages = [prob.stage(plan) for prob, plan in zip(problems, band_plans[Kb])]
-        out.times["band_%d" % (level + 1)] = time.perf_counter() - t0
+        out.times["%s_%d" % (name, level + 1)] = time.perf_counter() - t0
         collect_views(out, band_plans[Kb], lambda i, labels: problems[i].apply(labels), check_tol,
-                      "band_%d_check_fill" % (level + 1))
+                      "%s_%d_check_fill" % (name, level + 1))
         previous = [prob.carry_from(st) for prob, st in zip(problems, out.stages)] if carry else [None, None]
 
 

@@ -358,7 +358,11 @@ class dispmap_super:
         raise StereoHipError("refine_band: %s does not take its unary from the NCC sampler; band refinement is defined "
                              "for dispmap_ncc" % type(self).__name__)
 
-    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none", unary="images"):
+    def refine_candidates(self, levels, maxiter=None):
+        raise StereoHipError("refine_candidates: %s does not take its unary from the NCC sampler; candidate bands are "
+                             "defined for dispmap_ncc" % type(self).__name__)
+
+    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none", unary="images", propagate=None):
         raise StereoHipError("solve_pyramid: %s reaches its second view through a projection, and its refinement is the "
                              "plane band; the image pyramid is defined for dispmap_ncc" % type(self).__name__)
 
@@ -476,7 +480,28 @@ class dispmap_ncc(dispmap_super):
         self.set_disparity(self._unflip(out.dispmap))
         return out
 
-    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none", unary="images"):
+    def refine_candidates(self, levels, maxiter=None):
+        """Propagation around the current map (no reference counterpart): for every candidate level in
+        `levels` -- dict(offsets=, taps=, sources=), a source being 'base' (the current map), 'wta' (this volume's
+        best_disp_from_ncc map) or an H x W map in the coordinates current_dispmap() speaks -- TRW-S chooses per pixel
+        among current disparity + offset and the sources' values at the taps, with this object's volume, unary weight,
+        kernel, tolerance, smoothness weights and max_relgap, up to `maxiter` (default self.maxiter) iterations per
+        level.  The result goes in through set_disparity; returns candidates.refine_candidates's BandResult (its maps
+        are in the object's internal columns: flipped for a mirrored object; the caller's maps and the taps' dx are
+        in the image's own columns and are flipped on the way in)."""
+        from . import candidates
+        levels = candidates.check_levels(levels)
+        if self._mirrored:        # maps of the caller are in un-flipped columns, the object works in flipped ones
+            levels = [dict(l, sources=[s if isinstance(s, str) else np.asarray(s)[:, ::-1] for s in l["sources"]],
+                           taps=l["taps"] * np.array([1, -1], np.int32)) for l in levels]
+        base = self.disparitymap_from_assignment(self.assignment).reshape(self.sz[1], self.sz[0]).T    # internal columns
+        out = candidates.refine_candidates(self.ncc, self.disparities, self._unary_weight, base, self._kernel, self._tol, levels,
+                                           self.maxiter if maxiter is None else maxiter, self._max_relgap,
+                                           alphas=self.smooth_weights, conn=self.neighborhood)
+        self.set_disparity(self._unflip(out.dispmap))
+        return out
+
+    def solve_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none", unary="images", propagate=None):
         """The map from the image pyramid (no reference counterpart): this view solved at the scale
         2^levels with the level model of this object's kernel, unary weight and tolerance, carried up one scale at a time
         (`expand`: 'guided' by the reference image, or 'nearest') and refined at every finer level l by the band levels
@@ -484,8 +509,9 @@ class dispmap_ncc(dispmap_super):
         0 first; max_relgap is the object's.  A level's edges all weigh s^(k - 1): an object with other smooth_weights
         is refused.  A mirrored object works in its own flipped columns.  carry: 'none', 'levels' or 'scales'
         (pyramid.check_carry).  unary: 'images' (a level's volume is the NCC of the reduced images) or
-        'blocks' (the block means of this object's own volume; nothing is recomputed).  The result goes
-        in through set_disparity;
+        'blocks' (the block means of this object's own volume; nothing is recomputed).  propagate: per
+        level 0 .. levels - 1 a list of candidate levels that run before the level's bands.  The result
+        goes in through set_disparity;
         returns pyramid.solve_view_ncc_pyramid's ViewPyramidResult (maps in the object's internal columns)."""
         from . import pyramid
         unary = pyramid.check_unary(unary)
@@ -495,7 +521,7 @@ class dispmap_ncc(dispmap_super):
         out = pyramid.solve_view_ncc_pyramid(self.images, self.disparities, self._kernel, self._unary_weight, self._tol,
                                              levels, self.maxiter if maxiter is None else maxiter, self._max_relgap,
                                              bands=bands, expand=expand, carry=carry, unary=unary,
-                                             volume=self.ncc if unary == "blocks" else None)
+                                             volume=self.ncc if unary == "blocks" else None, propagate=propagate)
         self.set_disparity(self._unflip(out.dispmap))
         return out
 

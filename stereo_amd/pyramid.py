@@ -3,7 +3,7 @@ reduction of an image, the expansion of a coarse disparity map to the next finer
 and ``solve_pair_ncc_pyramid``: the pair solved at the coarsest scale, the maps carried up one scale at a time, band
 levels at every finer scale.  ``reduce_volume`` / ``level_volumes`` make a coarser
 level's NCC volume as the 2 x 2 block mean of the finer one (``unary="blocks"``) where the default takes the NCC of the
-reduced images.
+reduced images.  ``propagate=`` runs candidate levels (candidates.py) before a level's bands.
 
 Host forms take NumPy arrays: an image H x W x C (or H x W), a map H x W, any memory order.  Device forms take torch
 tensors of the current device in column-major storage: a map is a contiguous (W, H) tensor as lr_check_device takes
@@ -321,6 +321,32 @@ def check_plan(levels, maxiter, bands, expand):
     return levels, maxiter, checked, MODES[expand]
 
 
+def check_propagate(propagate, levels):
+    """`propagate` of a pyramid solve -> per level 0 .. levels - 1 a list of checked candidate levels
+    (candidates.check_level), empty where a level has none; None stays None."""
+    if propagate is None:
+        return None
+    from . import candidates
+    try:
+        n = len(propagate)
+    except TypeError:
+        n = -1
+    if n != levels or isinstance(propagate, (dict, str)):
+        raise StereoHipError("pyramid: propagate must hold one sequence of candidate levels per level 0 .. levels - 1 "
+                             "(%d, got %d)" % (levels, n))
+    checked = []
+    for l, passes in enumerate(propagate):
+        if passes is None:
+            passes = []
+        if isinstance(passes, dict):
+            passes = [passes]
+        try:
+            checked.append([candidates.check_level(c) for c in passes])
+        except TypeError:
+            raise StereoHipError("pyramid: propagate[%d] must be a sequence of candidate levels" % l)
+    return checked
+
+
 CARRY = ("none", "levels", "scales")
 
 
@@ -380,7 +406,7 @@ class PyramidResult:
 
 
 def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, levels, maxiter, max_relgap, bands=None,
-                           expand="guided", check_tol=1.0, carry="none", unary="images"):
+                           expand="guided", check_tol=1.0, carry="none", unary="images", propagate=None):
     """Both views of a rectified pair, coarse to fine.  Both images are reduced `levels` times (1 .. 5)
     on the device; solve_pair_ncc runs at the coarsest scale with that level's model (level_model, level_disparities);
     then for each finer level l each view's map is expanded with the view's own images of the two scales (`expand`:
@@ -393,8 +419,12 @@ def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
     of a scale into the first band of the next finer one; every view's `carried` says per pass whether it was.
     unary (check_unary): 'blocks' takes pair_volumes once, at full size, and every level's volumes from level_volumes
     (DESIGN.md 6.6); the images are reduced all the same, for the guided expansion.
+    propagate (check_propagate): per level 0 .. levels - 1 a list of candidate levels that run after the
+    expansion and before that level's bands, both views as a two-member TrwsBatch, each pass ending in the same check
+    and fill; a candidate pass neither takes nor leaves carried messages, so the band after one starts from zero.
     -> PyramidResult."""
     levels, maxiter, bands, mode = check_plan(levels, maxiter, bands, expand)
+    propagate = check_propagate(propagate, levels)
     carry = check_carry(carry)
     unary = check_unary(unary)
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
@@ -447,11 +477,18 @@ def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
         alphas = np.ones(conn.shape[1]) * out.smooth_weight[l]
         band_plans = {}
         try:
+            stages = out.levels[l + 1].stages if carry == "scales" else None
+            if propagate is not None and propagate[l]:
+                from . import candidates
+                problems = [candidates.CandidateProblem(vol, out.disparities[l], unary_weight, view.dispmap, conn, alphas, layout=1)
+                            for vol, view in zip(volumes, res.views)]
+                consistency.run_band_levels(res, problems, propagate[l], band_plans, kernel, conn, out.tol[l], maxiter[l],
+                                            max_relgap, check_tol / (1 << l), name="propagate")
+                stages = None                 # (a candidate pass hands on no messages)
             problems = [band.BandProblem(vol, out.disparities[l], unary_weight, view.dispmap, conn, alphas, layout=1)
                         for vol, view in zip(volumes, res.views)]
             consistency.run_band_levels(res, problems, bands[l], band_plans, kernel, conn, out.tol[l], maxiter[l], max_relgap,
-                                        check_tol / (1 << l), carry=carry != "none",
-                                        stages=out.levels[l + 1].stages if carry == "scales" else None, scales=True)
+                                        check_tol / (1 << l), carry=carry != "none", stages=stages, scales=True)
         finally:
             for plan in (p for pair in band_plans.values() for p in pair):
                 plan.close()
@@ -477,15 +514,17 @@ class ViewPyramidResult:
 
 
 def solve_view_ncc_pyramid(images, disparities, kernel, unary_weight, tol, levels, maxiter, max_relgap, bands=None,
-                           expand="guided", carry="none", unary="images", volume=None):
+                           expand="guided", carry="none", unary="images", volume=None, propagate=None):
     """One view, coarse to fine: `images` = (the reference image, the other one), a pixel at column x with disparity d
     matching column x - d of the other.  The steps of solve_pair_ncc_pyramid for one view with solo plans: the volume
     of a level is terms.ncc_volume on the level's images, the coarsest level one TrwsPlan on the level's slices, every
     finer level band.refine_band around the expanded map.  No cross-check.  carry: as in solve_pair_ncc_pyramid.
     unary (check_unary): with 'blocks' every level's volume comes from level_volumes on the full-size volume, which is
     `volume` where given (H x W x D, or D x N: told apart by the number of dimensions) and terms.ncc_volume on the
-    images otherwise.  -> ViewPyramidResult."""
+    images otherwise.  propagate: as in solve_pair_ncc_pyramid (candidates.refine_candidates before a level's bands).
+    -> ViewPyramidResult."""
     levels, maxiter, bands, mode = check_plan(levels, maxiter, bands, expand)
+    propagate = check_propagate(propagate, levels)
     carry = check_carry(carry)
     unary = check_unary(unary)
     if volume is not None and unary != "blocks":
@@ -541,12 +580,20 @@ def solve_view_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
         H, W = host[l][0].shape[:2]
         out.expanded[l], out.expand_source[l] = _expand_view(current, (H, W), mode, dev[l][0], dev[l + 1][0])
         conn = T.construct_neighborhood(H, W)
-        r = band.refine_band(level_volume(l), out.disparities[l], unary_weight, out.expanded[l], kernel, out.tol[l], bands[l], maxiter[l],
-                             max_relgap, alphas=np.ones(conn.shape[1]) * out.smooth_weight[l], layout=layout, conn=conn,
+        vol, alphas = level_volume(l), np.ones(conn.shape[1]) * out.smooth_weight[l]
+        start, results = out.expanded[l], []
+        if propagate is not None and propagate[l]:
+            from . import candidates
+            results.append(candidates.refine_candidates(vol, out.disparities[l], unary_weight, start, kernel, out.tol[l], propagate[l],
+                                                        maxiter[l], max_relgap, alphas=alphas, layout=layout, conn=conn))
+            start, stage = results[0].dispmap, None          # (a candidate pass hands on no messages)
+        r = band.refine_band(vol, out.disparities[l], unary_weight, start, kernel, out.tol[l], bands[l], maxiter[l],
+                             max_relgap, alphas=alphas, layout=layout, conn=conn,
                              carry=carry != "none", carry_start=(stage, True) if carry == "scales" else None)
         stage = r.stage
-        out.maps[l], out.labels[l], out.energy[l], out.carried[l] = r.maps, r.labels, r.energy, r.carried
-        out.lower_bound[l], out.iterations[l], out.paths[l] = r.lower_bound, r.iterations, r.paths
+        results.append(r)
+        for name in ("maps", "labels", "energy", "carried", "lower_bound", "iterations", "paths"):
+            getattr(out, name)[l] = [v for x in results for v in getattr(x, name)]
         current = r.dispmap
     out.dispmap = current
     return out
