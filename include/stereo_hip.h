@@ -36,8 +36,9 @@ extern "C" {
  * 15: stereo_band_carry / stereo_band_carry_device (messages carried from one band level or pyramid scale to the
  * next), stereo_trws_state_receivers_host.  16: stereo_pyramid_reduce_volume / _device (image pyramid: a coarser
  * level's NCC volume as the block mean of the finer one).  17: stereo_candidates_gather / _inputs / _apply (candidate
- * bands: per-pixel label sets propagated from neighbours). */
-#define STEREO_HIP_ABI_VERSION 17
+ * bands: per-pixel label sets propagated from neighbours).  18: stereo_plane_candidates_gather / _inputs_ncc /
+ * _inputs_globalstereo / _apply (plane candidates: per-pixel plane sets propagated from neighbours). */
+#define STEREO_HIP_ABI_VERSION 18
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -798,6 +799,93 @@ int stereo_candidates_inputs_device(const double *ncc, int H, int W, int D, int 
                                     int32_t *bad, void *stream, char *err, size_t errcap);
 int stereo_candidates_apply_device(const double *cand, int H, int W, int K, const int32_t *labels, double *out,
                                    int32_t *bad, void *stream, char *err, size_t errcap);
+
+/* ---- plane candidates: per-pixel plane sets propagated from neighbours ----------------- *
+ * No reference counterpart as a call; the problem is the reference's own energy restricted to K planes per pixel.
+ * Label k at pixel i means an arbitrary per-pixel PLANE pcand[:, k, i], not the fronto-parallel plane
+ * [0, 0, 1, -cand[k, i]] of the candidate bands above and not only pixel i's own plane moved along the disparity
+ * axis as in the plane band below.  A plane is a function on the whole image, so a plane copied from a neighbour is
+ * that neighbour's surface extended to this pixel: on a slanted surface the copy is right where a copied disparity
+ * is wrong by slope times tap distance.
+ *
+ * The plane candidate table `pcand` is 4 x K x N doubles: component j of label k at pixel i at j + 4*(k + K*i),
+ * pixels column major (pixel (y, x) is i = y + H*x, zero based), N = H*W, 1 <= K <= stereo_band_max_offsets().
+ *
+ * stereo_plane_candidates_gather builds a table from
+ *      planes       4 x N doubles, column major: the current assignment [a b c d] per pixel
+ *      offsets      Ko >= 1 doubles under the band's rules: finite, strictly ascending, containing 0.0
+ *      sources      M >= 0 plane maps, 4 x N doubles each, one after the other (source m starts at sources + 4*m*N)
+ *      taps         T >= 0 pairs of int32, (dy_t, dx_t) at taps[2t], taps[2t + 1], |dy|, |dx| < 2^15
+ * as
+ *      pcand[:, k, i]                  = [a_i, b_i, c_i, d_i - c_i * offsets_k]                     for k < Ko
+ *      pcand[:, Ko + m*T + t, (y, x)]  = src_m[:, clamp(y + dy_t, 0, H - 1) + H * clamp(x + dx_t, 0, W - 1)]
+ * The first is the plane band's label (one fp64 multiplication, one fp64 subtraction, no contraction); in the second
+ * the four doubles are copied and nothing is re-anchored.  K = Ko + M*T.  Duplicates are allowed and are not removed,
+ * as for stereo_candidates_gather.  With M*T == 0 sources and taps may be NULL and the table is the plane band's.
+ *
+ * stereo_plane_candidates_inputs_ncc / _globalstereo take a table (this one or any other the caller brings), not the
+ * recipe, and give exactly what the library's existing entries give for the K proposals P_k = pcand[:, k, :], byte
+ * for byte:
+ *      unary        K x N, label fastest: unary(k, i) is what stereo_ncc_unary (_ncc) or stereo_globalstereo_unary
+ *                   (_globalstereo) gives for proposal k at pixel i, whose point is [i / H + 1, i % H + 1], formed in
+ *                   the kernel (csrc/ncc_sample.h, csrc/gs_sample.h: one copy of each sampler).
+ *      q, qprim     K x E, label fastest: for e = (i1, i2) = (conn[2e], conn[2e + 1]), q(k, e) = plane pcand[:, k, i2]
+ *                   at the point of i2 and qprim(k, e) = plane pcand[:, k, i1] at the point of i2, through the
+ *                   plane -> disparity rule (dispmap_super.m:318-328), with d_min = d_step = 0 for _ncc and the
+ *                   (v - d_min) / d_step rescaling for _globalstereo: what stereo_trws_positions writes.  E = 0: conn,
+ *                   q and qprim may be NULL.
+ * stereo_plane_candidates_apply: out[:, i] = pcand[:, label_i - 1, i], 4 x N, labels int32 and one based; the values
+ * are copied.
+ *
+ * Everything is fp64 without FMA contraction.
+ *
+ * Refused with a message, before the device is looked for: the band's refusals (offsets not finite, not strictly
+ * ascending or without 0.0; Ko < 1; layout other than 0 / 1; D, H, W or C below 1; H*W >= 2^31; NULL for a required
+ * array; d_step == 0 for _globalstereo); K outside 1 .. stereo_band_max_offsets(); M < 0 or T < 0; M*T > 0 with NULL
+ * sources or taps; |dy| or |dx| >= 2^15; E < 0.  The host entries also refuse a plane -- of `planes`, of a source or
+ * of the table -- with a component that is not finite or with c == 0 ("Infinite disparity", dispmap_super.m:323-325);
+ * the message names the pixel and, for a table entry, the label.  They refuse a conn entry outside 0 .. N - 1 and,
+ * in apply, a label outside 1 .. K. */
+int stereo_plane_candidates_gather(const double *planes, int H, int W, const double *offsets, int Ko,
+                                   const double *sources, int M, const int32_t *taps, int T, double *pcand, char *err,
+                                   size_t errcap);
+int stereo_plane_candidates_inputs_ncc(const double *ncc, int H, int W, int D, int layout, const double *disparities,
+                                       double unary_weight, const double *pcand, int K, int64_t E,
+                                       const uint32_t *conn, double *unary, double *q, double *qprim, char *err,
+                                       size_t errcap);
+int stereo_plane_candidates_inputs_globalstereo(const double *im0, const double *im1, int H, int W, int C,
+                                                const double *P2, double d_min, double d_step, double col_thresh,
+                                                const double *pcand, int K, int64_t E, const uint32_t *conn,
+                                                double *unary, double *q, double *qprim, char *err, size_t errcap);
+int stereo_plane_candidates_apply(const double *pcand, int H, int W, int K, const int32_t *labels, double *out,
+                                  char *err, size_t errcap);
+/* The same on device arrays of the caller (planes, sources, pcand, ncc / im0 / im1, conn, labels and every output),
+ * launched on `stream` (hipStream_t, NULL = default) without waiting for it, with the conventions of
+ * stereo_candidates_*_device and stereo_plane_band_*_device: the short vectors are passed twice, on the host
+ * (`offsets`, `taps`, `disparities`: checked) and on the device (`d_offsets`, `d_taps`, `d_disparities`: read by the
+ * kernels), so the entries copy nothing; P2 is 12 host doubles and travels as a kernel argument.  A plane moves as two
+ * 16-byte accesses: planes, sources, pcand and out must be 16-byte aligned (refused otherwise).  `bad` (device
+ * int32, may be NULL) is set to zero on `stream` and then incremented once per offending pixel: in gather a pixel at
+ * which the own plane or a source's plane AT THAT PIXEL has a component that is not finite or c == 0, in inputs a pixel
+ * with such a candidate, in apply a pixel whose label is outside 1 .. K (its four outputs are NaN).  The outputs of
+ * an offending pixel are unspecified but written.  An edge that names a pixel outside 0 .. N - 1 reads nothing of
+ * that pixel; its positions are NaN. */
+int stereo_plane_candidates_gather_device(const double *planes, int H, int W, const double *offsets,
+                                          const double *d_offsets, int Ko, const double *sources, int M,
+                                          const int32_t *taps, const int32_t *d_taps, int T, double *pcand,
+                                          int32_t *bad, void *stream, char *err, size_t errcap);
+int stereo_plane_candidates_inputs_ncc_device(const double *ncc, int H, int W, int D, int layout,
+                                              const double *disparities, const double *d_disparities,
+                                              double unary_weight, const double *pcand, int K, int64_t E,
+                                              const uint32_t *conn, double *unary, double *q, double *qprim,
+                                              int32_t *bad, void *stream, char *err, size_t errcap);
+int stereo_plane_candidates_inputs_globalstereo_device(const double *im0, const double *im1, int H, int W, int C,
+                                                       const double *P2, double d_min, double d_step,
+                                                       double col_thresh, const double *pcand, int K, int64_t E,
+                                                       const uint32_t *conn, double *unary, double *q, double *qprim,
+                                                       int32_t *bad, void *stream, char *err, size_t errcap);
+int stereo_plane_candidates_apply_device(const double *pcand, int H, int W, int K, const int32_t *labels, double *out,
+                                         int32_t *bad, void *stream, char *err, size_t errcap);
 
 /* ---- messages carried from one band level or pyramid scale to the next --------------- *
  * No reference counterpart.  A chain of band problems solves every level around the map the level before produced;

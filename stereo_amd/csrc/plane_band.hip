@@ -16,14 +16,13 @@
 
 #include "band_common.h"
 #include "common.h"
-#include "gs_sample.h"
-#include "ncc_sample.h"
 #include "stereo_hip.h"
+#include "unary_source.h"
 
 namespace {
 
 using stereo::fail;
-using namespace stereo::band;   // kTB, band_index, check_offsets, check_sizes, guarded, grid_for
+using namespace stereo::band;   // kTB, band_index, check_offsets, check_sizes, guarded, grid_for, NccSource, GsSource
 
 // The plane of label k at a pixel: one fp64 multiplication and one fp64 subtraction (no contraction: the file is
 // compiled with -ffp-contract=off).
@@ -33,37 +32,7 @@ __device__ __forceinline__ bool plane_ok(double a, double b, double c, double d)
   return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d) && c != 0.0;
 }
 
-// The two unary sources.  begin(): what the block prepares once (the NCC source copies the D slice positions into
-// LDS, for the reason band.hip gives); at(): the unary of pixel px, whose point is (x, y), for a plane whose
-// disparity there is `disp`.
-constexpr int kMaxStagedSlices = 4096;   // 32 KiB of LDS; beyond it the kernel reads the slices where they are
-template <bool kStageSlices>
-struct NccSource {
-  const double *ncc;
-  int D, layout;
-  const double *dv;
-  double dmin, dmax, unary_weight;
-  int ascending;
-  __device__ __forceinline__ const double *begin(double *lds) const {
-    if (!kStageSlices) return dv;
-    for (int i = threadIdx.x; i < D; i += kTB) lds[i] = dv[i];
-    __syncthreads();
-    return lds;
-  }
-  __device__ __forceinline__ double at(const double *slices, int H, int64_t Npx, int64_t px, double x, double y, double disp) const {
-    return stereo::ncc_unary_at(ncc, Npx, D, layout, px, slices, dmin, dmax, unary_weight, disp, ascending);
-  }
-};
-struct GsSource {
-  const double *im0, *im1;
-  int W, C;
-  double P2[12];   // by value: read at constant indices, it stays in scalar registers
-  double d_min, d_step, col_thresh;
-  __device__ __forceinline__ const double *begin(double *) const { return nullptr; }
-  __device__ __forceinline__ double at(const double *, int H, int64_t, int64_t px, double x, double y, double disp) const {
-    return stereo::gs_unary_at(im0, im1, H, W, C, P2, d_min, d_step, col_thresh, px, x, y, disp);
-  }
-};
+// The two unary sources, NccSource<kStageSlices> and GsSource: unary_source.h (shared with plane_candidates.hip).
 
 template <class Source>
 __global__ __launch_bounds__(kTB) void plane_band_unary_kernel(Source src, int H, int64_t Npx, const double *__restrict__ planes,

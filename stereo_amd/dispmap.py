@@ -392,6 +392,34 @@ class dispmap_super:
         self.assignment = out.planes
         return out
 
+    def _plane_candidate_level(self, level):
+        """The hook of refine_plane_candidates: a level as the caller wrote it -> the level in the object's internal
+        columns, with the source forms of the class resolved to 4 x N planes."""
+        return level
+
+    def refine_plane_candidates(self, levels, maxiter=None):
+        """Plane propagation around the current assignment (no reference counterpart): for every
+        plane-candidate level in `levels` -- dict(offsets=, taps=, sources=), a source being 'base' (the current planes)
+        or 4 x N planes -- TRW-S chooses per pixel among the pixel's own plane moved by an offset along the disparity
+        axis and the sources' planes at the taps, copied unchanged (a neighbour's surface extended to this pixel), with
+        this object's unary, kernel, tolerance, smoothness weights, rescaling and max_relgap, up to `maxiter` (default
+        self.maxiter) iterations per level.  The offsets are in the units of refine_plane_band's levels.  4 x N sources
+        are in the object's internal columns, as `assignment` is.  The result goes in through the assignment setter;
+        returns plane_candidates.refine_plane_candidates's PlaneBandResult (planes in the object's internal columns)."""
+        from . import plane_candidates
+        if isinstance(levels, dict):
+            levels = [levels]
+        levels = plane_candidates.check_levels([self._plane_candidate_level(l) for l in levels])
+        source, unit = self._plane_band_source()
+        if unit is not None:
+            levels = [dict(l, offsets=l["offsets"] * unit) for l in levels]
+        out = plane_candidates.refine_plane_candidates(source, self.assignment, self._kernel, self.tol, levels,
+                                                       self.maxiter if maxiter is None else maxiter, self._max_relgap,
+                                                       alphas=self.smooth_weights, conn=self.neighborhood, d_min=self.d_min,
+                                                       d_step=self.d_step)
+        self.assignment = out.planes
+        return out
+
 
 class dispmap_ncc(dispmap_super):
     """dispmap_ncc.m"""
@@ -528,6 +556,31 @@ class dispmap_ncc(dispmap_super):
     def _plane_band_source(self):
         from . import plane_band
         return plane_band.NccSource(self.ncc, self.disparities, self._unary_weight), None
+
+    def _plane_candidate_level(self, level):
+        """dispmap_ncc takes two more source forms: 'wta' -- the fronto-parallel planes of this volume's best_disp_from_ncc
+        map; where that map is not finite the pixel's own plane stands in -- and an H x W map in the coordinates
+        current_dispmap() speaks, taken as fronto-parallel planes.  A mirrored object flips such a map and the taps' dx on
+        the way in; 4 x N sources are in the object's internal (flipped) columns, as `assignment` is, and pass unchanged."""
+        from . import plane_candidates
+        from .candidates import _taps
+        if not isinstance(level, dict) or "sources" not in level:
+            return level
+        sources = level["sources"]
+        if isinstance(sources, (str, np.ndarray, plane_candidates.OrOwn)):
+            sources = [sources]
+        N = self.sz[0] * self.sz[1]
+        out = []
+        for s in sources:
+            if isinstance(s, str) and s == "wta":
+                s = plane_candidates.OrOwn(plane_candidates.fronto(self._best_disp()))      # internal columns
+            elif not isinstance(s, (str, plane_candidates.OrOwn)) and np.shape(s) == tuple(self.sz) and np.shape(s) != (4, N):
+                s = plane_candidates.fronto(self._unflip(np.asarray(s, np.float64)))
+            out.append(s)
+        level = dict(level, sources=out)
+        if self._mirrored and "taps" in level:
+            level["taps"] = _taps(level["taps"]) * np.array([1, -1], np.int32)
+        return level
 
     # ---- proposals (dispmap_ncc.m:48-92).  Host side: a few dozen points and 3 x 3 SVDs per
     # proposal; MATLAB's svd is outside the reference tree, so this mirrors the arithmetic with

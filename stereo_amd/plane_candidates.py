@@ -1,0 +1,399 @@
+"""Plane candidates: per-pixel plane sets propagated from neighbours (the definition:
+include/stereo_hip.h).
+
+A plane candidate table ``pcand`` (4 x K x N: component, label, pixel; pixels column major) says what label k means at
+pixel i: a plane ``[a b c d]`` of its own.  ``gather`` builds one from the planes of an assignment (4 x N), the band's
+``offsets`` (strictly ascending, containing 0.0), M source plane maps (4 x N each) and T taps ``(dy, dx)``: the pixel's
+own plane moved by ``offsets_k`` along the disparity axis, then for every source and tap the source's plane at the
+clamped neighbour, copied unchanged -- a plane is a function on the whole image, so the copy is the neighbour's surface
+extended to this pixel.  ``plane_candidates_inputs`` makes the TRW-S problem of any table -- ``unary`` (K x N) from a
+unary source of plane_band.py (``NccSource`` or ``GlobalstereoSource``), ``q`` / ``qprim`` (K x E) as
+stereo_trws_positions gives them for the K proposals ``pcand[:, k, :]`` -- and ``plane_candidates_apply`` reads the planes
+a labelling selects.  ``refine_plane_candidates`` builds these on the device, solves them level by level and applies the
+labels.
+
+Host forms take NumPy arrays in MATLAB shapes (planes 4 x N, a table 4 x K x N, conn 2 x E zero based).  Device forms
+take torch tensors of the current device, as in plane_band.py: ``planes`` and ``out`` are contiguous float64 tensors of
+4 N elements (shape (N, 4)), M sources one contiguous (M, N, 4) tensor, a table a flat float64 tensor of 4 K N elements.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from . import band
+from . import plane_band
+from . import terms as T
+from ._lib import StereoHipError
+from .band import _conn, _flat, _vec, to_device_vector
+from .candidates import _taps, taps_to_device
+from .consistency import _map, _p, _stream
+from .plane_band import PlaneBandProblem, PlaneBandResult, _planes, _rescale, _source
+from .trws import TrwsPlan
+
+
+class OrOwn:
+    """A source (4 x N planes) whose planes that are not finite stand for 'the pixel's own plane': they are replaced by
+    the current assignment's when a level is built (dispmap_ncc's 'wta' source, whose map has holes where the volume
+    has NaN slices)."""
+
+    def __init__(self, planes):
+        self.planes = np.asfortranarray(np.asarray(planes, dtype=np.float64))
+        if self.planes.ndim != 2 or self.planes.shape[0] != 4:
+            raise StereoHipError("plane candidates: a source must be 4 x N planes")
+
+
+def fronto(m):
+    """An H x W map -> the 4 x N fronto-parallel planes [0, 0, 1, -v], pixels column major."""
+    m = _map(m, "a map")
+    out = np.zeros((4, m.size), order="F")
+    out[2] = 1.0
+    out[3] = -m.reshape(-1, order="F")
+    return out
+
+
+def _shape(shape):
+    H, W = (int(v) for v in shape)
+    return H, W
+
+
+def _table(pcand, N):
+    pcand = np.asarray(pcand, dtype=np.float64)
+    if pcand.ndim != 3 or pcand.shape[0] != 4 or pcand.shape[2] != N:
+        raise StereoHipError("pcand must be 4 x K x (H*W)")
+    return np.asfortranarray(pcand)
+
+
+def _host_sources(sources, N):
+    """M x (4 N) float64, C order: source m in the storage order of 4 x N column major."""
+    out = np.zeros((len(sources), 4 * N))
+    for m, s in enumerate(sources):
+        s = np.asarray(s, dtype=np.float64)
+        if s.ndim != 2 or s.shape != (4, N):
+            raise StereoHipError("a source must be 4 x N planes of the image's size")
+        out[m] = s.reshape(-1, order="F")
+    return out
+
+
+def gather(planes, offsets, shape, sources=(), taps=()):
+    """stereo_plane_candidates_gather for an image of `shape` = (H, W): `planes` 4 x N, `sources` a list of 4 x N plane
+    maps -> pcand, 4 x K x N (Fortran order), K = len(offsets) + len(sources) * len(taps)."""
+    H, W = _shape(shape)
+    N = H * W
+    planes = _planes(planes, N)
+    offsets, taps = _vec(offsets, "offsets"), _taps(taps)
+    src = _host_sources(list(sources), N)
+    Ko, M, Tn = offsets.shape[0], src.shape[0], taps.shape[0]
+    K = Ko + M * Tn
+    pcand = np.zeros((4, max(K, 1), max(N, 1)), order="F")
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_plane_candidates_gather(_p(planes), C.c_int(H), C.c_int(W), _p(offsets), C.c_int(Ko),
+                                                   _p(src) if M * Tn else None, C.c_int(M),
+                                                   _p(taps, C.c_int32) if M * Tn else None, C.c_int(Tn), _p(pcand), err,
+                                                   C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return pcand
+
+
+def _check_source_shape(source, H, W, what):
+    if (source.H, source.W) != (H, W):
+        raise StereoHipError("%s: the unary source is %d x %d, the table's image %d x %d" % (what, source.H, source.W, H, W))
+
+
+def plane_candidates_inputs(source, pcand, shape, conn, d_min=0.0, d_step=0.0):
+    """stereo_plane_candidates_inputs_ncc / _globalstereo for the table `pcand` (4 x K x N) of an image of `shape` =
+    (H, W); `source` a plane_band.NccSource or GlobalstereoSource -> (unary K x N, q K x E, qprim K x E), Fortran order."""
+    source = _source(source)
+    d_min, d_step = _rescale(source, d_min, d_step)
+    H, W = _shape(shape)
+    _check_source_shape(source, H, W, "plane_candidates_inputs")
+    N = H * W
+    pcand, conn = _table(pcand, N), _conn(conn)
+    K, E = pcand.shape[1], conn.shape[1]
+    unary = np.zeros((K, N), order="F")
+    q, qprim = np.zeros((K, E), order="F"), np.zeros((K, E), order="F")
+    err = _lib.errbuf()
+    tail = (_p(pcand), C.c_int(K), C.c_int64(E), _p(conn, C.c_uint32), _p(unary), _p(q), _p(qprim), err, C.c_size_t(len(err)))
+    if source.kind == "ncc":
+        rc = _lib.lib().stereo_plane_candidates_inputs_ncc(_p(source.vol), C.c_int(H), C.c_int(W), C.c_int(source.D),
+                                                           C.c_int(source.layout), _p(source.disparities),
+                                                           C.c_double(source.unary_weight), *tail)
+    else:
+        rc = _lib.lib().stereo_plane_candidates_inputs_globalstereo(_p(source.im0), _p(source.im1), C.c_int(H), C.c_int(W),
+                                                                    C.c_int(source.C), _p(source.P2), C.c_double(d_min),
+                                                                    C.c_double(d_step), C.c_double(source.col_thresh), *tail)
+    _lib.check(rc, err)
+    return unary, q, qprim
+
+
+def plane_candidates_apply(pcand, labels, shape):
+    """stereo_plane_candidates_apply -> 4 x N: pcand[:, labels - 1, pixel].  `labels`: N values, one based, as
+    plan.result() returns them."""
+    H, W = _shape(shape)
+    N = H * W
+    pcand = _table(pcand, N)
+    lab = plane_band._labels(labels, N)
+    out = np.zeros((4, N), order="F")
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_plane_candidates_apply(_p(pcand), C.c_int(H), C.c_int(W), C.c_int(pcand.shape[1]),
+                                                  _p(lab, C.c_int32), _p(out), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return out
+
+
+# ---------------------------------------------------------------- device forms
+
+def _vp(t):
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def _device_table(pcand, N):
+    import torch
+    pcand = _flat(pcand, "pcand", torch.float64)
+    if N < 1 or pcand.numel() == 0 or pcand.numel() % (4 * N):
+        raise StereoHipError("pcand must hold 4 * K * H * W elements")
+    return pcand, pcand.numel() // (4 * N)
+
+
+def gather_device(planes, offsets, shape, sources=None, taps=(), pcand=None, bad=None, stream=None, d_offsets=None,
+                  d_taps=None, check=True):
+    """stereo_plane_candidates_gather_device: `planes` a float64 tensor of 4 N elements, `sources` None or a contiguous
+    (M, N, 4) tensor, `offsets` and `taps` host arrays (`d_offsets` / `d_taps`: their device copies, made here when not
+    given).  check=True reads the count of pixels at which the own plane or a source's plane is not finite or has c == 0
+    back (this waits for the stream) and raises; check=False leaves it in `bad`.
+    -> (pcand: flat tensor of 4*K*N elements, bad)."""
+    import torch
+    H, W = _shape(shape)
+    N = H * W
+    planes = _flat(planes, "planes", torch.float64, 4 * N)
+    offsets, taps = _vec(offsets, "offsets"), _taps(taps)
+    Ko, Tn = offsets.shape[0], taps.shape[0]
+    M = 0
+    if sources is not None:
+        if not isinstance(sources, torch.Tensor) or sources.dim() != 3 or sources.shape[1] * sources.shape[2] != 4 * N:
+            raise StereoHipError("sources must be a contiguous (M, N, 4) float64 tensor on the device")
+        M = sources.shape[0]
+        sources = _flat(sources, "sources", torch.float64, M * 4 * N)
+    K = Ko + M * Tn
+    dev = planes.device
+    made_here = d_offsets is None or (d_taps is None and M * Tn)
+    d_offsets = to_device_vector(offsets) if d_offsets is None else _flat(d_offsets, "d_offsets", torch.float64, Ko)
+    if M * Tn:
+        d_taps = taps_to_device(taps) if d_taps is None else _flat(d_taps, "d_taps", torch.int32, 2 * Tn)
+    if made_here and stream is not None:
+        torch.cuda.current_stream().synchronize()     # the copies ran on torch's current stream, the kernel will not
+    pcand = (torch.empty(4 * max(K, 1) * N, dtype=torch.float64, device=dev) if pcand is None
+             else _flat(pcand, "pcand", torch.float64, 4 * K * N))
+    bad = torch.zeros(1, dtype=torch.int32, device=dev) if bad is None else _flat(bad, "bad", torch.int32, 1)
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_plane_candidates_gather_device(
+        _vp(planes), C.c_int(H), C.c_int(W), _p(offsets), _vp(d_offsets), C.c_int(Ko), _vp(sources) if M * Tn else None,
+        C.c_int(M), _p(taps, C.c_int32) if M * Tn else None, _vp(d_taps) if M * Tn else None, C.c_int(Tn), _vp(pcand),
+        _vp(bad), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    if check:
+        n = int(bad.item())
+        if n:
+            raise StereoHipError("gather_device: the own plane or a source's plane has c == 0 or a component that is not "
+                                 "finite at %d pixel(s)" % n)
+    return pcand, bad
+
+
+def plane_candidates_inputs_device(source, pcand, shape, conn, d_min=0.0, d_step=0.0, unary=None, q=None, qprim=None,
+                                   bad=None, stream=None, check=True):
+    """stereo_plane_candidates_inputs_*_device on torch tensors: `pcand` a flat float64 tensor of 4*K*N elements for an
+    image of `shape` = (H, W); the rest as plane_band.plane_band_inputs_device.  check=True reads the count of pixels
+    with a candidate that has c == 0 or is not finite back and raises.
+    -> (unary, q, qprim, bad): flat tensors K*N, K*E, K*E and the int32 counter."""
+    import torch
+    source = _source(source)
+    d_min, d_step = _rescale(source, d_min, d_step)
+    H, W = _shape(shape)
+    _check_source_shape(source, H, W, "plane_candidates_inputs_device")
+    N = H * W
+    pcand, K = _device_table(pcand, N)
+    conn = _flat(conn, "conn", torch.int32)
+    if conn.numel() % 2:
+        raise StereoHipError("conn must hold 2 E entries")
+    E = conn.numel() // 2
+    dev = pcand.device
+    fresh = source.device()
+    if stream is not None:
+        torch.cuda.current_stream().synchronize()         # (the source's copies ran on torch's current stream)
+    unary = torch.empty(K * N, dtype=torch.float64, device=dev) if unary is None else _flat(unary, "unary", torch.float64, K * N)
+    q = torch.empty(K * E, dtype=torch.float64, device=dev) if q is None else _flat(q, "q", torch.float64, K * E)
+    qprim = torch.empty(K * E, dtype=torch.float64, device=dev) if qprim is None else _flat(qprim, "qprim", torch.float64, K * E)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev) if bad is None else _flat(bad, "bad", torch.int32, 1)
+    err = _lib.errbuf()
+    tail = (_vp(pcand), C.c_int(K), C.c_int64(E), _vp(conn), _vp(unary), _vp(q), _vp(qprim), _vp(bad),
+            C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    if source.kind == "ncc":
+        rc = _lib.lib().stereo_plane_candidates_inputs_ncc_device(
+            _vp(fresh.d_vol), C.c_int(H), C.c_int(W), C.c_int(source.D), C.c_int(source.layout), _p(source.disparities),
+            _vp(fresh.d_disparities), C.c_double(source.unary_weight), *tail)
+    else:
+        rc = _lib.lib().stereo_plane_candidates_inputs_globalstereo_device(
+            _vp(fresh.d_im0), _vp(fresh.d_im1), C.c_int(H), C.c_int(W), C.c_int(source.C), _p(source.P2), C.c_double(d_min),
+            C.c_double(d_step), C.c_double(source.col_thresh), *tail)
+    _lib.check(rc, err)
+    if check:
+        n = int(bad.item())
+        if n:
+            raise StereoHipError("plane_candidates_inputs_device: a candidate has c == 0 or a component that is not finite "
+                                 "at %d pixel(s)" % n)
+    return unary, q, qprim, bad
+
+
+def plane_candidates_apply_device(pcand, labels, shape, out=None, bad=None, stream=None, check=True):
+    """stereo_plane_candidates_apply_device: `pcand` a flat float64 tensor of 4*K*N elements, `labels` a flat int32
+    tensor, one based.  check=True reads the count of labels outside 1 .. K back and raises.  -> (out (N, 4), bad)."""
+    import torch
+    H, W = _shape(shape)
+    N = H * W
+    pcand, K = _device_table(pcand, N)
+    labels = _flat(labels, "labels", torch.int32, N)
+    out = torch.empty((N, 4), dtype=torch.float64, device=pcand.device) if out is None else _flat(out, "out", torch.float64, 4 * N)
+    bad = torch.zeros(1, dtype=torch.int32, device=pcand.device) if bad is None else _flat(bad, "bad", torch.int32, 1)
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_plane_candidates_apply_device(_vp(pcand), C.c_int(H), C.c_int(W), C.c_int(K), _vp(labels), _vp(out),
+                                                         _vp(bad), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    if check:
+        n = int(bad.item())
+        if n:
+            raise StereoHipError("plane_candidates_apply_device: %d label(s) outside 1 .. %d" % (n, K))
+    return out, bad
+
+
+# ---------------------------------------------------------------- levels
+
+def check_level(level):
+    """A plane-candidate level as dict(offsets: float64 vector, taps: T x 2 int32, sources: list of 'base' / 4 x N plane
+    arrays / OrOwn), checked as far as it can be without the image: the band's rules for the offsets, whole-number taps
+    below 2^15, K = Ko + M T within 1 .. max_offsets()."""
+    if not isinstance(level, dict) or set(level) - {"offsets", "taps", "sources"}:
+        raise StereoHipError("a plane-candidate level must be dict(offsets=, taps=, sources=) (got %r)" % (level,))
+    offsets = _vec(level.get("offsets", [0.0]), "a level's offsets")
+    if offsets.shape[0] < 1 or not (np.isfinite(offsets).all() and (np.diff(offsets) > 0).all() and (offsets == 0.0).any()):
+        raise StereoHipError("plane candidates: a vector of offsets must be finite, strictly ascending and contain 0 (got %s)"
+                             % (offsets.tolist(),))
+    taps = _taps(level.get("taps", ()))
+    if taps.size and np.abs(taps).max() >= 1 << 15:
+        raise StereoHipError("plane candidates: a tap's |dy| and |dx| must be below 2^15")
+    sources = level.get("sources", ())
+    if isinstance(sources, (str, np.ndarray, OrOwn)):
+        sources = [sources]
+    sources = list(sources)
+    for s in sources:
+        if isinstance(s, str):
+            if s != "base":
+                raise StereoHipError("plane candidates: a source is 'base' or 4 x N planes (got %r)" % (s,))
+        elif not isinstance(s, OrOwn) and (np.ndim(s) != 2 or np.shape(s)[0] != 4):
+            raise StereoHipError("plane candidates: a source is 'base' or 4 x N planes")
+    K = offsets.shape[0] + len(sources) * taps.shape[0]
+    if K > band.max_offsets():
+        raise StereoHipError("plane candidates: K = Ko + M * T must be 1 .. %d (got %d)" % (band.max_offsets(), K))
+    return dict(offsets=offsets, taps=taps, sources=sources)
+
+
+def check_levels(levels):
+    """`levels` as a list of checked plane-candidate levels (check_level); at least one."""
+    if isinstance(levels, dict):
+        levels = [levels]
+    levels = [check_level(l) for l in levels]
+    if not levels:
+        raise StereoHipError("refine_plane_candidates: levels must hold at least one plane-candidate level")
+    return levels
+
+
+class PlaneCandidateProblem(PlaneBandProblem):
+    """One object's plane-candidate problems on the device, with PlaneBandProblem's interface: the source's data, the
+    connectivity and the smoothness weights go up once; build() gathers a level's table around the current planes, makes
+    its inputs and binds them to `plan`; apply() reads the table and moves the planes on.  A level's labels have no
+    common offset grid, so it neither takes nor leaves carried messages: carry_from() gives None."""
+
+    def __init__(self, source, planes, conn, alphas=None, d_min=0.0, d_step=0.0):
+        super().__init__(source, planes, conn, alphas, d_min, d_step)
+        self.shape = (self.source.H, self.source.W)
+        self.d_pcand = None
+
+    @staticmethod
+    def labels_of(level):
+        return level["offsets"].shape[0] + len(level["sources"]) * level["taps"].shape[0]
+
+    def _source_tensor(self, level):
+        import torch
+        maps = []
+        for s in level["sources"]:
+            if isinstance(s, str):
+                maps.append(self.d_planes.view(self.N, 4))
+                continue
+            fill = isinstance(s, OrOwn)
+            s = _planes(s.planes if fill else s, self.N)
+            t = torch.from_numpy(np.array(s.T, order="C")).cuda()              # (N, 4)
+            if fill:
+                t = torch.where(torch.isfinite(t).all(dim=1, keepdim=True), t, self.d_planes.view(self.N, 4))
+            maps.append(t)
+        return torch.stack(maps).contiguous() if maps and level["taps"].shape[0] else None
+
+    def build(self, level, plan, tol, carry=None):
+        """The inputs of the plane-candidate level `level` (check_level's dict) around the current planes, bound to
+        `plan`.  carry must be None."""
+        import torch
+        if carry is not None:
+            raise StereoHipError("plane candidates: a plane-candidate level does not take carried messages")
+        self.offsets = level["offsets"]
+        self.d_offsets = to_device_vector(self.offsets)
+        self.d_pcand, _ = gather_device(self.d_planes, self.offsets, self.shape, self._source_tensor(level), level["taps"],
+                                        d_offsets=self.d_offsets)
+        self.d_unary, self.d_q, self.d_qprim, _ = plane_candidates_inputs_device(
+            self.source, self.d_pcand, self.shape, self.d_conn, self.d_min, self.d_step)
+        torch.cuda.current_stream().synchronize()
+        plan.bind_device(self.d_unary.data_ptr(), self.d_alphas.data_ptr(), tol, d_q=self.d_q.data_ptr(),
+                         d_qprim=self.d_qprim.data_ptr(), keepalive=[self.d_unary, self.d_q, self.d_qprim, self.d_alphas])
+
+    def carry_from(self, plan, labels):
+        return None
+
+    def apply(self, labels):
+        """The planes the labels of the level built last select -> the new planes on the host, 4 x N."""
+        import torch
+        lab = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)).cuda()
+        self.d_planes, _ = plane_candidates_apply_device(self.d_pcand, lab, self.shape)
+        return np.asfortranarray(self.d_planes.cpu().numpy().T)
+
+
+def refine_plane_candidates(source, planes, kernel, tol, levels, maxiter, max_relgap, alphas=None, conn=None, d_min=0.0,
+                            d_step=0.0):
+    """Refines the plane map `planes` (4 x N) level by level: for each plane-candidate level in `levels` --
+    dict(offsets=, taps=, sources=), a source being 'base' (the current planes) or 4 x N planes -- the table is gathered
+    around the current planes on the device, its problem built (stereo_plane_candidates_inputs_*_device), bound to a
+    TrwsPlan(kernel, K, N, conn) -- one plan per distinct K -- iterated up to `maxiter` times (`max_relgap` as in trws)
+    and applied; the selected planes are the next level's.  The source's data goes to the device once; nothing K x N or
+    K x E touches the host.  conn: 2 x E zero based, default the image grid; d_min / d_step: the rescaling of the
+    positions and of the globalstereo unary.  Every level starts from zero messages.
+    -> plane_band.PlaneBandResult (`carried` all False)."""
+    levels = check_levels(levels)
+    source = _source(source)
+    conn = T.construct_neighborhood(source.H, source.W) if conn is None else conn
+    prob = PlaneCandidateProblem(source, planes, conn, alphas, d_min, d_step)
+    out = PlaneBandResult()
+    plans = {}
+    try:
+        for level in levels:
+            K = prob.labels_of(level)
+            if K not in plans:
+                plans[K] = TrwsPlan(int(kernel), K, prob.N, prob.conn)
+            plan = plans[K]
+            prob.build(level, plan, tol)
+            out.carried.append(False)
+            plan.iterate(maxiter, max_relgap)
+            labels, en, lb, it = plan.result()
+            out.paths.append(plan.path())
+            out.labels.append(labels); out.energy.append(en); out.lower_bound.append(lb); out.iterations.append(it)
+            out.plane_maps.append(prob.apply(labels))
+        out.planes = out.plane_maps[-1]
+    finally:
+        for plan in plans.values():
+            plan.close()
+    return out
