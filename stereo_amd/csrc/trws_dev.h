@@ -1219,11 +1219,12 @@ constexpr int kPipeCompute = 8;  // one compute wave per outgoing message (<= 8 
 constexpr int kPipeWaves = kPipeCompute + 4;  // loader (data behind flags), storer, loader A (own data, two visits
                                               // deep; trws_pipe_kernel only), primal
 constexpr int kPipeThreads = kPipeWaves * kWave;
-// LDS stage layout (doubles): D[64] m[8][64] qv[8][64] qpv[8][64] | a[8] gamma pad | ints: desc[64] px[8] row[8]
+// LDS stage layout (doubles): D[64] m[8][64] qv[8][64] qpv[8][64] | a[8] gamma pad | ints: desc[64] px[8] row[8] | P[64]
 constexpr int kStD = 0, kStM = 64, kStQ = 64 + 512, kStQP = 64 + 1024, kStA = 64 + 1536;
 constexpr int kStG = kStA + 8;                    // gamma = 1 / max(n_out, n_in) of the node (the loader's division)
 constexpr int kStI = kStA + 10;                   // int area starts here (as doubles)
-constexpr int kStageDoubles = kStI + 40;          // ints: desc[64] px[8] row[8] (where Di's k-th message row lives in LDS)
+constexpr int kStP = kStI + 40;                   // ints: desc[64] px[8] row[8] (where the k-th INCOMING message row of Di lives in LDS)
+constexpr int kStageDoubles = kStP + kWave;       // P: the prefix of Di in list order, D + the outgoing rows (loader A's sum)
 constexpr int kScalDoubles = 16;                  // newv[8], node_vmin, prim_e, x (as int)
 constexpr int kPipePad = 16;                      // source tables are padded by this many (+inf) entries on both sides
 constexpr int kPipeScr = 66;                      // doubles of scratch behind a wave's table: 129 ints of build_envelope_parallel

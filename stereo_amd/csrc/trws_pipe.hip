@@ -191,8 +191,8 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
         if (UPDATE && have_node) {
           const int *sti = (const int *)(st + kStI);
           const int f = __builtin_amdgcn_readfirstlane(sti[2]);
-          const int nout = f & 15, md = (f >> 16) & 255;
-          const int myrow = sti[72 + (lane & 7)];  // LDS offsets (doubles) of the node's message rows, from the loader
+          const int nout = f & 15, nin = (f >> 4) & 15, md = (f >> 16) & 255;
+          const int myrow = sti[72 + (lane & 7)];  // LDS offsets (doubles) of the node's incoming message rows, from the loader
           const unsigned twins = SHARED ? (unsigned)__builtin_amdgcn_readfirstlane(sti[kDescTwin]) : 0x76543210u;
           // lanes 0-7: the edge ids of the node's messages, lane 8: the granule word -- one LDS read in flight with the
           // ones above, so that publishing behind the message waits for no LDS round trip (it used to wait for three)
@@ -200,24 +200,31 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
           const int gpub = p.gran ? (RLI(gword, 8) >> 8) & 255 : 0;   // messages published as granules
           VSTAMP(0);
           if (wave < nout || (BACKWARD && wave == 0)) {  // waves without a message stay out of the way
-          double Di = act ? st[kStD + lane] : 0.0;
-          // (this wave's own old message is one of the rows; it is read once more below rather than
-          //  picked out of the loop with eight selects)
+          // the prefix of Di in list order -- the unary row and the outgoing rows, last sweep's messages -- is
+          // loader A's sum, staged once per node (a lane beyond K holds a value nobody uses)
+          double Di = st[kStP + lane];
+          // (this wave's own old message is one of the prefix's rows; it is read from its stage row)
           const double mown = st[kStM + (wave < nout ? wave : 0) * kWave + lane];
           const int partner = wave < nout ? (int)((twins >> (4 * wave)) & 15u) : wave;
           const int twin_mask = (SHARED && KERNEL == 1) ? __builtin_amdgcn_readfirstlane((int)st[kStA + 9]) : 0;   // (loader A's verdict)
           const double alpha_me = st[kStA + (wave < nout ? wave : 0)];
-          // (all eight rows are requested together and added in list order; a row the node does not have
-          //  is the zero row -- x + 0.0 == x --, so nothing here branches on the node's degree and the
-          //  reads share one LDS latency instead of paying one each)
-          //  (per-edge positions: two batches of four -- that kernel has no registers to spare)
+          // (the tail -- list positions nout .. nout + 3, the incoming rows of an ordinary node -- is requested
+          //  together and added in list order; a position the node does not have is the zero row -- x + 0.0 == x --,
+          //  so nothing here branches on the node's degree and the reads share one LDS latency instead of paying
+          //  one each; a node with more than four incoming rows -- border chain, row ends, off-grid graphs --
+          //  takes one uniform branch for positions nout + 4 ..)
+          {
+            double rowv[4];
 #pragma unroll
-          for (int b = 0; b < 8; b += (SHARED ? 8 : 4)) {
-            double rowv[8];
+            for (int j = 0; j < 4; ++j) rowv[j] = lds[__builtin_amdgcn_readlane(myrow, j) + lane];
 #pragma unroll
-            for (int j = 0; j < (SHARED ? 8 : 4); ++j) rowv[j] = lds[__builtin_amdgcn_readlane(myrow, b + j) + lane];
+            for (int j = 0; j < 4; ++j) Di += rowv[j];
+            if (nin > 4) {
 #pragma unroll
-            for (int j = 0; j < (SHARED ? 8 : 4); ++j) Di += rowv[j];
+              for (int j = 0; j < 4; ++j) rowv[j] = lds[__builtin_amdgcn_readlane(myrow, 4 + j) + lane];
+#pragma unroll
+              for (int j = 0; j < 4; ++j) Di += rowv[j];
+            }
           }
           double node_vmin = 0;
           if (BACKWARD) {
@@ -319,14 +326,17 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
             ++ndep;
           }
           {
-            // where the compute waves find the node's message rows at visit pos + 1: a message handed
+            // where the compute waves find the tail of Di at visit pos + 1 -- entry k: list position nout + k, the
+            // node's k-th incoming row; the outgoing rows are in loader A's prefix --: a message handed
             // over inside the run sits in the ring of the last two visits, everything else in this
-            // stage, a row the node does not have is the zero row -- decided once here instead of by
+            // stage, a position the node does not have is the zero row -- decided once here instead of by
             // every compute wave in scalar code
-            const int row = j8 >= ntot ? (int)(zrow - lds)
-                          : (j8 < nout || sl < 0) ? (int)(stn - lds) + kStM + j8 * kWave
-                          : sl >= 8 ? (int)(hand - lds) + ((pos - 1) & 3) * 8 * kWave + (sl - 8) * kWave
-                                    : (int)(hand - lds) + (pos & 3) * 8 * kWave + sl * kWave;
+            const int q8 = (nout + j8) & 7;
+            const int slq = sfirst ? -1 : __shfl(w, 12 + q8, kWave);
+            const int row = nout + j8 >= ntot ? (int)(zrow - lds)
+                          : slq < 0 ? (int)(stn - lds) + kStM + q8 * kWave
+                          : slq >= 8 ? (int)(hand - lds) + ((pos - 1) & 3) * 8 * kWave + (slq - 8) * kWave
+                                     : (int)(hand - lds) + (pos & 3) * 8 * kWave + slq * kWave;
             if (lane < 8) stni[72 + lane] = row;
           }
           // (everything that does not depend on other workgroups -- unary, previous-sweep messages,
@@ -446,11 +456,15 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
           const int f = RLI(wa1, 2);
           const int nout = f & 15, nin = (f >> 4) & 15;
           stn[kStD + lane] = rdk;
+          // (the prefix of Di in list order, ((D + m_0) + m_1) + ..: the association the compute waves used to form, each
+          //  by itself, from the rows written here -- those stay for the primal wave, the waves' own rows and the twin verdict)
+          double pk = rdk;
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
-            if (j < nout) stn[kStM + j * kWave + lane] = rmv[j];
+            if (j < nout) { stn[kStM + j * kWave + lane] = rmv[j]; if (UPDATE) pk += rmv[j]; }
             if (!SHARED && j < nout + nin) { stn[kStQ + j * kWave + lane] = rqv[j]; stn[kStQP + j * kWave + lane] = rqpv[j]; }
           }
+          if (UPDATE) stn[kStP + lane] = pk;
           if (SPEC && UPDATE && seg >= 0 && !second_walk) {
             // a speculative segment keeps the rows its visits overwrite: a second walk starts from them (below)
 #pragma unroll

@@ -162,6 +162,16 @@ void launch_persistent(stereo_trws_plan *P, const DevParams &p, int what, hipStr
       int blocks = P->grid_blocks;
       static const char *be = std::getenv("STEREO_HIP_TRWS_BLOCKS");   // (development: workgroups of a pipelined sweep launch)
       if (be && std::atoi(be) > 0) blocks = std::min(blocks, std::atoi(be));
+      // (development, STEREO_HIP_TRWS_TIMELINE=first: the fused launches leave the timeline alone, so that direction 0 keeps
+      //  the plan's first forward launch -- the only one without a primal pass; a single plan's own K <= 64 launches only,
+      //  which is where the row-lag record of DESIGN.md 4.4 is taken: groups, batches and the other families ignore it)
+      static const bool tl_first = [] { const char *c = std::getenv("STEREO_HIP_TRWS_TIMELINE"); return c && std::string(c) == "first"; }();
+      if (tl_first && what == 2) {
+        DevParams q = p;
+        q.timeline = nullptr;
+        launch_pipe(P->kernel, P->pos != nullptr, what, blocks, s, q, epoch);
+        break;
+      }
       launch_pipe(P->kernel, P->pos != nullptr, what, blocks, s, p, epoch);
       break;
     }

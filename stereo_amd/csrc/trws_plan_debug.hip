@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <limits>
 
 #include "trws_plan.h"
@@ -62,8 +63,16 @@ void print_timeline(const stereo_trws_plan *plan) {
                         : (chain ? plan->graph->sweep[0].chain_run_ptr.size() : plan->graph->sweep[0].run_ptr.size()) - 1;
   std::vector<unsigned long long> t(4 * (R + 1) + 8);
   if (hipMemcpy(t.data(), plan->d_timeline.p, sizeof(unsigned long long) * (4 * R + 4), hipMemcpyDeviceToHost) == hipSuccess) {
+    // (STEREO_HIP_TRWS_TIMELINE=first, trws_plan.hip: launch_persistent -- direction 0's run stamps are the first forward
+    //  launch's, but the runner stamps through the plan's own parameter block, in every launch: its line would set the
+    //  first launch's segments against the last launch's runner)
+    const char *tl = std::getenv("STEREO_HIP_TRWS_TIMELINE");
+    const bool first = tl && std::strcmp(tl, "first") == 0;
+    if (first)
+      std::fprintf(stderr, "[stereo_hip timeline] dir 0: the plan's FIRST forward launch (no primal pass); its runner line is left out (the runner's "
+                           "stamps are the last launch's)\n");
     if (spec)
-      for (int d = 0; d < 2; ++d) {
+      for (int d = first ? 1 : 0; d < 2; ++d) {
         const auto &sp = own_spec(plan, d);
         const unsigned long long t0 = t[(2 * R + d) * 2];
         std::fprintf(stderr, "[stereo_hip timeline] dir %d speculative: runner %.0f us; segments (us since the runner started, start..commit): ", d,
