@@ -44,6 +44,16 @@ constexpr int kRsNt = 0, kRsKinds = 1, kRsNmsg = 2, kRsCut = 5, kRsPubKinds = 6,
 typedef __attribute__((address_space(3))) int spec_lds_int;
 __device__ __forceinline__ int lds_load(const int *w) { return __hip_atomic_load((const spec_lds_int *)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_store(int *w, int v) { __hip_atomic_store((spec_lds_int *)w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+// The dynamic LDS allocation as a role of the runner addresses it.  The roles are real (noinline) functions: there the
+// compiler finds the allocation's offset in a table in memory, and between the compiler barriers of a visit it loads
+// that word again -- a scalar load and a full wait on the path of every visit.  Read once and pinned to a scalar
+// register, the offset is a value like any other for the whole walk.
+typedef __attribute__((address_space(3))) double spec_lds_double;
+__device__ __forceinline__ double *pinned_lds(double *dyn) {
+  unsigned off = (unsigned)(size_t)(spec_lds_double *)dyn;
+  asm volatile("" : "+s"(off));
+  return (double *)(spec_lds_double *)(size_t)off;
+}
 #define SPEC_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local")
 #define SPEC_RELEASE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local")
 
@@ -346,7 +356,7 @@ struct RunArgsM {
 // next node's go.  Everything that steers the visit is a scalar; the lanes only ever do the arithmetic.
 template <bool BACKWARD, int G>
 __device__ __forceinline__ bool run_visit_m(const RunArgsM &a, double *rb, int *rw, double *tabl, int *cons_word, int lane, bool act, int i, int &slot_off,
-                                            RunNodeM &cur, RunNodeM &nxt, double &A0, double &A1, double (&ad)[4 * G], double &alpha_have,
+                                            RunNodeM &cur, RunNodeM &nxt, double &A0, double &A1, double (&ad)[4 * G], double &alpha_have, double &al,
                                             int *abort_word) {
   const double inf = __builtin_huge_val();
   if (__builtin_amdgcn_readlane(cur.sw, kRsTag) != i + 1) {   // (not there yet when it was asked for)
@@ -360,8 +370,18 @@ __device__ __forceinline__ bool run_visit_m(const RunArgsM &a, double *rb, int *
   const int key = __builtin_amdgcn_readlane(sw, kRsKinds), nmsg = __builtin_amdgcn_readlane(sw, kRsNmsg), cut = __builtin_amdgcn_readlane(sw, kRsCut);
   double Di = cur.P;
   // the tail of the node's list from the first handed-over row on, in list order (the order of the reference's additions)
-  if (key == 0x20098) { Di += A0; Di += A1; }                                   // handed over, handed over (forward chain)
-  else if (key == 0x30908) { Di += A0; Di += cur.S0; Di += A1; }                // ... with a row of another run in between
+  // (the direction's common keys first, on a copy of the key that is opaque to the compiler: one chain of equality
+  //  tests becomes a search tree, which put two dozen scalar instructions and seven branches in front of two additions.
+  //  Forward, every chain node but two has 0x20098.  Backward it is the handed-over pair with the interior row behind it,
+  //  0x30098, or in between, 0x30908, about half the chain each: ONE test for the two, the order by a select)
+  int key_first = key;
+  asm volatile("" : "+s"(key_first));
+  const bool between = BACKWARD && key_first == 0x30908;
+  if (BACKWARD) key_first ^= between ? 0x30908 ^ 0x30098 : 0;
+  if (!BACKWARD && __builtin_expect(key_first == 0x20098, 1)) { Di += A0; Di += A1; }               // handed over, handed over
+  else if (BACKWARD && __builtin_expect(key_first == 0x30098, 1)) { Di += A0; Di += between ? cur.S0 : A1; Di += between ? A1 : cur.S0; }
+  else if (key == 0x20098) { Di += A0; Di += A1; }
+  else if (key == 0x30908) { Di += A0; Di += cur.S0; Di += A1; }
   else if (key == 0x30098) { Di += A0; Di += A1; Di += cur.S0; }
   else if (key == 0x41908) { Di += A0; Di += cur.S0; Di += A1; Di += cur.S1; }
   else {
@@ -393,21 +413,26 @@ __device__ __forceinline__ bool run_visit_m(const RunArgsM &a, double *rb, int *
         asm volatile("" ::: "memory");
 #pragma unroll
         for (int d = 0; d < 4 * G; ++d) ad[d] = alpha * ((double)(d + 1) * a.step);
+        al = alpha * a.lambda;
         alpha_have = alpha;
       }
-      const double hmin = wave_min_dpp(h);
-      const double vtrunc = hmin + alpha * a.lambda;
+      // the window's reads go out behind the write of h and IN FRONT of the reduction, whose two dozen instructions
+      // then hide their latency (LDS serves one wave's requests in order: the reads need the write and nothing else)
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       double lo[4 * G], hi[4 * G];
 #pragma unroll
       for (int d = 0; d < 4 * G; ++d) { lo[d] = tabl[-(d + 1)]; hi[d] = tabl[d + 1]; }
-      double ma = h, mb = vtrunc;   // (two chains)
+      __builtin_amdgcn_sched_barrier(0);
+      const double hmin = wave_min_dpp(h);
+      __builtin_amdgcn_sched_barrier(0);   // (or the window's first additions, and the wait for its reads, move up into the reduction)
+      const double vtrunc = hmin + al;
+      double ma = h, mb = hi[0] + ad[0];   // (two chains; the truncation value joins last: a minimum is exact in any order)
 #pragma unroll
-      for (int d = 0; d < 4 * G; ++d) { ma = min_raw(ma, lo[d] + ad[d]); mb = min_raw(mb, hi[d] + ad[d]); }
+      for (int d = 0; d < 4 * G; ++d) { ma = min_raw(ma, lo[d] + ad[d]); if (d > 0) mb = min_raw(mb, hi[d] + ad[d]); }
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      out = min_raw(ma, mb) - hmin;
+      out = min_raw(min_raw(ma, mb), vtrunc) - hmin;
     }
     if (m == 0) R0 = out; else R1 = out;
   }
@@ -436,6 +461,7 @@ __device__ __forceinline__ void run_messages_g(const RunArgsM &a, double *rb, in
 #pragma unroll
   for (int d = 0; d < 4 * G; ++d) ad[d] = 0;
   double alpha_have = 0;   // (never a weight that takes the window path)
+  double al = 0;           // alpha lambda for that weight
   double A0 = 0, A1 = 0;
   RunNodeM na, nb;
   run_request_m(rb, lane, na);
@@ -443,8 +469,8 @@ __device__ __forceinline__ void run_messages_g(const RunArgsM &a, double *rb, in
   int slot_off = 0;
   // (two visits per trip: the nodes' registers swap roles instead of being copied)
   for (int i = a.c0; i < a.c1; i += 2) {
-    if (!run_visit_m<BACKWARD, G>(a, rb, rw, tabl, cons_word, lane, act, i, slot_off, na, nb, A0, A1, ad, alpha_have, abort_word)) return;
-    if (i + 1 < a.c1 && !run_visit_m<BACKWARD, G>(a, rb, rw, tabl, cons_word, lane, act, i + 1, slot_off, nb, na, A0, A1, ad, alpha_have, abort_word)) return;
+    if (!run_visit_m<BACKWARD, G>(a, rb, rw, tabl, cons_word, lane, act, i, slot_off, na, nb, A0, A1, ad, alpha_have, al, abort_word)) return;
+    if (i + 1 < a.c1 && !run_visit_m<BACKWARD, G>(a, rb, rw, tabl, cons_word, lane, act, i + 1, slot_off, nb, na, A0, A1, ad, alpha_have, al, abort_word)) return;
   }
 }
 
@@ -456,8 +482,9 @@ __device__ __attribute__((noinline)) void run_messages(const DevParams *pp) {
   a.K = uniform_value(pp->K); a.window = uniform_value(pp->window); a.c0 = uniform_value(pp->spec_c0[D]); a.c1 = uniform_value(pp->spec_c1[D]);
   a.lambda = uniform_value(pp->lambda); a.step = uniform_value(pp->uniform_step);
   a.abort_flag = uniform_value(pp->abort_flag); a.spin_ticks = uniform_value(pp->spin_ticks); a.stat = uniform_value(pp->spec_stat);
-  double *rb = run_lds + kRunBase;
-  int *abort_word = (int *)run_lds + kRunAbortInt;
+  double *lds0 = pinned_lds(run_lds);
+  double *rb = lds0 + kRunBase;
+  int *abort_word = (int *)lds0 + kRunAbortInt;
   const int lane = threadIdx.x & (kWave - 1);
   // the window in groups of four entries (entries beyond it cost >= vTrunc bit for bit, finish_inputs checks the spacing);
   // windows of more than eight entries keep the plain schedule (spec_active, trws_plan.hip)
@@ -477,63 +504,88 @@ __device__ __forceinline__ void run_request_p(const double *sl, int lane, RunNod
   n.TH = sl[kRunRowTH + lane];
   n.O0 = sl[kRunRowOUT + lane]; n.O1 = sl[kRunRowOUT + 64 + lane]; n.O2 = sl[kRunRowOUT + 128 + lane]; n.O3 = sl[kRunRowOUT + 192 + lane];
 }
-template <bool BACKWARD>
-__device__ __attribute__((noinline)) void run_labels(const DevParams *pp_) {
-  extern __shared__ __attribute__((aligned(16))) double run_lds[];
-  const DevParams p = uniform_params(pp_);
-  double *rb = run_lds + kRunBase;
-  int *abort_word = (int *)run_lds + kRunAbortInt;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int c0 = p.spec_c0[BACKWARD ? 1 : 0], c1 = p.spec_c1[BACKWARD ? 1 : 0];
+// What the labels need of the launch parameters, as uniform values.
+struct RunArgsP {
+  int c0, c1;
+  double lambda;
+  int32_t *abort_flag;
+  long long spin_ticks;
+};
+// One visit of the labels' recurrence, built like run_visit_m: the node's words and rows were asked for during the visit
+// before, the waits are calls whose result is declared uniform (inlined, their look at the abort flag in global memory
+// makes every exit of the walk an exec-mask region), the word that frees the ring slot is stored by all lanes (lane 0
+// hits the word, the others the words nobody reads) and the ring offset is carried, not divided out.
+__device__ __forceinline__ bool run_visit_p(const RunArgsP &a, double *rb, int *rw, int *cons_word, int lane, bool act, double posk, int i, int &slot_off,
+                                            RunNodeP &cur, RunNodeP &nxt, int &xprev, int *abort_word) {
   const double inf = __builtin_huge_val();
-  const int K = p.K;
+  if (RLI(cur.sw, kRsTag) != i + 1) {
+    if (!__builtin_amdgcn_readfirstlane((int)run_wait((const int *)(rb + slot_off + kRunSc) + kRsTag, i + 1, abort_word, a.abort_flag, a.spin_ticks))) return false;
+    run_request_p(rb + slot_off, lane, cur);
+  }
+  const int sw = cur.sw;
+  const double sd = cur.sd;
+  const int nout = RLI(sw, kRsNout), nin = RLI(sw, kRsNin), md = RLI(sw, kRsMd), cut = RLI(sw, kRsCut);
+  double db = act ? cur.TH : 0.0;
+  const double o0 = cur.O0, o1 = cur.O1, o2 = cur.O2, o3 = cur.O3;
+  lds_store(cons_word, i + 1 - a.c0);
+  slot_off += kRunSlotDoubles;
+  if (slot_off == kRunSlots * kRunSlotDoubles) slot_off = 0;
+  if (i + 1 < a.c1) run_request_p(rb + slot_off, lane, nxt);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (k < nin) {
+      const int src = RLI(sw, kRsSrc + k);
+      const int ks = src < 0 ? xprev : src;
+      const double pks = readlane_f64(posk, ks);
+      const double d = ((md >> k) & 1) == 0 ? pks - posk : posk - pks;
+      db += readlane_f64(sd, 3 + k) * min_raw(fabs(d), a.lambda);
+    }
+  }
+  double di = db;
+  if (nout > 0) di += o0;
+  if (nout > 1) di += o1;
+  if (nout > 2) di += o2;
+  if (nout > 3) di += o3;
+  const double dim = act ? di : inf;
+  const double vbest = wave_min_dpp(dim);
+  xprev = __builtin_ctzll(__builtin_amdgcn_ballot_w64(dim == vbest));
+  if (cut) {
+    const int ps = cut & 1;
+    if (__builtin_amdgcn_readfirstlane(lds_load(rw + kSwFree)) < cut - 2 &&
+        !__builtin_amdgcn_readfirstlane((int)run_wait(rw + kSwFree, cut - 2, abort_word, a.abort_flag, a.spin_ticks))) return false;
+    SPEC_ACQUIRE();
+    if (lane == 0) { rw[kSwLabel + ps] = xprev; rw[kSwNode + ps] = RLI(sw, kRsNode); }
+    SPEC_RELEASE();
+    if (lane == 0) lds_store(rw + kSwPubP + ps, cut);
+  }
+  return true;
+}
+template <bool BACKWARD>
+__device__ __attribute__((noinline)) void run_labels(const DevParams *pp) {
+  extern __shared__ __attribute__((aligned(16))) double run_lds[];
+  constexpr int D = BACKWARD ? 1 : 0;
+  RunArgsP a;
+  a.c0 = uniform_value(pp->spec_c0[D]); a.c1 = uniform_value(pp->spec_c1[D]); a.lambda = uniform_value(pp->lambda);
+  a.abort_flag = uniform_value(pp->abort_flag); a.spin_ticks = uniform_value(pp->spin_ticks);
+  const int K = uniform_value(pp->K);
+  const double *pos = uniform_value(pp->pos);
+  double *lds0 = pinned_lds(run_lds);
+  double *rb = lds0 + kRunBase;
+  int *abort_word = (int *)lds0 + kRunAbortInt;
+  const int lane = threadIdx.x & (kWave - 1);
   const bool act = lane < K;
   int *rw = (int *)(rb + kRunWords);
-  const double posk = act ? p.pos[lane] : 0.0;
-  const double lambda = p.lambda;
+  int *cons_word = lane == 0 ? rw + kSwConsP : (int *)(rb + kRunDoubles) + lane;   // (kRunDummy, as the message wave's)
+  const double posk = act ? pos[lane] : 0.0;
   int xprev = 0;
-  RunNodeP cur, nxt;
-  run_request_p(rb, lane, cur);
-  nxt = cur;
-  for (int i = c0; i < c1; ++i) {
-    const double *sl = rb + ((i - c0) % kRunSlots) * kRunSlotDoubles;
-    if (RLI(cur.sw, kRsTag) != i + 1) {
-      if (!run_wait_i<true>((const int *)(sl + kRunSc) + kRsTag, i + 1, abort_word, p.abort_flag, p.spin_ticks)) return;
-      run_request_p(sl, lane, cur);
-    }
-    const int sw = cur.sw;
-    const double sd = cur.sd;
-    const int nout = RLI(sw, kRsNout), nin = RLI(sw, kRsNin), md = RLI(sw, kRsMd), cut = RLI(sw, kRsCut);
-    double db = act ? cur.TH : 0.0;
-    const double o0 = cur.O0, o1 = cur.O1, o2 = cur.O2, o3 = cur.O3;
-    if (lane == 0) lds_store(rw + kSwConsP, i + 1 - c0);
-    if (i + 1 < c1) run_request_p(rb + ((i + 1 - c0) % kRunSlots) * kRunSlotDoubles, lane, nxt);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (k < nin) {
-        const int src = RLI(sw, kRsSrc + k);
-        const int ks = src < 0 ? xprev : src;
-        const double pks = readlane_f64(posk, ks);
-        const double d = ((md >> k) & 1) == 0 ? pks - posk : posk - pks;
-        db += readlane_f64(sd, 3 + k) * min_raw(fabs(d), lambda);
-      }
-    }
-    double di = db;
-    if (nout > 0) di += o0;
-    if (nout > 1) di += o1;
-    if (nout > 2) di += o2;
-    if (nout > 3) di += o3;
-    const double dim = act ? di : inf;
-    const double vbest = wave_min_dpp(dim);
-    xprev = __builtin_ctzll(__builtin_amdgcn_ballot_w64(dim == vbest));
-    if (cut) {
-      const int ps = cut & 1;
-      if (!run_wait_i<true>(rw + kSwFree, cut - 2, abort_word, p.abort_flag, p.spin_ticks)) return;
-      if (lane == 0) { rw[kSwLabel + ps] = xprev; rw[kSwNode + ps] = RLI(sw, kRsNode); }
-      SPEC_RELEASE();
-      if (lane == 0) lds_store(rw + kSwPubP + ps, cut);
-    }
-    cur = nxt;
+  RunNodeP na, nb;
+  run_request_p(rb, lane, na);
+  nb = na;
+  int slot_off = 0;
+  // (two visits per trip: the nodes' registers swap roles instead of being copied)
+  for (int i = a.c0; i < a.c1; i += 2) {
+    if (!run_visit_p(a, rb, rw, cons_word, lane, act, posk, i, slot_off, na, nb, xprev, abort_word)) return;
+    if (i + 1 < a.c1 && !run_visit_p(a, rb, rw, cons_word, lane, act, posk, i + 1, slot_off, nb, na, xprev, abort_word)) return;
   }
 }
 
@@ -542,8 +594,9 @@ template <bool BACKWARD, bool PRIMAL, bool UPDATE>
 __device__ __attribute__((noinline)) void run_loader(const DevParams *pp_, int epoch_, int lw_) {
   extern __shared__ __attribute__((aligned(16))) double run_lds[];
   const DevParams p = uniform_params(pp_);
-  double *rb = run_lds + kRunBase;
-  int *abort_word = (int *)run_lds + kRunAbortInt;
+  double *lds0 = pinned_lds(run_lds);
+  double *rb = lds0 + kRunBase;
+  int *abort_word = (int *)lds0 + kRunAbortInt;
   const int lane = threadIdx.x & (kWave - 1);
   const int epoch = __builtin_amdgcn_readfirstlane(epoch_), lw = __builtin_amdgcn_readfirstlane(lw_);
   constexpr int D = BACKWARD ? 1 : 0;
