@@ -85,6 +85,9 @@ struct DevParams {
   // {32-bit value, tag = the sweep's epoch} (tag in the high word), zeroed wherever `done` is.
   unsigned long long *gran;   // [E][K][2]: the high and the low half of a message entry
   unsigned long long *xgran;  // [N]: a node's label (primal sweeps)
+  // Host-made records of the K <= 64 runner's loaders (trws_runner_records.h), per direction: kRecWords words for every
+  // position spec_c0 .. spec_c1 - 1 of the bound descriptor set, or null without the speculative schedule
+  const int32_t *run_rec[2];
 };
 
 // Several strips of one problem in ONE launch (row strips that share a device: logical strips, or

@@ -76,6 +76,10 @@ struct stereo_trws_plan {
   bool sub_rows[2] = {false, false};
   stereo::DevBuf<int32_t> d_sub_desc[2], d_sub_run_ptr[2], d_sub_run_order[2];
   stereo::DevBuf<int32_t> d_sub_spec_run_ptr[2], d_sub_spec_run_order[2], d_sub_spec_kind[2];
+  // the runner's chain records (trws_runner_records.h) per direction, [0] over the chain schedule's descriptors, [1]
+  // over the sub-row schedule's, and the segment geometry {c0, c1, seg_len, nseg} each was built for
+  stereo::DevBuf<int32_t> d_run_rec[2][2];
+  int32_t run_rec_geom[2][2][4] = {};
   // which sweep kernel runs the plan (trws_family.h): the facts and the families still possible are fixed at creation,
   // the family follows every upload / bind (finish_inputs)
   stereo::TrwsPlanFacts facts;
@@ -216,6 +220,10 @@ DevParams make_params(stereo_trws_plan *P, bool allow_spec = true, bool allow_su
 // the plan's own launches walk direction d's sub-row runs; the speculative schedule over the runs they walk
 bool own_sub_rows(const stereo_trws_plan *P, int d);
 const TrwsGraph::Sweep::Spec &own_spec(const stereo_trws_plan *P, int d);
+// trws_plan_create.hip: the runner's chain records of direction d over the chain schedule's descriptors (sub false) or
+// the sub-row schedule's, for the segment geometry make_params binds with them; built and uploaded again only if that
+// geometry is not the one the device copy was made for.  Returns the device copy.
+const int32_t *runner_records(stereo_trws_plan *P, int d, bool sub);
 size_t persistent_lds_bytes(bool large, int Kp);   // dynamic LDS of the generic / the large family's sweep kernel
 constexpr int kHeldWords = 33;                     // stereo_trws_plan::h_held
 // the state of a minimisation: zero messages, labels, flags, counters of iterations (a pending sweep is discarded first)

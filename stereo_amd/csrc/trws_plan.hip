@@ -30,6 +30,7 @@
 //                        lists, rank-contiguous runs · trws_graph_schedule.cpp chain schedule, sub-row runs ·
 //                        trws_graph_desc.cpp descriptors, protocol proof, marks · trws_graph_strips.cpp strip layouts ·
 //                        trws_graph_views.cpp host views for tests · trws_graph_stages.h what the stages pass on
+//   trws_runner_records.h/.cpp  the K <= 64 runner's chain records, made from the bound descriptors (host only)
 //   trws_plan.h          struct stereo_trws_plan, the table of creation-time switches (internal)
 //   trws_plan_create.hip creation (with the cache of the last graph analysis) and destruction
 //   trws_plan.hip        this file: inputs, iterations, results, strip wiring, min-marginals
@@ -134,6 +135,7 @@ DevParams make_params(stereo_trws_plan *P, bool allow_spec, bool allow_sub) {
       p.run_ptr[d] = (sub[d] ? P->d_sub_spec_run_ptr[d] : P->d_spec_run_ptr[d]).p; p.nruns[d] = (int)sp.kind.size();
       p.run_order[d] = (sub[d] ? P->d_sub_spec_run_order[d] : P->d_spec_run_order[d]).p; p.ntickets[d] = (int)sp.run_order.size();
       p.spec_kind[d] = (sub[d] ? P->d_sub_spec_kind[d] : P->d_spec_kind[d]).p; p.spec_c0[d] = sp.c0; p.spec_c1[d] = sp.c1;
+      if (P->family == TrwsFamily::Pipe) p.run_rec[d] = runner_records(P, d, sub[d]);
     }
     const TrwsGraph::Sweep::Spec &sp = P->graph->sweep[0].spec;   // (the same segments over either set of runs)
     p.spec_len = sp.seg_len; p.spec_nseg = sp.nseg; p.spec_max_len = sp.max_len;

@@ -5,6 +5,7 @@
 #include <mutex>
 
 #include "trws_plan.h"
+#include "trws_runner_records.h"
 
 namespace stereo {
 namespace {
@@ -41,8 +42,23 @@ std::shared_ptr<const TrwsGraph> shared_graph_for(GraphKey key, std::string &ger
   return fresh;
 }
 
-
 }  // namespace
+
+const int32_t *runner_records(stereo_trws_plan *P, int d, bool sub) {
+  const TrwsGraph::Sweep &S = P->graph->sweep[d];
+  const TrwsGraph::Sweep::Spec &sp = sub ? S.chunked.spec : S.spec, &s0 = P->graph->sweep[0].spec;
+  const int32_t geom[4] = {sp.c0, sp.c1, s0.seg_len, s0.nseg};
+  DevBuf<int32_t> &buf = P->d_run_rec[d][sub ? 1 : 0];
+  if (!buf.p || std::memcmp(geom, P->run_rec_geom[d][sub ? 1 : 0], sizeof(geom)) != 0) {
+    std::vector<int32_t> rec;
+    build_runner_records((sub ? S.chunked.desc : S.desc).data(), geom[0], geom[1], geom[2], geom[3], rec);
+    buf.upload(rec.data(), rec.size());
+    STEREO_HIP_CHECK(hipStreamSynchronize(nullptr));   // (`rec` goes away)
+    std::memcpy(P->run_rec_geom[d][sub ? 1 : 0], geom, sizeof(geom));
+  }
+  return buf.p;
+}
+
 }  // namespace stereo
 
 using namespace stereo;
@@ -192,6 +208,11 @@ static int plan_create_impl(int kernel, int K, int64_t N, int64_t E, const uint3
             P->d_sub_spec_run_ptr[d].upload(cs.run_ptr.data(), cs.run_ptr.size());
             P->d_sub_spec_run_order[d].upload(cs.run_order.data(), cs.run_order.size());
             P->d_sub_spec_kind[d].upload(cs.kind.data(), cs.kind.size());
+          }
+          // the K <= 64 runner's chain records, for either descriptor set it can be launched on
+          if (possible(fam, TrwsFamily::Pipe)) {
+            runner_records(P.get(), d, false);
+            if (P->sub_rows[d]) runner_records(P.get(), d, true);
           }
         }
         const size_t ml = (size_t)std::max(s0.max_len, s1.max_len);

@@ -6,8 +6,8 @@
 //               plain windowed min-plus (what message_regs returns whenever its certificate holds), the row for node i + 1
 //               stays in registers -- no certificate, no tangency keys, no barrier, ~100 instructions per visit;
 //   wave 1      labels of the primal pass: x_i from x_(i-1), exact (the same operations as the primal wave of a visit);
-//   waves 2-9   loaders: descriptor of node i, its foreign flags, unary + message rows, prefix sum in list order, into a
-//               ring of kRunSlots staged nodes in LDS (node i belongs to loader i mod 8);
+//   waves 2-9   loaders: host-made record of node i (trws_runner_records.h), its foreign flags, unary + message rows, prefix
+//               sum in list order, into a ring of kRunSlots staged nodes in LDS (node i belongs to loader i mod 8);
 //   wave 10     publisher: at every cut, the rows / label of the node in front go to p.spec_rows / p.spec_x, drained, then
 //               the segment's flag done[N + s].
 // Nothing here decides a result: the segments recompute every visit with the certified routine and compare what they
@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "trws_dev.h"
+#include "trws_runner_records.h"
 
 namespace stereo {
 namespace {
@@ -131,6 +132,7 @@ __device__ __forceinline__ DevParams uniform_params(const DevParams *pp) {
   U(K); U(lambda); U(unary); U(msg); U(pos); U(alpha); U(x); U(done); U(abort_flag); U(spin_ticks); U(n_own); U(N);
   U(desc[0]); U(desc[1]); U(window); U(uniform_step); U(spec_c0[0]); U(spec_c0[1]); U(spec_c1[0]); U(spec_c1[1]);
   U(spec_len); U(spec_nseg); U(spec_max_len); U(spec_rows); U(spec_x); U(spec_undo); U(spec_stat); U(timeline); U(tl_stride); U(debug);
+  U(run_rec[0]); U(run_rec[1]);
 #undef U
   return q;
 }
@@ -590,6 +592,20 @@ __device__ __attribute__((noinline)) void run_labels(const DevParams *pp) {
 }
 
 // ---- waves 2-9: staging ---------------------------------------------------------------------------------------------
+// A loader works from the node's host-made record (trws_runner_records.h): which rows to load in front of and behind
+// the foreign flags, where each goes in the ring slot, the staged words, gamma.  What is left to a turn is what depends
+// on the sweep: the loads, the two waits, the twin verdict, the labels, the stores and the tag.
+
+// r[s] for a uniform s: a tree of selects on the bits of s.  (The rows are eight named values, not an array: handed to
+// a routine by reference the array went to scratch memory, every load waited for and stored there.)
+__device__ __forceinline__ double run_pick4(int s, double r0, double r1, double r2, double r3) {
+  const bool b0 = s & 1, b1 = s & 2;
+  const double a0 = b0 ? r1 : r0, a1 = b0 ? r3 : r2;
+  return b1 ? a1 : a0;
+}
+__device__ __forceinline__ double run_pick8(int s, double r0, double r1, double r2, double r3, double r4, double r5, double r6, double r7) {
+  return (s & 4) ? run_pick4(s, r4, r5, r6, r7) : run_pick4(s, r0, r1, r2, r3);
+}
 template <bool BACKWARD, bool PRIMAL, bool UPDATE>
 __device__ __attribute__((noinline)) void run_loader(const DevParams *pp_, int epoch_, int lw_) {
   extern __shared__ __attribute__((aligned(16))) double run_lds[];
@@ -600,135 +616,111 @@ __device__ __attribute__((noinline)) void run_loader(const DevParams *pp_, int e
   const int lane = threadIdx.x & (kWave - 1);
   const int epoch = __builtin_amdgcn_readfirstlane(epoch_), lw = __builtin_amdgcn_readfirstlane(lw_);
   constexpr int D = BACKWARD ? 1 : 0;
-  const int c0 = p.spec_c0[D], c1 = p.spec_c1[D];
-  constexpr int DW = TrwsGraph::kDescWords;
-  const int32_t *desc = p.desc[D];
+  const int c0 = p.spec_c0[D], n = p.spec_c1[D] - c0;   // (positions count from the run's first: j = i - c0)
+  const int32_t *rec = p.run_rec[D] + lane;
   const int K = p.K;
   const int lk = lane < K ? lane : K - 1;
   int *rw = (int *)(rb + kRunWords);
-  const int L = p.spec_len, nseg = p.spec_nseg;
-  // (the descriptors of this wave's NEXT node are asked for before the current one is worked on)
-  int w2 = 0, wn2 = 0;
-  if (c0 + lw < c1) { w2 = desc[(size_t)(c0 + lw) * DW + lane]; wn2 = c0 + lw + 1 < c1 ? desc[(size_t)(c0 + lw + 1) * DW + lane] : 0; }
-  for (int i = c0 + lw; i < c1; i += kRunLoaders) {
-    const int w = w2, wn = wn2;
-    if (i + kRunLoaders < c1) {
-      w2 = desc[(size_t)(i + kRunLoaders) * DW + lane];
-      wn2 = i + kRunLoaders + 1 < c1 ? desc[(size_t)(i + kRunLoaders + 1) * DW + lane] : 0;
-    }
-    const int f = RLI(w, 2), fn = RLI(wn, 2);
-    const int nout = f & 15, nin = (f >> 4) & 15, ndep = (f >> 8) & 15, md = (f >> 16) & 255, ntot = nout + nin;
-    const int noutn = fn & 15, ntotn = noutn + ((fn >> 4) & 15);
-    const int j8 = lane & 7;
-    const int slw = __shfl(w, 12 + j8, kWave), sln = __shfl(wn, 12 + j8, kWave);
-    // rows the node in front hands over (this node's and, for the messages to compute here, the next node's)
-    const int fr = i > c0 ? (int)(__builtin_amdgcn_ballot_w64(lane < 8 && lane >= nout && lane < ntot && slw >= 0) & 255ull) : 0;
-    const int frn = i + 1 < c1 ? (int)(__builtin_amdgcn_ballot_w64(lane < 8 && lane >= noutn && lane < ntotn && sln >= 0) & 255ull) : 0;
-    const int kfirst = fr ? __builtin_ctz(fr) : ntot;
-    int s0 = -1, s1 = -1;   // slots, in this node's outgoing list, of the (up to two distinct) messages the next node takes from it
-    {
-      int rest = frn;
-      while (rest) {
-        const int k = __builtin_ctz(rest);
-        rest &= rest - 1;
-        const int s = __builtin_amdgcn_readlane(wn, 12 + k);
-        if (s0 < 0 || s0 == s) s0 = s; else s1 = s;
-      }
-    }
-    // the slots of the rows THIS node receives, in the numbering of the node in front (first distinct one: row "A0")
-    int p0s = -1;
-    if (fr) p0s = __builtin_amdgcn_readlane(w, 12 + kfirst);
-    int kinds = 0, nt = 0, nstaged = 0, stage_of[4] = {-1, -1, -1, -1};
-    for (int k = kfirst; k < ntot; ++k) {
-      int kd;
-      if ((fr >> k) & 1) kd = __builtin_amdgcn_readlane(w, 12 + k) == p0s ? 8 : 9;
-      else { kd = nstaged; if (nstaged < 4) stage_of[nstaged] = k; ++nstaged; }
-      kinds |= kd << (4 * nt);
-      ++nt;
-    }
-    // cut behind this node?
-    int cut = 0, pubkinds = 0;
-    if (i + 1 < c1 && (i + 1 - c0) % L == 0 && (i + 1 - c0) / L < nseg) {
-      cut = (i + 1 - c0) / L;
-      for (int k = noutn; k < ntotn; ++k)
-        if ((frn >> k) & 1) pubkinds |= (__builtin_amdgcn_readlane(wn, 12 + k) == s0 ? 8 : 9) << (4 * k);
-    }
+  const bool alane = (unsigned)(lane - kRecAlphaEdge) < 8u;   // the lanes that hold the edges of the node's weights
+  static_assert(kRunLoaders <= kRunSlots, "run_loader: a loader's first node has a ring slot of its own");
+  int slot_off = lw * kRunSlotDoubles;
+  // (the record of this wave's NEXT node is asked for before the current one is worked on)
+  int v2 = 0;
+  if (lw < n) v2 = rec[(size_t)lw * kRecWords];
+  for (int j = lw; j < n; j += kRunLoaders) {
+    const int v = v2;
+    if (j + kRunLoaders < n) v2 = rec[(size_t)(j + kRunLoaders) * kRecWords];
+    const int nout = RLI(v, kRecNout), ndep = RLI(v, kRecNdep);
     // the node's own data (nobody writes it before the segment that holds the node walks it)
-    const int fm = RLI(w, kDescFetch) & 255;
-    const double *ua = p.unary + (size_t)((unsigned long long)(unsigned)RLI(w, 0) * (unsigned long long)(unsigned)K) + lk;
-    const double theta = *ua;
-    const double av = p.alpha[__shfl(w, 4 + j8, kWave)];
-    double r[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      r[k] = 0;
-      if (k < nout) r[k] = *(p.msg + (size_t)((unsigned long long)(unsigned)RLI(w, 4 + k) * (unsigned long long)(unsigned)K) + lk);
-    }
+    const double theta = *(p.unary + (size_t)((unsigned long long)(unsigned)RLI(v, kRsNode) * (unsigned long long)(unsigned)K) + lk);
+    double ad = p.alpha[alane ? v : 0];   // lane 16 + d: the weight that goes to double d of the staged node
+    // (one uniform test per row that exists, then out)
+    double r0 = 0, r1 = 0, r2 = 0, r3 = 0, r4 = 0, r5 = 0, r6 = 0, r7 = 0;
+#define RUN_ROW(k) (p.msg + (size_t)((unsigned long long)(unsigned)RLI(v, kRecEdge + k) * (unsigned long long)(unsigned)K) + lk)
+    if (nout > 0) { r0 = *RUN_ROW(0);
+    if (nout > 1) { r1 = *RUN_ROW(1);
+    if (nout > 2) { r2 = *RUN_ROW(2);
+    if (nout > 3) { r3 = *RUN_ROW(3);
+    if (nout > 4) { r4 = *RUN_ROW(4);
+    if (nout > 5) { r5 = *RUN_ROW(5);
+    if (nout > 6) { r6 = *RUN_ROW(6);
+    if (nout > 7) { r7 = *RUN_ROW(7); } } } } } } } }
     // foreign dependencies (everything but the node in front), then their rows and labels
-    if (ndep > 0) wait_for_dependencies_w(p, ndep, __shfl(w, 20 + (lane & 3), kWave), RLI(w, 1), epoch, lane, abort_word);
+    if (ndep > 0) wait_for_dependencies_w(p, ndep, __shfl(v, kRecDep + (lane & 3), kWave), RLI(v, kRecRank), epoch, lane, abort_word);
     if (lds_load(abort_word)) return;
-    int src = -1;   // lane k < nin: the label the k-th incoming row's pairwise term takes (-1: the node in front)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (k >= nout && k < ntot && ((fm >> k) & 1) && !((fr >> k) & 1)) {
-        if (UPDATE) r[k] = ld_sc1(p.msg + (size_t)((unsigned long long)(unsigned)RLI(w, 4 + k) * (unsigned long long)(unsigned)K) + lk);
-        if (PRIMAL) { const int xv = ld_sc1(p.x + RLI(w, 32 + k)); if (lane == k - nout) src = xv; }
+    int word = v;   // lanes 0-14: the staged words; 9-12 take the labels found behind the flags, 2 the twin verdict
+    const int fetch = RLI(v, kRecFetch);
+    if (fetch) {
+      const int labels = RLI(v, kRecLabels), lane0 = kRsSrc - nout;
+#define RUN_FETCH(k) \
+      if ((fetch >> k) & 1) { \
+        if (UPDATE) r##k = ld_sc1(RUN_ROW(k)); \
+        if (PRIMAL && ((labels >> k) & 1)) { const int xv = ld_sc1(p.x + RLI(v, kRecOther + k)); word = lane == lane0 + k ? xv : word; } \
       }
+      RUN_FETCH(0) RUN_FETCH(1) RUN_FETCH(2) RUN_FETCH(3) RUN_FETCH(4) RUN_FETCH(5) RUN_FETCH(6) RUN_FETCH(7)
+#undef RUN_FETCH
     }
+#undef RUN_ROW
     // the ring slot: both recurrences have taken the node that had it into their registers
-    double *sl = rb + ((i - c0) % kRunSlots) * kRunSlotDoubles;
-    if (UPDATE && !run_wait_i<true>(rw + kRwConsM, i - c0 - kRunSlots + 1, abort_word, p.abort_flag, p.spin_ticks)) return;
-    if (PRIMAL && !run_wait_i<true>(rw + kSwConsP, i - c0 - kRunSlots + 1, abort_word, p.abort_flag, p.spin_ticks)) return;
+    double *sl = rb + slot_off;
+    slot_off += kRunLoaders * kRunSlotDoubles;
+    if (slot_off >= kRunSlots * kRunSlotDoubles) slot_off -= kRunSlots * kRunSlotDoubles;
+    if (UPDATE && !run_wait_i<true>(rw + kRwConsM, j - kRunSlots + 1, abort_word, p.abort_flag, p.spin_ticks)) return;
+    if (PRIMAL && !run_wait_i<true>(rw + kSwConsP, j - kRunSlots + 1, abort_word, p.abort_flag, p.spin_ticks)) return;
+    int nmsg = RLI(v, kRsNmsg);
     if (UPDATE) {
+      // P = ((theta + r0) + r1) + ... over exactly the first kfirst rows, in list order
       double P = theta;
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (k < kfirst) P += r[k];
+      const int kfirst = RLI(v, kRecKfirst);
+      if (kfirst > 0) { P += r0;
+      if (kfirst > 1) { P += r1;
+      if (kfirst > 2) { P += r2;
+      if (kfirst > 3) { P += r3;
+      if (kfirst > 4) { P += r4;
+      if (kfirst > 5) { P += r5;
+      if (kfirst > 6) { P += r6;
+      if (kfirst > 7) { P += r7; } } } } } } } }
       sl[kRunRowP + lane] = P;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        if (stage_of[0] == k) sl[kRunRowS + lane] = r[k];
-        if (stage_of[1] == k) sl[kRunRowS + 64 + lane] = r[k];
-        if (stage_of[2] == k) sl[kRunRowS + 128 + lane] = r[k];
+      const int st0 = RLI(v, kRecStage);
+      if (st0 >= 0) {   // (staged rows are numbered in list order: no second without a first)
+        sl[kRunRowS + lane] = run_pick8(st0, r0, r1, r2, r3, r4, r5, r6, r7);
+        const int st1 = RLI(v, kRecStage + 1);
+        if (st1 >= 0) {
+          sl[kRunRowS + 64 + lane] = run_pick8(st1, r0, r1, r2, r3, r4, r5, r6, r7);
+          const int st2 = RLI(v, kRecStage + 2);
+          if (st2 >= 0) sl[kRunRowS + 128 + lane] = run_pick8(st2, r0, r1, r2, r3, r4, r5, r6, r7);
+        }
       }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {   // (lanes beyond K: -inf, which makes the recurrence's H = gamma Di - m = +inf there without a select)
-        if (s0 == k) sl[kRunRowM + lane] = lane < K ? r[k] : -__builtin_huge_val();
-        if (s1 == k) sl[kRunRowM + 64 + lane] = lane < K ? r[k] : -__builtin_huge_val();
+      // the old rows of the messages to the next node (lanes beyond K: -inf, which makes the recurrence's
+      // H = gamma Di - m = +inf there without a select); the two are ONE message if weights and old rows agree
+      // (positions are shared)
+      const int m0k = RLI(v, kRecMsg), m1k = RLI(v, kRecMsg + 1), twin = RLI(v, kRecTwin);
+      double m0 = 0, m1 = 0;
+      if (m0k >= 0) { m0 = run_pick4(m0k, r0, r1, r2, r3); sl[kRunRowM + lane] = lane < K ? m0 : -__builtin_huge_val(); }
+      if (m1k >= 0) { m1 = run_pick4(m1k, r0, r1, r2, r3); sl[kRunRowM + 64 + lane] = lane < K ? m1 : -__builtin_huge_val(); }
+      if (twin) {
+        bool same = RLI(__double2hiint(ad), kRecAlphaEdge) == RLI(__double2hiint(ad), kRecAlphaEdge + 1) &&
+                    RLI(__double2loint(ad), kRecAlphaEdge) == RLI(__double2loint(ad), kRecAlphaEdge + 1);
+        if (twin == 2) same = same && !UNI(lane < K && __double_as_longlong(m0) != __double_as_longlong(m1));
+        nmsg = same ? 1 : 2;
       }
     }
     if (PRIMAL) {
       sl[kRunRowTH + lane] = theta;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (k < nout) sl[kRunRowOUT + k * 64 + lane] = r[k];
+      if (nout > 0) { sl[kRunRowOUT + lane] = r0;
+      if (nout > 1) { sl[kRunRowOUT + 64 + lane] = r1;
+      if (nout > 2) { sl[kRunRowOUT + 128 + lane] = r2;
+      if (nout > 3) { sl[kRunRowOUT + 192 + lane] = r3; } } } }
     }
-    // the two messages to the next node are ONE message if weights and old rows agree (positions are shared)
-    int nmsg = s0 < 0 ? 0 : 1;
-    if (UPDATE && s1 >= 0) {
-      bool same = RLI(__double2hiint(av), s0) == RLI(__double2hiint(av), s1) && RLI(__double2loint(av), s0) == RLI(__double2loint(av), s1);
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-          if (a != b && s0 == a && s1 == b) same = same && !UNI(lane < K && __double_as_longlong(r[a]) != __double_as_longlong(r[b]));
-      nmsg = same ? 1 : 2;
-    }
-    {
-      int word = 0;
-      word = lane == kRsNt ? nt : lane == kRsKinds ? (kinds | (nt << 16)) : lane == kRsNmsg ? nmsg : lane == kRsCut ? cut
-           : lane == kRsPubKinds ? pubkinds : lane == kRsNout ? nout : lane == kRsNin ? nin : lane == kRsMd ? (md >> nout) : lane == kRsNode ? RLI(w, 0) : 0;
-      const int srck = __shfl(src, lane - kRsSrc, kWave);
-      if (lane >= kRsSrc && lane < kRsSrc + 4) word = srck;
-      if (lane < kRsTag) ((int *)(sl + kRunSc))[lane] = word;
-      // doubles 8-15: alpha of the two messages, gamma (MRFEnergy.cpp:207-228), alpha of the incoming rows
-      const double a0 = readlane_f64(av, s0 < 0 ? 0 : s0), a1 = readlane_f64(av, s1 < 0 ? (s0 < 0 ? 0 : s0) : s1);
-      const double ain = __shfl(av, nout + (lane - 3 < 0 ? 0 : lane - 3), kWave);
-      const double g = (double)1 / (double)(nout > nin ? nout : nin > 0 ? nin : 1);
-      if (lane < 8) sl[kRunSc + 8 + lane] = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? g : ain;
-    }
+    word = lane == kRsNmsg ? nmsg : word;
+    if (lane < kRsTag) ((int *)(sl + kRunSc))[lane] = word;
+    // doubles 8-15: alpha of the two messages, gamma (MRFEnergy.cpp:207-228; its bits come with the record), alpha of
+    // the incoming rows
+    const double g = __hiloint2double(RLI(v, kRecGamma + 1), RLI(v, kRecGamma));
+    ad = lane == kRecAlphaEdge + 2 ? g : ad;
+    if (alane) sl[kRunSc + 8 - kRecAlphaEdge + lane] = ad;
     SPEC_RELEASE();
-    if (lane == 0) lds_store((int *)(sl + kRunSc) + kRsTag, i + 1);
+    if (lane == 0) lds_store((int *)(sl + kRunSc) + kRsTag, c0 + j + 1);
   }
 }
 
