@@ -5,6 +5,10 @@ label k at pixel i means disparity ``base_i + offsets_k``: ``unary`` (K x N) fro
 sampler, ``q`` / ``qprim`` (K x E) as stereo_trws_positions gives them for the planes ``[0 0 1 -(base + offsets_k)]``.
 ``refine_band`` builds these on the device, solves them level by level and applies the labels.
 
+This module is also the one home of what the four level builders (band, plane_band, candidates, plane_candidates)
+share: the host-array helpers, the helpers of the device wrappers (``_out`` ... ``_raise_bad``), the per-level result
+lists (``LevelsResult``) and the level loop (``run_levels``) with the protocol a problem class offers it.
+
 Host forms take NumPy arrays in MATLAB shapes (volume H x W x D for layout 0, D x N for layout 1; conn 2 x E zero
 based).  Device forms take torch tensors of the current device: a map is a contiguous (W, H) tensor (the column-major
 storage of H x W, as lr_check_device takes it), the volume, ``unary``, ``q`` and ``qprim`` are flat float64 tensors in
@@ -120,6 +124,61 @@ def to_device_vector(v):
     return torch.from_numpy(np.array(v, dtype=np.float64)).cuda()
 
 
+def _vp(t):
+    """A tensor's address as the C entries take it: NULL for no tensor and for an empty one."""
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def _out(t, what, n, dev, new=None):
+    """An output of a device wrapper: `t` validated (n float64 elements), or a new tensor on `dev` (of shape `new`
+    where that is not n)."""
+    import torch
+    return torch.empty(n if new is None else new, dtype=torch.float64, device=dev) if t is None else _flat(t, what, torch.float64, n)
+
+
+def _bad(bad, dev):
+    """The int32 counter a kernel adds its offending pixels to."""
+    import torch
+    return torch.zeros(1, dtype=torch.int32, device=dev) if bad is None else _flat(bad, "bad", torch.int32, 1)
+
+
+def _edges(conn):
+    """A flat int32 tensor of 2 E entries -> (conn, E)."""
+    import torch
+    conn = _flat(conn, "conn", torch.int32)
+    if conn.numel() % 2:
+        raise StereoHipError("conn must hold 2 E entries")
+    return conn, conn.numel() // 2
+
+
+def _device_vectors(stream, *vectors):
+    """Short host vectors (float64 or int32) on the device.  Each of `vectors` is (host array, its device copy or None,
+    the copy's name): a copy given is validated, one that is missing is made here.  If one was made and `stream` is
+    given, torch's current stream is synchronized once: the copies ran on it, the kernels will not."""
+    import torch
+    made_here = any(d is None for _, d, _ in vectors)
+    out = [torch.from_numpy(np.array(v).reshape(-1)).cuda() if d is None
+           else _flat(d, what, torch.float64 if v.dtype == np.float64 else torch.int32, v.size) for v, d, what in vectors]
+    if made_here and stream is not None:
+        torch.cuda.current_stream().synchronize()
+    return out
+
+
+def _raise_bad(bad, check, message, *more):
+    """check=True: reads the counter back (this waits for the stream) and raises `message % (count, *more)` if it is
+    not zero."""
+    if check:
+        n = int(bad.item())
+        if n:
+            raise StereoHipError(message % ((n,) + more))
+
+
+def _device_labels(labels):
+    """plan.result()'s labels as the flat int32 tensor the apply entries read."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)).cuda()
+
+
 def band_inputs_device(ncc, disparities, unary_weight, base, offsets, conn, layout=0, unary=None, q=None, qprim=None,
                        bad=None, stream=None, d_disparities=None, d_offsets=None, check=True):
     """stereo_band_inputs_device on torch tensors (module docstring), launched on `stream` (a torch stream or a raw
@@ -133,31 +192,18 @@ def band_inputs_device(ncc, disparities, unary_weight, base, offsets, conn, layo
     disparities, offsets = _vec(disparities, "disparities"), _vec(offsets, "offsets")
     D, K, N = disparities.shape[0], offsets.shape[0], H * W
     ncc = _flat(ncc, "ncc", torch.float64, N * D)
-    conn = _flat(conn, "conn", torch.int32)
-    if conn.numel() % 2:
-        raise StereoHipError("conn must hold 2 E entries")
-    E = conn.numel() // 2
+    conn, E = _edges(conn)
     dev = base.device
-    made_here = d_disparities is None or d_offsets is None
-    d_disparities = to_device_vector(disparities) if d_disparities is None else _flat(d_disparities, "d_disparities", torch.float64, D)
-    d_offsets = to_device_vector(offsets) if d_offsets is None else _flat(d_offsets, "d_offsets", torch.float64, K)
-    if made_here and stream is not None:
-        torch.cuda.current_stream().synchronize()     # the copies ran on torch's current stream, the kernels will not
-    unary = torch.empty(max(K, 0) * N, dtype=torch.float64, device=dev) if unary is None else _flat(unary, "unary", torch.float64, K * N)
-    q = torch.empty(max(K, 0) * E, dtype=torch.float64, device=dev) if q is None else _flat(q, "q", torch.float64, K * E)
-    qprim = torch.empty(max(K, 0) * E, dtype=torch.float64, device=dev) if qprim is None else _flat(qprim, "qprim", torch.float64, K * E)
-    bad = torch.zeros(1, dtype=torch.int32, device=dev) if bad is None else _flat(bad, "bad", torch.int32, 1)
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    d_disparities, d_offsets = _device_vectors(stream, (disparities, d_disparities, "d_disparities"), (offsets, d_offsets, "d_offsets"))
+    unary, q, qprim = _out(unary, "unary", K * N, dev), _out(q, "q", K * E, dev), _out(qprim, "qprim", K * E, dev)
+    bad = _bad(bad, dev)
     err = _lib.errbuf()
-    rc = _lib.lib().stereo_band_inputs_device(vp(ncc), C.c_int(H), C.c_int(W), C.c_int(D), C.c_int(int(layout)), _p(disparities),
-                                              vp(d_disparities), C.c_double(float(unary_weight)), vp(base), _p(offsets),
-                                              vp(d_offsets), C.c_int(K), C.c_int64(E), vp(conn), vp(unary), vp(q), vp(qprim),
-                                              vp(bad), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    rc = _lib.lib().stereo_band_inputs_device(_vp(ncc), C.c_int(H), C.c_int(W), C.c_int(D), C.c_int(int(layout)), _p(disparities),
+                                              _vp(d_disparities), C.c_double(float(unary_weight)), _vp(base), _p(offsets),
+                                              _vp(d_offsets), C.c_int(K), C.c_int64(E), _vp(conn), _vp(unary), _vp(q), _vp(qprim),
+                                              _vp(bad), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
     _lib.check(rc, err)
-    if check:
-        n = int(bad.item())
-        if n:
-            raise StereoHipError("band_inputs_device: base is not finite at %d pixel(s)" % n)
+    _raise_bad(bad, check, "band_inputs_device: base is not finite at %d pixel(s)")
     return unary, q, qprim, bad
 
 
@@ -170,24 +216,15 @@ def band_apply_device(base, labels, offsets, refined=None, bad=None, stream=None
     offsets = _vec(offsets, "offsets")
     K = offsets.shape[0]
     labels = _flat(labels, "labels", torch.int32, H * W)
-    if d_offsets is None:
-        d_offsets = to_device_vector(offsets)
-        if stream is not None:
-            torch.cuda.current_stream().synchronize()
-    else:
-        d_offsets = _flat(d_offsets, "d_offsets", torch.float64, K)
+    d_offsets, = _device_vectors(stream, (offsets, d_offsets, "d_offsets"))
     refined = torch.empty((W, H), dtype=torch.float64, device=base.device) if refined is None else _device_map(refined, "refined", np.float64, base.shape)
-    bad = torch.zeros(1, dtype=torch.int32, device=base.device) if bad is None else _flat(bad, "bad", torch.int32, 1)
-    vp = lambda t: C.c_void_p(t.data_ptr())
+    bad = _bad(bad, base.device)
     err = _lib.errbuf()
-    rc = _lib.lib().stereo_band_apply_device(vp(base), C.c_int(H), C.c_int(W), vp(labels), _p(offsets), vp(d_offsets),
-                                             C.c_int(K), vp(refined), vp(bad), C.c_void_p(_stream(stream)), err,
+    rc = _lib.lib().stereo_band_apply_device(_vp(base), C.c_int(H), C.c_int(W), _vp(labels), _p(offsets), _vp(d_offsets),
+                                             C.c_int(K), _vp(refined), _vp(bad), C.c_void_p(_stream(stream)), err,
                                              C.c_size_t(len(err)))
     _lib.check(rc, err)
-    if check:
-        n = int(bad.item())
-        if n:
-            raise StereoHipError("band_apply_device: %d label(s) outside 1 .. %d" % (n, K))
+    _raise_bad(bad, check, "band_apply_device: %d label(s) outside 1 .. %d", K)
     return refined, bad
 
 
@@ -201,20 +238,73 @@ def check_levels(levels):
     return levels
 
 
-class BandResult:
-    """refine_band's result: `dispmap` (H x W, the last level's refined map), `maps` (one per level) and per level
-    `energy`, `lower_bound`, `iterations`, `labels` (N, one based), `paths` (the kernel family that ran,
-    TrwsPlan.path()) and `carried` (the level started from the previous level's messages)."""
+class LevelsResult:
+    """What every refine_* keeps per level: `maps` (what apply() returned), `energy`, `lower_bound`, `iterations`,
+    `labels` (N, one based), `paths` (the kernel family that ran, TrwsPlan.path()) and `carried` (the level started from
+    the previous level's messages)."""
 
     def __init__(self):
-        self.dispmap = self.stage = None
         self.maps, self.labels = [], []
         self.energy, self.lower_bound, self.iterations, self.paths, self.carried = [], [], [], [], []
 
 
+class BandResult(LevelsResult):
+    """refine_band's result: LevelsResult's lists, `dispmap` (H x W, the last level's refined map) and `stage` (with
+    carry: the carry.Stage the last level leaves)."""
+
+    def __init__(self):
+        super().__init__()
+        self.dispmap = self.stage = None
+
+
+def run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, carry=False, start=None):
+    """The level loop of refine_band, refine_plane_band, refine_candidates and refine_plane_candidates.  For each of the
+    checked `levels`: a TrwsPlan(kernel, K, N, conn) -- one per distinct K, made here and closed here -- is bound to the
+    level's inputs, iterated up to `maxiter` times (`max_relgap` as in trws) and read, `out`'s (LevelsResult) lists
+    grow by one entry, and the labels are applied.  carry=True: a level starts from what the one before it left;
+    start: the carry.Carry the first level starts from.  -> what the last level left (None without carry).
+
+    The protocol of `prob` (BandProblem, PlaneBandProblem and the two candidate problems derived from them):
+    N, conn; labels_of(level) -> K, before the level is built; build(level, plan, tol, carry=) binds the level's inputs
+    to `plan`, which starts from the carry.Carry `carry` if that is not None; leave(plan, labels) -> what the solved
+    level leaves for the next one, taken before apply() (a plan is reused for equal K and the next bind wipes it);
+    apply(labels) moves the problem on and returns the new map for the host; carry_from(left) -> the Carry into the
+    next build from what leave() gave, taken after apply() (None for None)."""
+    plans, previous, left = {}, start, None
+    try:
+        for level in levels:
+            K = prob.labels_of(level)
+            if K not in plans:
+                plans[K] = TrwsPlan(int(kernel), K, prob.N, prob.conn)
+            plan = plans[K]
+            prob.build(level, plan, tol, carry=previous)
+            out.carried.append(previous is not None)
+            plan.iterate(maxiter, max_relgap)
+            labels, en, lb, it = plan.result()
+            out.paths.append(plan.path())
+            out.labels.append(labels); out.energy.append(en); out.lower_bound.append(lb); out.iterations.append(it)
+            left = prob.leave(plan, labels) if carry else None
+            out.maps.append(prob.apply(labels))
+            previous = prob.carry_from(left)
+    finally:
+        for plan in plans.values():
+            plan.close()
+    return left
+
+
+def bind_inputs(prob, plan, tol):
+    """The inputs a build() has just made (prob.d_unary, d_q, d_qprim; torch's current stream has to finish them first)
+    bound to `plan` with the problem's smoothness weights."""
+    import torch
+    torch.cuda.current_stream().synchronize()
+    plan.bind_device(prob.d_unary.data_ptr(), prob.d_alphas.data_ptr(), tol, d_q=prob.d_q.data_ptr(),
+                     d_qprim=prob.d_qprim.data_ptr(), keepalive=[prob.d_unary, prob.d_q, prob.d_qprim, prob.d_alphas])
+
+
 class BandProblem:
     """One view's band problems on the device: the volume, the connectivity and the smoothness weights go up once;
-    build() makes a level's inputs from the current base and binds them to `plan`, apply() moves the base on."""
+    build() makes a level's inputs from the current base and binds them to `plan`, apply() moves the base on.  (The
+    protocol the level loops drive it by: run_levels.)"""
 
     def __init__(self, ncc, disparities, unary_weight, base, conn, alphas=None, layout=0):
         import torch
@@ -270,10 +360,7 @@ class BandProblem:
             d_disparities=self.d_disparities, d_offsets=self.d_offsets)
         if zero_columns is not None:
             self.d_unary.view(self.N, -1)[zero_columns] = 0.0
-        import torch
-        torch.cuda.current_stream().synchronize()
-        plan.bind_device(self.d_unary.data_ptr(), self.d_alphas.data_ptr(), tol, d_q=self.d_q.data_ptr(),
-                         d_qprim=self.d_qprim.data_ptr(), keepalive=[self.d_unary, self.d_q, self.d_qprim, self.d_alphas])
+        bind_inputs(self, plan, tol)
         if carry is not None:
             carry_mod.load_carried(plan, carry, self.offsets, self.receiver(), self.N, self.d_offsets)
 
@@ -286,6 +373,10 @@ class BandProblem:
             return None
         return carry_mod.Stage(d_m, self.offsets, self.d_built_base.reshape(-1), self.conn, self.receiver_host(), (self.H, self.W))
 
+    def leave(self, plan, labels=None):
+        """What the solved level leaves for the next one: its stage()."""
+        return self.stage(plan)
+
     def carry_from(self, stage, scales=False):
         """The carry.Carry from `stage` into the next level around the current base (None without a stage).  The shift
         is taken on the device from the two bases, so a base filled or otherwise edited in between is handled as well.
@@ -294,9 +385,7 @@ class BandProblem:
 
     def apply(self, labels):
         """The base moved by the labels of the level built last -> the new base on the host, H x W."""
-        import torch
-        lab = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)).cuda()
-        self.d_base, _ = band_apply_device(self.d_base, lab, self.offsets, d_offsets=self.d_offsets)
+        self.d_base, _ = band_apply_device(self.d_base, _device_labels(labels), self.offsets, d_offsets=self.d_offsets)
         return self.d_base.cpu().numpy().T
 
 
@@ -316,25 +405,7 @@ def refine_band(ncc, disparities, unary_weight, base, kernel, tol, levels, maxit
     conn = T.construct_neighborhood(H, W) if conn is None else conn
     prob = BandProblem(ncc, disparities, unary_weight, base, conn, alphas, layout)
     out = BandResult()
-    plans = {}
-    previous = prob.carry_from(carry_start[0], carry_start[1]) if carry_start is not None else None
-    try:
-        for offsets in levels:
-            K = offsets.shape[0]
-            if K not in plans:
-                plans[K] = TrwsPlan(int(kernel), K, prob.N, prob.conn)
-            plan = plans[K]
-            prob.build(offsets, plan, tol, carry=previous)
-            out.carried.append(previous is not None)
-            plan.iterate(maxiter, max_relgap)
-            labels, en, lb, it = plan.result()
-            out.paths.append(plan.path())
-            out.labels.append(labels); out.energy.append(en); out.lower_bound.append(lb); out.iterations.append(it)
-            out.maps.append(prob.apply(labels))
-            out.stage = prob.stage(plan) if carry else None
-            previous = prob.carry_from(out.stage)
-        out.dispmap = out.maps[-1]
-    finally:
-        for plan in plans.values():
-            plan.close()
+    start = prob.carry_from(carry_start[0], carry_start[1]) if carry_start is not None else None
+    out.stage = run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, carry, start)
+    out.dispmap = out.maps[-1]
     return out

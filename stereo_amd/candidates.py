@@ -11,6 +11,8 @@ the device, solves them level by level and applies the labels.
 
 Host forms take NumPy arrays in MATLAB shapes, device forms torch tensors of the current device, as in band.py: a map is
 a contiguous (W, H) tensor, a table a flat float64 tensor of K*N elements, M sources one contiguous (M, W, H) tensor.
+The helpers of the wrappers and the level loop are band.py's; the checks of a candidate level (check_level,
+check_levels, labels_of) are here for plane_candidates.py as well.
 """
 import ctypes as C
 
@@ -20,9 +22,9 @@ from . import _lib
 from . import band
 from . import terms as T
 from ._lib import StereoHipError
-from .band import _conn, _flat, _labels, _vec, _volume, to_device_vector
+from .band import (_bad, _conn, _device_labels, _device_vectors, _edges, _flat, _labels, _out, _raise_bad, _vec, _volume, _vp,
+                   bind_inputs, run_levels, to_device_vector)
 from .consistency import _device_map, _map, _p, _stream
-from .trws import TrwsPlan
 
 SOURCE_NAMES = ("base", "wta")
 
@@ -119,6 +121,13 @@ def taps_to_device(taps):
     return torch.from_numpy(np.array(_taps(taps).reshape(-1), dtype=np.int32)).cuda()
 
 
+def _device_vectors_of_gather(stream, offsets, d_offsets, taps, d_taps, taken):
+    """band._device_vectors for a gather: the offsets always, the taps only where a source is read (`taken`)."""
+    if not taken:
+        return _device_vectors(stream, (offsets, d_offsets, "d_offsets"))[0], d_taps
+    return _device_vectors(stream, (offsets, d_offsets, "d_offsets"), (taps, d_taps, "d_taps"))
+
+
 def gather_device(base, offsets, sources=None, taps=(), cand=None, bad=None, stream=None, d_offsets=None, d_taps=None,
                   check=True):
     """stereo_candidates_gather_device: `base` a (W, H) float64 map tensor, `sources` None or a contiguous (M, W, H)
@@ -138,26 +147,16 @@ def gather_device(base, offsets, sources=None, taps=(), cand=None, bad=None, str
         sources = _flat(sources, "sources", torch.float64, M * N)
     K = Ko + M * Tn
     dev = base.device
-    made_here = d_offsets is None or (d_taps is None and M * Tn)
-    d_offsets = to_device_vector(offsets) if d_offsets is None else _flat(d_offsets, "d_offsets", torch.float64, Ko)
-    if M * Tn:
-        d_taps = taps_to_device(taps) if d_taps is None else _flat(d_taps, "d_taps", torch.int32, 2 * Tn)
-    if made_here and stream is not None:
-        torch.cuda.current_stream().synchronize()     # the copies ran on torch's current stream, the kernel will not
-    cand = torch.empty(max(K, 1) * N, dtype=torch.float64, device=dev) if cand is None else _flat(cand, "cand", torch.float64, K * N)
-    bad = torch.zeros(1, dtype=torch.int32, device=dev) if bad is None else _flat(bad, "bad", torch.int32, 1)
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    d_offsets, d_taps = _device_vectors_of_gather(stream, offsets, d_offsets, taps, d_taps, M * Tn)
+    cand, bad = _out(cand, "cand", K * N, dev, new=max(K, 1) * N), _bad(bad, dev)
     err = _lib.errbuf()
-    rc = _lib.lib().stereo_candidates_gather_device(vp(base), C.c_int(H), C.c_int(W), _p(offsets), vp(d_offsets), C.c_int(Ko),
-                                                    vp(sources) if M * Tn else None, C.c_int(M),
-                                                    _p(taps, C.c_int32) if M * Tn else None, vp(d_taps) if M * Tn else None,
-                                                    C.c_int(Tn), vp(cand), vp(bad), C.c_void_p(_stream(stream)), err,
+    rc = _lib.lib().stereo_candidates_gather_device(_vp(base), C.c_int(H), C.c_int(W), _p(offsets), _vp(d_offsets), C.c_int(Ko),
+                                                    _vp(sources) if M * Tn else None, C.c_int(M),
+                                                    _p(taps, C.c_int32) if M * Tn else None, _vp(d_taps) if M * Tn else None,
+                                                    C.c_int(Tn), _vp(cand), _vp(bad), C.c_void_p(_stream(stream)), err,
                                                     C.c_size_t(len(err)))
     _lib.check(rc, err)
-    if check:
-        n = int(bad.item())
-        if n:
-            raise StereoHipError("gather_device: the base or a source is not finite at %d pixel(s)" % n)
+    _raise_bad(bad, check, "gather_device: the base or a source is not finite at %d pixel(s)")
     return cand, bad
 
 
@@ -176,32 +175,18 @@ def candidates_inputs_device(ncc, disparities, unary_weight, cand, shape, conn, 
         raise StereoHipError("cand must hold K * H * W elements")
     K = cand.numel() // N
     ncc = _flat(ncc, "ncc", torch.float64, N * D)
-    conn = _flat(conn, "conn", torch.int32)
-    if conn.numel() % 2:
-        raise StereoHipError("conn must hold 2 E entries")
-    E = conn.numel() // 2
+    conn, E = _edges(conn)
     dev = cand.device
-    if d_disparities is None:
-        d_disparities = to_device_vector(disparities)
-        if stream is not None:
-            torch.cuda.current_stream().synchronize()
-    else:
-        d_disparities = _flat(d_disparities, "d_disparities", torch.float64, D)
-    unary = torch.empty(K * N, dtype=torch.float64, device=dev) if unary is None else _flat(unary, "unary", torch.float64, K * N)
-    q = torch.empty(K * E, dtype=torch.float64, device=dev) if q is None else _flat(q, "q", torch.float64, K * E)
-    qprim = torch.empty(K * E, dtype=torch.float64, device=dev) if qprim is None else _flat(qprim, "qprim", torch.float64, K * E)
-    bad = torch.zeros(1, dtype=torch.int32, device=dev) if bad is None else _flat(bad, "bad", torch.int32, 1)
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    d_disparities, = _device_vectors(stream, (disparities, d_disparities, "d_disparities"))
+    unary, q, qprim = _out(unary, "unary", K * N, dev), _out(q, "q", K * E, dev), _out(qprim, "qprim", K * E, dev)
+    bad = _bad(bad, dev)
     err = _lib.errbuf()
-    rc = _lib.lib().stereo_candidates_inputs_device(vp(ncc), C.c_int(H), C.c_int(W), C.c_int(D), C.c_int(int(layout)),
-                                                    _p(disparities), vp(d_disparities), C.c_double(float(unary_weight)), vp(cand),
-                                                    C.c_int(K), C.c_int64(E), vp(conn), vp(unary), vp(q), vp(qprim), vp(bad),
+    rc = _lib.lib().stereo_candidates_inputs_device(_vp(ncc), C.c_int(H), C.c_int(W), C.c_int(D), C.c_int(int(layout)),
+                                                    _p(disparities), _vp(d_disparities), C.c_double(float(unary_weight)), _vp(cand),
+                                                    C.c_int(K), C.c_int64(E), _vp(conn), _vp(unary), _vp(q), _vp(qprim), _vp(bad),
                                                     C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
     _lib.check(rc, err)
-    if check:
-        n = int(bad.item())
-        if n:
-            raise StereoHipError("candidates_inputs_device: a candidate is not finite at %d pixel(s)" % n)
+    _raise_bad(bad, check, "candidates_inputs_device: a candidate is not finite at %d pixel(s)")
     return unary, q, qprim, bad
 
 
@@ -217,73 +202,76 @@ def candidates_apply_device(cand, labels, shape, out=None, bad=None, stream=None
     K = cand.numel() // N
     labels = _flat(labels, "labels", torch.int32, N)
     out = torch.empty((W, H), dtype=torch.float64, device=cand.device) if out is None else _device_map(out, "out", np.float64, (W, H))
-    bad = torch.zeros(1, dtype=torch.int32, device=cand.device) if bad is None else _flat(bad, "bad", torch.int32, 1)
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+    bad = _bad(bad, cand.device)
     err = _lib.errbuf()
-    rc = _lib.lib().stereo_candidates_apply_device(vp(cand), C.c_int(H), C.c_int(W), C.c_int(K), vp(labels), vp(out), vp(bad),
+    rc = _lib.lib().stereo_candidates_apply_device(_vp(cand), C.c_int(H), C.c_int(W), C.c_int(K), _vp(labels), _vp(out), _vp(bad),
                                                    C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
     _lib.check(rc, err)
-    if check:
-        n = int(bad.item())
-        if n:
-            raise StereoHipError("candidates_apply_device: %d label(s) outside 1 .. %d" % (n, K))
+    _raise_bad(bad, check, "candidates_apply_device: %d label(s) outside 1 .. %d", K)
     return out, bad
 
 
 # ---------------------------------------------------------------- levels
 
-def check_level(level):
+def _check_source(s):
+    if isinstance(s, str):
+        if s not in SOURCE_NAMES:
+            raise StereoHipError("candidates: a source is 'base', 'wta' or an H x W map (got %r)" % (s,))
+    elif np.ndim(s) != 2:
+        raise StereoHipError("candidates: a source is 'base', 'wta' or an H x W map")
+
+
+def check_level(level, check_source=_check_source, prefix="candidates", single=(str, np.ndarray)):
     """A candidate level as dict(offsets: float64 vector, taps: T x 2 int32, sources: list of 'base' / 'wta' / H x W
     maps), checked as far as it can be without the image: the band's rules for the offsets, whole-number taps below
-    2^15, K = Ko + M T within 1 .. max_offsets()."""
+    2^15, K = Ko + M T within 1 .. max_offsets().  plane_candidates.py checks its levels here too: check_source refuses
+    what is not a source, prefix ("candidates" / "plane candidates") starts the messages, single: the types of one
+    source given without a list."""
     if not isinstance(level, dict) or set(level) - {"offsets", "taps", "sources"}:
-        raise StereoHipError("a candidate level must be dict(offsets=, taps=, sources=) (got %r)" % (level,))
+        raise StereoHipError("a %s level must be dict(offsets=, taps=, sources=) (got %r)" % (prefix[:-1].replace(" ", "-"), level))
     offsets = _vec(level.get("offsets", [0.0]), "a level's offsets")
     if offsets.shape[0] < 1 or not (np.isfinite(offsets).all() and (np.diff(offsets) > 0).all() and (offsets == 0.0).any()):
-        raise StereoHipError("candidates: a vector of offsets must be finite, strictly ascending and contain 0 (got %s)"
-                             % (offsets.tolist(),))
+        raise StereoHipError("%s: a vector of offsets must be finite, strictly ascending and contain 0 (got %s)"
+                             % (prefix, offsets.tolist()))
     taps = _taps(level.get("taps", ()))
     if taps.size and np.abs(taps).max() >= 1 << 15:
-        raise StereoHipError("candidates: a tap's |dy| and |dx| must be below 2^15")
+        raise StereoHipError("%s: a tap's |dy| and |dx| must be below 2^15" % prefix)
     sources = level.get("sources", ())
-    if isinstance(sources, (str, np.ndarray)):
-        sources = [sources]
-    sources = list(sources)
+    sources = [sources] if isinstance(sources, single) else list(sources)
     for s in sources:
-        if isinstance(s, str):
-            if s not in SOURCE_NAMES:
-                raise StereoHipError("candidates: a source is 'base', 'wta' or an H x W map (got %r)" % (s,))
-        elif np.ndim(s) != 2:
-            raise StereoHipError("candidates: a source is 'base', 'wta' or an H x W map")
+        check_source(s)
     K = offsets.shape[0] + len(sources) * taps.shape[0]
     if K > band.max_offsets():
-        raise StereoHipError("candidates: K = Ko + M * T must be 1 .. %d (got %d)" % (band.max_offsets(), K))
+        raise StereoHipError("%s: K = Ko + M * T must be 1 .. %d (got %d)" % (prefix, band.max_offsets(), K))
     return dict(offsets=offsets, taps=taps, sources=sources)
 
 
-def check_levels(levels):
-    """`levels` as a list of checked candidate levels (check_level); at least one."""
+def check_levels(levels, prefix="candidates", **how):
+    """`levels` as a list of checked candidate levels (check_level, which takes `prefix` and `how`); at least one."""
     if isinstance(levels, dict):
         levels = [levels]
-    levels = [check_level(l) for l in levels]
+    levels = [check_level(l, prefix=prefix, **how) for l in levels]
     if not levels:
-        raise StereoHipError("refine_candidates: levels must hold at least one candidate level")
+        raise StereoHipError("refine_%s: levels must hold at least one %s level" % (prefix.replace(" ", "_"), prefix[:-1].replace(" ", "-")))
     return levels
+
+
+def labels_of(level):
+    """K of a checked candidate level, before it is built."""
+    return level["offsets"].shape[0] + len(level["sources"]) * level["taps"].shape[0]
 
 
 class CandidateProblem(band.BandProblem):
     """One view's candidate problems on the device, with BandProblem's interface: the volume, the connectivity and the
     smoothness weights go up once; build() gathers a level's table around the current base, makes its inputs and binds
     them to `plan`; apply() moves the base on.  A candidate level's labels have no common offset grid, so it neither
-    takes nor leaves carried messages: stage() and carry_from() give None."""
+    takes nor leaves carried messages: stage(), leave() and carry_from() give None."""
 
     def __init__(self, ncc, disparities, unary_weight, base, conn, alphas=None, layout=0):
         super().__init__(ncc, disparities, unary_weight, base, conn, alphas, layout)
         self.d_cand = self.d_wta = None
 
-    @staticmethod
-    def labels_of(level):
-        return level["offsets"].shape[0] + len(level["sources"]) * level["taps"].shape[0]
+    labels_of = staticmethod(labels_of)
 
     def wta(self):
         """The volume's winner-take-all map (stereo_ncc_best_disp) as a (W, H) tensor, made once.  (Where it is not
@@ -316,7 +304,6 @@ class CandidateProblem(band.BandProblem):
     def build(self, level, plan, tol, zero_columns=None, carry=None):
         """The inputs of the candidate level `level` (check_level's dict) around the current base, bound to `plan`.
         zero_columns: as in BandProblem.build.  carry must be None."""
-        import torch
         if carry is not None:
             raise StereoHipError("candidates: a candidate level does not take carried messages")
         self.offsets = level["offsets"]
@@ -328,9 +315,7 @@ class CandidateProblem(band.BandProblem):
             d_disparities=self.d_disparities)
         if zero_columns is not None:
             self.d_unary.view(self.N, -1)[zero_columns] = 0.0
-        torch.cuda.current_stream().synchronize()
-        plan.bind_device(self.d_unary.data_ptr(), self.d_alphas.data_ptr(), tol, d_q=self.d_q.data_ptr(),
-                         d_qprim=self.d_qprim.data_ptr(), keepalive=[self.d_unary, self.d_q, self.d_qprim, self.d_alphas])
+        bind_inputs(self, plan, tol)
 
     def stage(self, plan):
         return None
@@ -340,9 +325,7 @@ class CandidateProblem(band.BandProblem):
 
     def apply(self, labels):
         """The map the labels of the level built last select -> the new base on the host, H x W."""
-        import torch
-        lab = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)).cuda()
-        self.d_base, _ = candidates_apply_device(self.d_cand, lab, (self.H, self.W))
+        self.d_base, _ = candidates_apply_device(self.d_cand, _device_labels(labels), (self.H, self.W))
         return self.d_base.cpu().numpy().T
 
 
@@ -360,22 +343,6 @@ def refine_candidates(ncc, disparities, unary_weight, base, kernel, tol, levels,
     conn = T.construct_neighborhood(H, W) if conn is None else conn
     prob = CandidateProblem(ncc, disparities, unary_weight, base, conn, alphas, layout)
     out = band.BandResult()
-    plans = {}
-    try:
-        for level in levels:
-            K = prob.labels_of(level)
-            if K not in plans:
-                plans[K] = TrwsPlan(int(kernel), K, prob.N, prob.conn)
-            plan = plans[K]
-            prob.build(level, plan, tol)
-            out.carried.append(False)
-            plan.iterate(maxiter, max_relgap)
-            labels, en, lb, it = plan.result()
-            out.paths.append(plan.path())
-            out.labels.append(labels); out.energy.append(en); out.lower_bound.append(lb); out.iterations.append(it)
-            out.maps.append(prob.apply(labels))
-        out.dispmap = out.maps[-1]
-    finally:
-        for plan in plans.values():
-            plan.close()
+    run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap)
+    out.dispmap = out.maps[-1]
     return out

@@ -218,9 +218,9 @@ def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, m
     as a two-member TrwsBatch; the labels are applied, the refined maps checked with `check_tol` and filled
     (collect_views).  band_plans: {K: [plan, plan]}, filled here, closed by the caller.  zero_occluded: the unary
     columns of the pixels the preceding check found occluded are zeroed.
-    The problems may as well be candidates.CandidateProblem: a level is then a candidate level, not a
-    vector of offsets (the problem's labels_of says how many labels it has), carry must be off, and `name`, the prefix of
-    the passes' entries in out.times, tells the two kinds apart.
+    The problems are driven by the protocol of band.run_levels (labels_of, build, leave, apply, carry_from), so they may
+    as well be candidates.CandidateProblem: a level is then a candidate level, not a vector of offsets,
+    carry must be off, and `name`, the prefix of the passes' entries in out.times, tells the two kinds apart.
     carry: every level after the first starts from the view's previous level's messages; the members
     take them as batch members take any state.  stages: per view the carry.Stage the FIRST level starts from (None:
     from zero) -- a solve on this grid, or with scales=True on the grid one box reduction coarser.  out.stages: per
@@ -240,7 +240,7 @@ def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, m
         with TrwsBatch(band_plans[Kb]) as batch:
             batch.iterate(maxiter, max_relgap)
         if carry:
-            out.stages = [prob.stage(plan) for prob, plan in zip(problems, band_plans[Kb])]
+            out.stages = [prob.leave(plan) for prob, plan in zip(problems, band_plans[Kb])]
         out.times["%s_%d" % (name, level + 1)] = time.perf_counter() - t0
         collect_views(out, band_plans[Kb], lambda i, labels: problems[i].apply(labels), check_tol,
                       "%s_%d_check_fill" % (name, level + 1))

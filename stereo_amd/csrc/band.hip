@@ -8,6 +8,9 @@
 // slices of one volume column; in the label-fastest volume (layout 1) those are the same cache lines, so
 // the column's span comes from memory once and the lanes' three loads each are served from cache.  LDS holds the
 // D slice positions of the unary kernel and nothing else.
+//
+// What this file shares with plane_band.hip, candidates.hip and plane_candidates.hip -- the element index, the launch
+// sizes, slice_range(), the argument checks, the scans of a host entry's arrays and HostOutputs -- is in band_common.h.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -20,7 +23,7 @@
 namespace {
 
 using stereo::fail;
-using namespace stereo::band;   // kTB, kMaxOffsets, band_index, check_offsets, check_sizes, guarded, grid_for
+using namespace stereo::band;   // band_common.h: the indices, the launch sizes, every check and scan, HostOutputs
 
 // The disparity of label k at a pixel whose base is b: plane_disp of [0 0 1 -(b + delta)].  The plane's
 // s = 0 x + 0 y is +0 at every pixel, so no pixel coordinate is formed; the value is b + delta, with the
@@ -33,7 +36,6 @@ __device__ __forceinline__ double band_disp(double b, double delta) {
 // kStageSlices: the block copies the D slice positions into LDS first.  The nearest-slice search and the parabola read
 // them a dozen times per lane, each read waiting for the one before (bisection); from LDS that chain is several
 // times shorter than from the vector cache (DESIGN.md 6.2 has the measurement that asked for it).
-constexpr int kMaxStagedSlices = 4096;   // 32 KiB of LDS; beyond it the kernel reads the slices where they are
 template <bool kStageSlices>
 __global__ __launch_bounds__(kTB) void band_unary_kernel(const double *__restrict__ ncc, int64_t Npx, int D, int layout,
                                                         const double *__restrict__ dv, double dmin, double dmax,
@@ -122,11 +124,9 @@ int check_inputs(const std::string &what, const void *ncc, int H, int W, int D, 
                  const void *base, const double *offsets, int K, int64_t E, const void *conn, const void *unary,
                  const void *q, const void *qprim, char *err, size_t errcap) {
   if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
-  if (D < 1) return fail(what + ": D must be at least 1", err, errcap);
-  if (layout != 0 && layout != 1) return fail(what + ": layout must be 0 (H x W x D) or 1 (D x N, label fastest)", err, errcap);
-  if (E < 0) return fail(what + ": E must not be negative", err, errcap);
-  if (!ncc || !disparities || !base || !unary) return fail(what + ": ncc, disparities, base and unary must not be NULL", err, errcap);
-  if (E > 0 && (!conn || !q || !qprim)) return fail(what + ": conn, q and qprim must not be NULL", err, errcap);
+  if (int rc = check_volume(what, ncc, D, layout, disparities, err, errcap)) return rc;
+  if (int rc = check_edges(what, E, conn, q, qprim, err, errcap)) return rc;
+  if (!base || !unary) return fail(what + ": base and unary must not be NULL", err, errcap);
   return check_offsets(what, offsets, K, err, errcap);
 }
 
@@ -137,33 +137,20 @@ int check_apply(const std::string &what, const void *base, int H, int W, const v
   return check_offsets(what, offsets, K, err, errcap);
 }
 
-int check_base(const std::string &what, const double *base, int H, int W, char *err, size_t errcap) {
-  for (int64_t i = 0; i < (int64_t)H * W; ++i)
-    if (!std::isfinite(base[i]))
-      return fail(what + ": base is not finite at pixel (row " + std::to_string(i % H) + ", column " + std::to_string(i / H) + ")", err, errcap);
-  return 0;
-}
-
 // `disparities` / `offsets`: the host vectors (checked; min, max and the order of the slices come from them);
 // `d_disparities` / `d_offsets`: the same values in device memory, which the kernels read
 void launch_inputs(const double *ncc, int H, int W, int D, int layout, const double *disparities,
                    const double *d_disparities, double unary_weight, const double *base, const double *d_offsets, int K,
                    int64_t E, const uint32_t *conn, double *unary, double *q, double *qprim, int32_t *bad, hipStream_t s) {
   const int64_t Npx = (int64_t)H * W;
-  double dmin = disparities[0], dmax = disparities[0];
-  bool ascending = disparities[0] == disparities[0];
-  for (int i = 1; i < D; ++i) {
-    dmin = disparities[i] < dmin ? disparities[i] : dmin;
-    dmax = disparities[i] > dmax ? disparities[i] : dmax;
-    ascending = ascending && disparities[i] > disparities[i - 1];
-  }
+  const SliceRange r = slice_range(disparities, D);
   if (bad) STEREO_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int32_t), s));
   if (D <= kMaxStagedSlices)
     hipLaunchKernelGGL(band_unary_kernel<true>, dim3(grid_for(Npx * K)), dim3(kTB), (size_t)D * sizeof(double), s, ncc, Npx, D,
-                       layout, d_disparities, dmin, dmax, unary_weight, base, d_offsets, K, ascending ? 1 : 0, unary, bad);
+                       layout, d_disparities, r.dmin, r.dmax, unary_weight, base, d_offsets, K, r.ascending, unary, bad);
   else
     hipLaunchKernelGGL(band_unary_kernel<false>, dim3(grid_for(Npx * K)), dim3(kTB), 0, s, ncc, Npx, D, layout, d_disparities,
-                       dmin, dmax, unary_weight, base, d_offsets, K, ascending ? 1 : 0, unary, bad);
+                       r.dmin, r.dmax, unary_weight, base, d_offsets, K, r.ascending, unary, bad);
   STEREO_HIP_CHECK(hipGetLastError());
   if (E > 0) {
     hipLaunchKernelGGL(band_positions_kernel, dim3(grid_for((E * K + kPosPerThread - 1) / kPosPerThread)), dim3(kTB), 0, s, E, K, Npx, conn, base, d_offsets, q, qprim);
@@ -214,22 +201,16 @@ int stereo_band_inputs(const double *ncc, int H, int W, int D, int layout, const
   const std::string what = "stereo_band_inputs";
   if (int rc = check_inputs(what, ncc, H, W, D, layout, disparities, base, offsets, K, E, conn, unary, q, qprim, err, errcap))
     return rc;
-  if (int rc = check_base(what, base, H, W, err, errcap)) return rc;
   const size_t n = (size_t)H * W;
-  for (int64_t e = 0; e < 2 * E; ++e)
-    if (conn[e] >= n) return fail(what + ": conn names a pixel outside 0 .. H*W - 1 (edge " + std::to_string(e / 2) + ")", err, errcap);
+  if (int rc = check_finite(what, "base", base, (int64_t)n, H, 0, err, errcap)) return rc;
+  if (int rc = check_conn(what, conn, E, n, err, errcap)) return rc;
   return guarded("stereo_band_inputs", err, errcap, [&] {
-    stereo::DevBuf<double> dn, db, dd, doff, du, dq, dqp;
-    stereo::DevBuf<uint32_t> dc;
-    dn.upload(ncc, n * D); db.upload(base, n); dd.upload(disparities, D); doff.upload(offsets, K); du.alloc(n * K);
-    if (E > 0) { dc.upload(conn, 2 * (size_t)E); dq.alloc((size_t)E * K); dqp.alloc((size_t)E * K); }
-    launch_inputs(dn.p, H, W, D, layout, disparities, dd.p, unary_weight, db.p, doff.p, K, E, dc.p, du.p, dq.p, dqp.p, nullptr,
-                  nullptr);
-    STEREO_HIP_CHECK(hipMemcpy(unary, du.p, n * K * sizeof(double), hipMemcpyDeviceToHost));
-    if (E > 0) {
-      STEREO_HIP_CHECK(hipMemcpy(q, dq.p, (size_t)E * K * sizeof(double), hipMemcpyDeviceToHost));
-      STEREO_HIP_CHECK(hipMemcpy(qprim, dqp.p, (size_t)E * K * sizeof(double), hipMemcpyDeviceToHost));
-    }
+    stereo::DevBuf<double> dn, db, dd, doff;
+    dn.upload(ncc, n * D); db.upload(base, n); dd.upload(disparities, D); doff.upload(offsets, K);
+    HostOutputs out(n, K, E, conn);
+    launch_inputs(dn.p, H, W, D, layout, disparities, dd.p, unary_weight, db.p, doff.p, K, E, out.dc.p, out.du.p, out.dq.p,
+                  out.dqp.p, nullptr, nullptr);
+    out.fetch(unary, q, qprim);
   });
 }
 
@@ -237,11 +218,9 @@ int stereo_band_apply(const double *base, int H, int W, const int32_t *labels, c
                       char *err, size_t errcap) {
   const std::string what = "stereo_band_apply";
   if (int rc = check_apply(what, base, H, W, labels, offsets, K, refined, err, errcap)) return rc;
-  if (int rc = check_base(what, base, H, W, err, errcap)) return rc;
   const size_t n = (size_t)H * W;
-  for (size_t i = 0; i < n; ++i)
-    if (labels[i] < 1 || labels[i] > K)
-      return fail(what + ": label " + std::to_string(labels[i]) + " at pixel " + std::to_string(i) + " is outside 1 .. " + std::to_string(K), err, errcap);
+  if (int rc = check_finite(what, "base", base, (int64_t)n, H, 0, err, errcap)) return rc;
+  if (int rc = check_labels(what, labels, n, K, err, errcap)) return rc;
   return guarded("stereo_band_apply", err, errcap, [&] {
     stereo::DevBuf<double> db, doff, out;
     stereo::DevBuf<int32_t> dl;

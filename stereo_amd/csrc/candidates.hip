@@ -6,7 +6,9 @@
 // selects.
 //
 // The lane mapping is the band's (band.hip): a lane is one (pixel, k) or (edge, k) element in storage order, every
-// wave stores 512 consecutive bytes, the 64-bit division by K is done once per block on uniform values.
+// wave stores 512 consecutive bytes, the 64-bit division by K is done once per block on uniform values.  The index,
+// the clamp of a tap (tapped_pixel), the launch sizes, slice_range(), the argument checks (check_gather takes the
+// names of this file's two arrays), the scans of a host entry's arrays and HostOutputs are in band_common.h.
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -19,9 +21,7 @@
 namespace {
 
 using stereo::fail;
-using namespace stereo::band;   // kTB, kMaxOffsets, band_index, check_offsets, check_sizes, guarded, grid_for
-
-constexpr int kMaxTap = 1 << 15;   // |dy|, |dx| below it: a tap never needs more than the int32 it is stored in
+using namespace stereo::band;   // band_common.h: the indices, the launch sizes, every check and scan, HostOutputs
 
 // The disparity of a label whose candidate is c: plane_disp of [0 0 1 -c], i.e. c with the plane's sign of zero
 // (-0 for c == 0), as band_disp gives it for base + delta.
@@ -53,11 +53,7 @@ __global__ __launch_bounds__(kTB) void candidates_gather_kernel(int64_t Npx, int
       v = base[ix.item] + offsets[ix.k];
     } else {
       const int j = ix.k - Ko, m = j / T, t = j - m * T;
-      const uint32_t px = (uint32_t)ix.item, x = px / (uint32_t)H, y = px - x * (uint32_t)H;
-      int64_t ys = (int64_t)y + taps[2 * t], xs = (int64_t)x + taps[2 * t + 1];
-      ys = ys < 0 ? 0 : ys > H - 1 ? H - 1 : ys;
-      xs = xs < 0 ? 0 : xs > W - 1 ? W - 1 : xs;
-      v = sources[(int64_t)m * Npx + xs * H + ys];
+      v = sources[(int64_t)m * Npx + tapped_pixel(ix.item, H, W, taps, t)];
     }
     cand[first + threadIdx.x] = v;
   }
@@ -68,7 +64,6 @@ __global__ __launch_bounds__(kTB) void candidates_gather_kernel(int64_t Npx, int
 // finite: a lane tests the candidate it has loaded anyway, and only a lane that finds one looks at the pixel's
 // lower labels to see whether it is the first (a loop over K in the lane k == 0 of every pixel cost 17 - 37 % of the
 // builder's time).
-constexpr int kMaxStagedSlices = 4096;   // 32 KiB of LDS; beyond it the kernel reads the slices where they are
 template <bool kStageSlices>
 __global__ __launch_bounds__(kTB) void candidates_unary_kernel(const double *__restrict__ ncc, int64_t Npx, int D, int layout,
                                                               const double *__restrict__ dv, double dmin, double dmax,
@@ -152,39 +147,13 @@ __global__ __launch_bounds__(kTB) void candidates_apply_kernel(int64_t Npx, int 
 
 // ---------------------------------------------------------------- argument checks (no device call)
 
-int check_k(const std::string &what, int K, char *err, size_t errcap) {
-  if (K < 1 || K > kMaxOffsets)
-    return fail(what + ": the number of candidates K must be 1 .. " + std::to_string(kMaxOffsets) + " (got " + std::to_string(K) + ")", err, errcap);
-  return 0;
-}
-
-int check_gather(const std::string &what, const void *base, int H, int W, const double *offsets, int Ko, const void *sources,
-                 int M, const int32_t *taps, int T, const void *cand, char *err, size_t errcap) {
-  if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
-  if (M < 0 || T < 0) return fail(what + ": M and T must not be negative", err, errcap);
-  if (!base || !cand) return fail(what + ": base and cand must not be NULL", err, errcap);
-  if (int rc = check_offsets(what, offsets, Ko, err, errcap)) return rc;
-  const int64_t K = (int64_t)Ko + (int64_t)M * T;
-  if (K > kMaxOffsets)
-    return fail(what + ": the number of candidates K = Ko + M * T must be 1 .. " + std::to_string(kMaxOffsets) + " (got " + std::to_string(K) + ")", err, errcap);
-  if ((int64_t)M * T > 0) {
-    if (!sources || !taps) return fail(what + ": sources and taps must not be NULL when M * T > 0", err, errcap);
-    for (int t = 0; t < 2 * T; ++t)
-      if (taps[t] <= -kMaxTap || taps[t] >= kMaxTap)
-        return fail(what + ": tap " + std::to_string(t / 2) + " has |dy| or |dx| of 2^15 or more", err, errcap);
-  }
-  return 0;
-}
-
 int check_inputs(const std::string &what, const void *ncc, int H, int W, int D, int layout, const double *disparities,
                  const void *cand, int K, int64_t E, const void *conn, const void *unary, const void *q, const void *qprim,
                  char *err, size_t errcap) {
   if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
-  if (D < 1) return fail(what + ": D must be at least 1", err, errcap);
-  if (layout != 0 && layout != 1) return fail(what + ": layout must be 0 (H x W x D) or 1 (D x N, label fastest)", err, errcap);
-  if (E < 0) return fail(what + ": E must not be negative", err, errcap);
-  if (!ncc || !disparities || !cand || !unary) return fail(what + ": ncc, disparities, cand and unary must not be NULL", err, errcap);
-  if (E > 0 && (!conn || !q || !qprim)) return fail(what + ": conn, q and qprim must not be NULL", err, errcap);
+  if (int rc = check_volume(what, ncc, D, layout, disparities, err, errcap)) return rc;
+  if (int rc = check_edges(what, E, conn, q, qprim, err, errcap)) return rc;
+  if (!cand || !unary) return fail(what + ": cand and unary must not be NULL", err, errcap);
   return check_k(what, K, err, errcap);
 }
 
@@ -193,22 +162,6 @@ int check_apply(const std::string &what, const void *cand, int H, int W, int K, 
   if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
   if (!cand || !labels || !out) return fail(what + ": cand, labels and out must not be NULL", err, errcap);
   return check_k(what, K, err, errcap);
-}
-
-int check_map(const std::string &what, const std::string &name, const double *map, int H, int W, char *err, size_t errcap) {
-  for (int64_t i = 0; i < (int64_t)H * W; ++i)
-    if (!std::isfinite(map[i]))
-      return fail(what + ": " + name + " is not finite at pixel (row " + std::to_string(i % H) + ", column " + std::to_string(i / H) + ")", err, errcap);
-  return 0;
-}
-
-int check_table(const std::string &what, const double *cand, int H, int W, int K, char *err, size_t errcap) {
-  for (int64_t t = 0; t < (int64_t)H * W * K; ++t)
-    if (!std::isfinite(cand[t])) {
-      const int64_t i = t / K;
-      return fail(what + ": cand is not finite at pixel (row " + std::to_string(i % H) + ", column " + std::to_string(i / H) + "), label " + std::to_string(t % K + 1), err, errcap);
-    }
-  return 0;
 }
 
 void launch_gather(const double *base, int H, int W, const double *d_offsets, int Ko, const double *sources, int M,
@@ -224,20 +177,14 @@ void launch_inputs(const double *ncc, int H, int W, int D, int layout, const dou
                    double unary_weight, const double *cand, int K, int64_t E, const uint32_t *conn, double *unary, double *q,
                    double *qprim, int32_t *bad, hipStream_t s) {
   const int64_t Npx = (int64_t)H * W;
-  double dmin = disparities[0], dmax = disparities[0];
-  bool ascending = disparities[0] == disparities[0];
-  for (int i = 1; i < D; ++i) {
-    dmin = disparities[i] < dmin ? disparities[i] : dmin;
-    dmax = disparities[i] > dmax ? disparities[i] : dmax;
-    ascending = ascending && disparities[i] > disparities[i - 1];
-  }
+  const SliceRange r = slice_range(disparities, D);
   if (bad) STEREO_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int32_t), s));
   if (D <= kMaxStagedSlices)
     hipLaunchKernelGGL(candidates_unary_kernel<true>, dim3(grid_for(Npx * K)), dim3(kTB), (size_t)D * sizeof(double), s, ncc, Npx,
-                       D, layout, d_disparities, dmin, dmax, unary_weight, cand, K, ascending ? 1 : 0, unary, bad);
+                       D, layout, d_disparities, r.dmin, r.dmax, unary_weight, cand, K, r.ascending, unary, bad);
   else
     hipLaunchKernelGGL(candidates_unary_kernel<false>, dim3(grid_for(Npx * K)), dim3(kTB), 0, s, ncc, Npx, D, layout,
-                       d_disparities, dmin, dmax, unary_weight, cand, K, ascending ? 1 : 0, unary, bad);
+                       d_disparities, r.dmin, r.dmax, unary_weight, cand, K, r.ascending, unary, bad);
   STEREO_HIP_CHECK(hipGetLastError());
   if (E > 0) {
     hipLaunchKernelGGL(candidates_positions_kernel, dim3(grid_for((E * K + kPosPerThread - 1) / kPosPerThread)), dim3(kTB), 0, s, E,
@@ -261,7 +208,7 @@ int stereo_candidates_gather_device(const double *base, int H, int W, const doub
                                     const double *sources, int M, const int32_t *taps, const int32_t *d_taps, int T,
                                     double *cand, int32_t *bad, void *stream, char *err, size_t errcap) {
   const std::string what = "stereo_candidates_gather_device";
-  if (int rc = check_gather(what, base, H, W, offsets, Ko, sources, M, taps, T, cand, err, errcap)) return rc;
+  if (int rc = check_gather(what, "base", "cand", base, H, W, offsets, Ko, sources, M, taps, T, cand, err, errcap)) return rc;
   if (!d_offsets) return fail(what + ": d_offsets must not be NULL", err, errcap);
   if ((int64_t)M * T > 0 && !d_taps) return fail(what + ": d_taps must not be NULL when M * T > 0", err, errcap);
   return guarded("stereo_candidates_gather_device", err, errcap,
@@ -291,12 +238,12 @@ int stereo_candidates_apply_device(const double *cand, int H, int W, int K, cons
 int stereo_candidates_gather(const double *base, int H, int W, const double *offsets, int Ko, const double *sources, int M,
                              const int32_t *taps, int T, double *cand, char *err, size_t errcap) {
   const std::string what = "stereo_candidates_gather";
-  if (int rc = check_gather(what, base, H, W, offsets, Ko, sources, M, taps, T, cand, err, errcap)) return rc;
-  if (int rc = check_map(what, "base", base, H, W, err, errcap)) return rc;
+  if (int rc = check_gather(what, "base", "cand", base, H, W, offsets, Ko, sources, M, taps, T, cand, err, errcap)) return rc;
   const size_t n = (size_t)H * W;
+  if (int rc = check_finite(what, "base", base, (int64_t)n, H, 0, err, errcap)) return rc;
   const bool taken = (int64_t)M * T > 0;
   for (int m = 0; taken && m < M; ++m)
-    if (int rc = check_map(what, "source " + std::to_string(m), sources + (size_t)m * n, H, W, err, errcap)) return rc;
+    if (int rc = check_finite(what, "source " + std::to_string(m), sources + (size_t)m * n, (int64_t)n, H, 0, err, errcap)) return rc;
   const size_t K = (size_t)Ko + (size_t)M * T;
   return guarded("stereo_candidates_gather", err, errcap, [&] {
     stereo::DevBuf<double> db, doff, ds, dc;
@@ -313,21 +260,16 @@ int stereo_candidates_inputs(const double *ncc, int H, int W, int D, int layout,
                              double *qprim, char *err, size_t errcap) {
   const std::string what = "stereo_candidates_inputs";
   if (int rc = check_inputs(what, ncc, H, W, D, layout, disparities, cand, K, E, conn, unary, q, qprim, err, errcap)) return rc;
-  if (int rc = check_table(what, cand, H, W, K, err, errcap)) return rc;
   const size_t n = (size_t)H * W;
-  for (int64_t e = 0; e < 2 * E; ++e)
-    if (conn[e] >= n) return fail(what + ": conn names a pixel outside 0 .. H*W - 1 (edge " + std::to_string(e / 2) + ")", err, errcap);
+  if (int rc = check_finite(what, "cand", cand, (int64_t)n, H, K, err, errcap)) return rc;
+  if (int rc = check_conn(what, conn, E, n, err, errcap)) return rc;
   return guarded("stereo_candidates_inputs", err, errcap, [&] {
-    stereo::DevBuf<double> dn, dcand, dd, du, dq, dqp;
-    stereo::DevBuf<uint32_t> dc;
-    dn.upload(ncc, n * D); dcand.upload(cand, n * K); dd.upload(disparities, D); du.alloc(n * K);
-    if (E > 0) { dc.upload(conn, 2 * (size_t)E); dq.alloc((size_t)E * K); dqp.alloc((size_t)E * K); }
-    launch_inputs(dn.p, H, W, D, layout, disparities, dd.p, unary_weight, dcand.p, K, E, dc.p, du.p, dq.p, dqp.p, nullptr, nullptr);
-    STEREO_HIP_CHECK(hipMemcpy(unary, du.p, n * K * sizeof(double), hipMemcpyDeviceToHost));
-    if (E > 0) {
-      STEREO_HIP_CHECK(hipMemcpy(q, dq.p, (size_t)E * K * sizeof(double), hipMemcpyDeviceToHost));
-      STEREO_HIP_CHECK(hipMemcpy(qprim, dqp.p, (size_t)E * K * sizeof(double), hipMemcpyDeviceToHost));
-    }
+    stereo::DevBuf<double> dn, dcand, dd;
+    dn.upload(ncc, n * D); dcand.upload(cand, n * K); dd.upload(disparities, D);
+    HostOutputs out(n, K, E, conn);
+    launch_inputs(dn.p, H, W, D, layout, disparities, dd.p, unary_weight, dcand.p, K, E, out.dc.p, out.du.p, out.dq.p, out.dqp.p,
+                  nullptr, nullptr);
+    out.fetch(unary, q, qprim);
   });
 }
 
@@ -335,11 +277,9 @@ int stereo_candidates_apply(const double *cand, int H, int W, int K, const int32
                             size_t errcap) {
   const std::string what = "stereo_candidates_apply";
   if (int rc = check_apply(what, cand, H, W, K, labels, out, err, errcap)) return rc;
-  if (int rc = check_table(what, cand, H, W, K, err, errcap)) return rc;
   const size_t n = (size_t)H * W;
-  for (size_t i = 0; i < n; ++i)
-    if (labels[i] < 1 || labels[i] > K)
-      return fail(what + ": label " + std::to_string(labels[i]) + " at pixel " + std::to_string(i) + " is outside 1 .. " + std::to_string(K), err, errcap);
+  if (int rc = check_finite(what, "cand", cand, (int64_t)n, H, K, err, errcap)) return rc;
+  if (int rc = check_labels(what, labels, n, K, err, errcap)) return rc;
   return guarded("stereo_candidates_apply", err, errcap, [&] {
     stereo::DevBuf<double> dcand, dout;
     stereo::DevBuf<int32_t> dl;

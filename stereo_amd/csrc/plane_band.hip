@@ -5,9 +5,10 @@
 // (gs_sample.h), q / qprim (K x E) by the plane -> disparity rule with the rescaling of stereo_trws_positions,
 // and the planes a labelling selects.
 //
-// The layout is band.hip's: the outputs are label fastest, a lane is one (pixel, k) or (edge, k) element of them in
-// storage order (every wave stores 512 consecutive bytes), and the 64-bit division by K is done once per block on
-// uniform values.  The K lanes of a pixel or an edge read the same planes, so those come from cache.  A pixel's
+// The layout is band.hip's, and the index, the launch sizes, the argument checks, the scans of a host entry's arrays
+// and HostOutputs are the shared ones of band_common.h: the outputs are label fastest, a lane is one (pixel, k) or
+// (edge, k) element of them in storage order (every wave stores 512 consecutive bytes), and the 64-bit division by K is
+// done once per block on uniform values.  The K lanes of a pixel or an edge read the same planes, so those come from cache.  A pixel's
 // point is [id / H + 1, id % H + 1], formed in the kernel; no points array is read.
 #include <cmath>
 #include <cstdint>
@@ -22,7 +23,7 @@
 namespace {
 
 using stereo::fail;
-using namespace stereo::band;   // kTB, band_index, check_offsets, check_sizes, guarded, grid_for, NccSource, GsSource
+using namespace stereo::band;   // band_common.h: the indices, the launch sizes, every check and scan, HostOutputs; the sources
 
 // The plane of label k at a pixel: one fp64 multiplication and one fp64 subtraction (no contraction: the file is
 // compiled with -ffp-contract=off).
@@ -32,7 +33,7 @@ __device__ __forceinline__ bool plane_ok(double a, double b, double c, double d)
   return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d) && c != 0.0;
 }
 
-// The two unary sources, NccSource<kStageSlices> and GsSource: unary_source.h (shared with plane_candidates.hip).
+// The two unary sources, NccSource<kStageSlices> and GsSource: unary_source.h.
 
 template <class Source>
 __global__ __launch_bounds__(kTB) void plane_band_unary_kernel(Source src, int H, int64_t Npx, const double *__restrict__ planes,
@@ -137,33 +138,13 @@ __global__ __launch_bounds__(kTB) void plane_band_apply_kernel(int64_t Npx, int 
 
 // ---------------------------------------------------------------- argument checks (no device call)
 
+// the part of an inputs entry's checks that does not depend on the unary source
 int check_band(const std::string &what, int H, int W, const void *planes, const double *offsets, int K, int64_t E,
                const void *conn, const void *unary, const void *q, const void *qprim, char *err, size_t errcap) {
   if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
-  if (E < 0) return fail(what + ": E must not be negative", err, errcap);
+  if (int rc = check_edges(what, E, conn, q, qprim, err, errcap)) return rc;
   if (!planes || !unary) return fail(what + ": planes and unary must not be NULL", err, errcap);
-  if (E > 0 && (!conn || !q || !qprim)) return fail(what + ": conn, q and qprim must not be NULL", err, errcap);
   return check_offsets(what, offsets, K, err, errcap);
-}
-
-int check_ncc(const std::string &what, const void *ncc, int H, int W, int D, int layout, const double *disparities,
-              const void *planes, const double *offsets, int K, int64_t E, const void *conn, const void *unary, const void *q,
-              const void *qprim, char *err, size_t errcap) {
-  if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
-  if (D < 1) return fail(what + ": D must be at least 1", err, errcap);
-  if (layout != 0 && layout != 1) return fail(what + ": layout must be 0 (H x W x D) or 1 (D x N, label fastest)", err, errcap);
-  if (!ncc || !disparities) return fail(what + ": ncc and disparities must not be NULL", err, errcap);
-  return check_band(what, H, W, planes, offsets, K, E, conn, unary, q, qprim, err, errcap);
-}
-
-int check_gs(const std::string &what, const void *im0, const void *im1, int H, int W, int C, const double *P2, double d_step,
-             const void *planes, const double *offsets, int K, int64_t E, const void *conn, const void *unary, const void *q,
-             const void *qprim, char *err, size_t errcap) {
-  if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
-  if (C < 1) return fail(what + ": C must be at least 1", err, errcap);
-  if (!im0 || !im1 || !P2) return fail(what + ": im0, im1 and P2 must not be NULL", err, errcap);
-  if (d_step == 0) return fail(what + ": d_step must not be 0 (the photo-consistency unary divides by it)", err, errcap);
-  return check_band(what, H, W, planes, offsets, K, E, conn, unary, q, qprim, err, errcap);
 }
 
 int check_apply(const std::string &what, const void *planes, int64_t N, const void *labels, const double *offsets, int K,
@@ -172,25 +153,6 @@ int check_apply(const std::string &what, const void *planes, int64_t N, const vo
   if (N >= ((int64_t)1 << 31)) return fail(what + ": N must be below 2^31", err, errcap);
   if (!planes || !labels || !refined) return fail(what + ": planes, labels and refined must not be NULL", err, errcap);
   return check_offsets(what, offsets, K, err, errcap);
-}
-
-// H > 0: the message names the pixel by row and column; H == 0: by its index
-int check_planes(const std::string &what, const double *planes, int64_t N, int H, char *err, size_t errcap) {
-  for (int64_t i = 0; i < N; ++i) {
-    const double *p = planes + 4 * i;
-    const bool finite = std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && std::isfinite(p[3]);
-    if (finite && p[2] != 0) continue;
-    const std::string where = H > 0 ? "pixel (row " + std::to_string(i % H) + ", column " + std::to_string(i / H) + ")"
-                                    : "pixel " + std::to_string(i);
-    return fail(what + (finite ? ": Infinite disparity (c == 0) at " : ": a plane is not finite at ") + where, err, errcap);
-  }
-  return 0;
-}
-
-int check_conn(const std::string &what, const uint32_t *conn, int64_t E, size_t n, char *err, size_t errcap) {
-  for (int64_t e = 0; e < 2 * E; ++e)
-    if (conn[e] >= n) return fail(what + ": conn names a pixel outside 0 .. H*W - 1 (edge " + std::to_string(e / 2) + ")", err, errcap);
-  return 0;
 }
 
 void launch_positions(int H, int64_t Npx, const double *planes, const double *d_offsets, int K, int64_t E, const uint32_t *conn,
@@ -207,20 +169,14 @@ void launch_ncc(const double *ncc, int H, int W, int D, int layout, const double
                 double unary_weight, const double *planes, const double *d_offsets, int K, int64_t E, const uint32_t *conn,
                 double *unary, double *q, double *qprim, int32_t *bad, hipStream_t s) {
   const int64_t Npx = (int64_t)H * W;
-  double dmin = disparities[0], dmax = disparities[0];
-  bool ascending = disparities[0] == disparities[0];
-  for (int i = 1; i < D; ++i) {
-    dmin = disparities[i] < dmin ? disparities[i] : dmin;
-    dmax = disparities[i] > dmax ? disparities[i] : dmax;
-    ascending = ascending && disparities[i] > disparities[i - 1];
-  }
+  const SliceRange r = slice_range(disparities, D);
   if (bad) STEREO_HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(int32_t), s));
   if (D <= kMaxStagedSlices) {
-    const NccSource<true> src{ncc, D, layout, d_disparities, dmin, dmax, unary_weight, ascending ? 1 : 0};
+    const NccSource<true> src{ncc, D, layout, d_disparities, r.dmin, r.dmax, unary_weight, r.ascending};
     hipLaunchKernelGGL(plane_band_unary_kernel<NccSource<true>>, dim3(grid_for(Npx * K)), dim3(kTB), (size_t)D * sizeof(double), s,
                        src, H, Npx, planes, d_offsets, K, unary, bad);
   } else {
-    const NccSource<false> src{ncc, D, layout, d_disparities, dmin, dmax, unary_weight, ascending ? 1 : 0};
+    const NccSource<false> src{ncc, D, layout, d_disparities, r.dmin, r.dmax, unary_weight, r.ascending};
     hipLaunchKernelGGL(plane_band_unary_kernel<NccSource<false>>, dim3(grid_for(Npx * K)), dim3(kTB), 0, s, src, H, Npx, planes,
                        d_offsets, K, unary, bad);
   }
@@ -248,23 +204,6 @@ void launch_apply(const double *planes, int64_t N, const int32_t *labels, const 
   STEREO_HIP_CHECK(hipGetLastError());
 }
 
-// the outputs of a host entry: allocated on the device, fetched after the launches
-struct HostOutputs {
-  stereo::DevBuf<double> du, dq, dqp;
-  size_t nu, ne;
-  HostOutputs(size_t n, int K, int64_t E) : nu(n * K), ne((size_t)E * K) {
-    du.alloc(nu);
-    if (E > 0) { dq.alloc(ne); dqp.alloc(ne); }
-  }
-  void fetch(double *unary, double *q, double *qprim) {
-    STEREO_HIP_CHECK(hipMemcpy(unary, du.p, nu * sizeof(double), hipMemcpyDeviceToHost));
-    if (ne > 0) {
-      STEREO_HIP_CHECK(hipMemcpy(q, dq.p, ne * sizeof(double), hipMemcpyDeviceToHost));
-      STEREO_HIP_CHECK(hipMemcpy(qprim, dqp.p, ne * sizeof(double), hipMemcpyDeviceToHost));
-    }
-  }
-};
-
 }  // namespace
 
 extern "C" {
@@ -275,7 +214,8 @@ int stereo_plane_band_inputs_ncc_device(const double *ncc, int H, int W, int D, 
                                         double *unary, double *q, double *qprim, int32_t *bad, void *stream, char *err,
                                         size_t errcap) {
   const char *what = "stereo_plane_band_inputs_ncc_device";
-  if (int rc = check_ncc(what, ncc, H, W, D, layout, disparities, planes, offsets, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_band(what, H, W, planes, offsets, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_volume(what, ncc, D, layout, disparities, err, errcap)) return rc;
   if (!d_disparities || !d_offsets) return fail(std::string(what) + ": d_disparities and d_offsets must not be NULL", err, errcap);
   return guarded(what, err, errcap, [&] {
     launch_ncc(ncc, H, W, D, layout, disparities, d_disparities, unary_weight, planes, d_offsets, K, E, conn, unary, q, qprim, bad,
@@ -289,7 +229,8 @@ int stereo_plane_band_inputs_globalstereo_device(const double *im0, const double
                                                  const uint32_t *conn, double *unary, double *q, double *qprim, int32_t *bad,
                                                  void *stream, char *err, size_t errcap) {
   const char *what = "stereo_plane_band_inputs_globalstereo_device";
-  if (int rc = check_gs(what, im0, im1, H, W, C, P2, d_step, planes, offsets, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_band(what, H, W, planes, offsets, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_gs(what, im0, im1, C, P2, d_step, err, errcap)) return rc;
   if (!d_offsets) return fail(std::string(what) + ": d_offsets must not be NULL", err, errcap);
   return guarded(what, err, errcap, [&] {
     launch_gs(im0, im1, H, W, C, P2, d_min, d_step, col_thresh, planes, d_offsets, K, E, conn, unary, q, qprim, bad,
@@ -310,17 +251,16 @@ int stereo_plane_band_inputs_ncc(const double *ncc, int H, int W, int D, int lay
                                  double unary_weight, const double *planes, const double *offsets, int K, int64_t E,
                                  const uint32_t *conn, double *unary, double *q, double *qprim, char *err, size_t errcap) {
   const std::string what = "stereo_plane_band_inputs_ncc";
-  if (int rc = check_ncc(what, ncc, H, W, D, layout, disparities, planes, offsets, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_band(what, H, W, planes, offsets, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_volume(what, ncc, D, layout, disparities, err, errcap)) return rc;
   const size_t n = (size_t)H * W;
-  if (int rc = check_planes(what, planes, (int64_t)n, H, err, errcap)) return rc;
+  if (int rc = check_planes(what, "", planes, (int64_t)n, H, 0, err, errcap)) return rc;
   if (int rc = check_conn(what, conn, E, n, err, errcap)) return rc;
   return guarded("stereo_plane_band_inputs_ncc", err, errcap, [&] {
     stereo::DevBuf<double> dn, dp, dd, doff;
-    stereo::DevBuf<uint32_t> dc;
     dn.upload(ncc, n * D); dp.upload(planes, 4 * n); dd.upload(disparities, D); doff.upload(offsets, K);
-    if (E > 0) dc.upload(conn, 2 * (size_t)E);
-    HostOutputs out(n, K, E);
-    launch_ncc(dn.p, H, W, D, layout, disparities, dd.p, unary_weight, dp.p, doff.p, K, E, dc.p, out.du.p, out.dq.p, out.dqp.p,
+    HostOutputs out(n, K, E, conn);
+    launch_ncc(dn.p, H, W, D, layout, disparities, dd.p, unary_weight, dp.p, doff.p, K, E, out.dc.p, out.du.p, out.dq.p, out.dqp.p,
                nullptr, nullptr);
     out.fetch(unary, q, qprim);
   });
@@ -331,17 +271,16 @@ int stereo_plane_band_inputs_globalstereo(const double *im0, const double *im1, 
                                           const double *offsets, int K, int64_t E, const uint32_t *conn, double *unary, double *q,
                                           double *qprim, char *err, size_t errcap) {
   const std::string what = "stereo_plane_band_inputs_globalstereo";
-  if (int rc = check_gs(what, im0, im1, H, W, C, P2, d_step, planes, offsets, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_band(what, H, W, planes, offsets, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_gs(what, im0, im1, C, P2, d_step, err, errcap)) return rc;
   const size_t n = (size_t)H * W;
-  if (int rc = check_planes(what, planes, (int64_t)n, H, err, errcap)) return rc;
+  if (int rc = check_planes(what, "", planes, (int64_t)n, H, 0, err, errcap)) return rc;
   if (int rc = check_conn(what, conn, E, n, err, errcap)) return rc;
   return guarded("stereo_plane_band_inputs_globalstereo", err, errcap, [&] {
     stereo::DevBuf<double> d0, d1, dp, doff;
-    stereo::DevBuf<uint32_t> dc;
     d0.upload(im0, n * C); d1.upload(im1, n * C); dp.upload(planes, 4 * n); doff.upload(offsets, K);
-    if (E > 0) dc.upload(conn, 2 * (size_t)E);
-    HostOutputs out(n, K, E);
-    launch_gs(d0.p, d1.p, H, W, C, P2, d_min, d_step, col_thresh, dp.p, doff.p, K, E, dc.p, out.du.p, out.dq.p, out.dqp.p, nullptr,
+    HostOutputs out(n, K, E, conn);
+    launch_gs(d0.p, d1.p, H, W, C, P2, d_min, d_step, col_thresh, dp.p, doff.p, K, E, out.dc.p, out.du.p, out.dq.p, out.dqp.p, nullptr,
               nullptr);
     out.fetch(unary, q, qprim);
   });
@@ -351,10 +290,8 @@ int stereo_plane_band_apply(const double *planes, int64_t N, const int32_t *labe
                             double *refined, char *err, size_t errcap) {
   const std::string what = "stereo_plane_band_apply";
   if (int rc = check_apply(what, planes, N, labels, offsets, K, refined, err, errcap)) return rc;
-  if (int rc = check_planes(what, planes, N, 0, err, errcap)) return rc;
-  for (int64_t i = 0; i < N; ++i)
-    if (labels[i] < 1 || labels[i] > K)
-      return fail(what + ": label " + std::to_string(labels[i]) + " at pixel " + std::to_string(i) + " is outside 1 .. " + std::to_string(K), err, errcap);
+  if (int rc = check_planes(what, "", planes, N, 0, 0, err, errcap)) return rc;
+  if (int rc = check_labels(what, labels, (size_t)N, K, err, errcap)) return rc;
   return guarded("stereo_plane_band_apply", err, errcap, [&] {
     stereo::DevBuf<double> dp, doff, out;
     stereo::DevBuf<int32_t> dl;

@@ -6,7 +6,9 @@
 // with the rescaling of stereo_trws_positions -- and apply reads the planes a labelling selects.
 //
 // The lane mapping is the band's (band.hip): a lane is one (pixel, k) or (edge, k) element in storage order, the
-// 64-bit division by K is done once per block on uniform values.  A plane is 32 contiguous bytes and moves as two
+// 64-bit division by K is done once per block on uniform values; the index, the clamp of a tap (tapped_pixel), the
+// launch sizes, slice_range(), the argument checks but the alignment, the scans of a host entry's arrays and
+// HostOutputs are in band_common.h.  A plane is 32 contiguous bytes and moves as two
 // 16-byte accesses; a wave of the gather stores 2 KiB in a row.  A pixel's point is [id / H + 1, id % H + 1], formed
 // in the kernel.
 #include <cmath>
@@ -22,9 +24,7 @@
 namespace {
 
 using stereo::fail;
-using namespace stereo::band;   // kTB, kMaxOffsets, band_index, check_offsets, check_sizes, guarded, grid_for, the sources
-
-constexpr int kMaxTap = 1 << 15;   // |dy|, |dx| below it: a tap never needs more than the int32 it is stored in
+using namespace stereo::band;   // band_common.h: the indices, the launch sizes, every check and scan, HostOutputs; the sources
 
 // one plane in registers: [a b] and [c d], each a 16-byte access
 struct Plane {
@@ -74,11 +74,7 @@ __global__ __launch_bounds__(kTB) void plane_candidates_gather_kernel(int64_t Np
       p.cd.y = p.cd.y - p.cd.x * offsets[ix.k];
     } else {
       const int j = ix.k - Ko, m = j / T, t = j - m * T;
-      const uint32_t px = (uint32_t)ix.item, x = px / (uint32_t)H, y = px - x * (uint32_t)H;
-      int64_t ys = (int64_t)y + taps[2 * t], xs = (int64_t)x + taps[2 * t + 1];
-      ys = ys < 0 ? 0 : ys > H - 1 ? H - 1 : ys;
-      xs = xs < 0 ? 0 : xs > W - 1 ? W - 1 : xs;
-      p = load_plane(sources + 4 * ((int64_t)m * Npx + xs * H + ys));
+      p = load_plane(sources + 4 * ((int64_t)m * Npx + tapped_pixel(ix.item, H, W, taps, t)));
     }
     store_plane(pcand + 4 * (first + threadIdx.x), p);
   }
@@ -187,56 +183,13 @@ __global__ __launch_bounds__(kTB) void plane_candidates_apply_kernel(int64_t Npx
 
 // ---------------------------------------------------------------- argument checks (no device call)
 
-int check_k(const std::string &what, int K, char *err, size_t errcap) {
-  if (K < 1 || K > kMaxOffsets)
-    return fail(what + ": the number of candidates K must be 1 .. " + std::to_string(kMaxOffsets) + " (got " + std::to_string(K) + ")", err, errcap);
-  return 0;
-}
-
-int check_gather(const std::string &what, const void *planes, int H, int W, const double *offsets, int Ko, const void *sources,
-                 int M, const int32_t *taps, int T, const void *pcand, char *err, size_t errcap) {
-  if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
-  if (M < 0 || T < 0) return fail(what + ": M and T must not be negative", err, errcap);
-  if (!planes || !pcand) return fail(what + ": planes and pcand must not be NULL", err, errcap);
-  if (int rc = check_offsets(what, offsets, Ko, err, errcap)) return rc;
-  const int64_t K = (int64_t)Ko + (int64_t)M * T;
-  if (K > kMaxOffsets)
-    return fail(what + ": the number of candidates K = Ko + M * T must be 1 .. " + std::to_string(kMaxOffsets) + " (got " + std::to_string(K) + ")", err, errcap);
-  if ((int64_t)M * T > 0) {
-    if (!sources || !taps) return fail(what + ": sources and taps must not be NULL when M * T > 0", err, errcap);
-    for (int t = 0; t < 2 * T; ++t)
-      if (taps[t] <= -kMaxTap || taps[t] >= kMaxTap)
-        return fail(what + ": tap " + std::to_string(t / 2) + " has |dy| or |dx| of 2^15 or more", err, errcap);
-  }
-  return 0;
-}
-
+// the part of an inputs entry's checks that does not depend on the unary source
 int check_inputs(const std::string &what, int H, int W, const void *pcand, int K, int64_t E, const void *conn, const void *unary,
                  const void *q, const void *qprim, char *err, size_t errcap) {
-  if (E < 0) return fail(what + ": E must not be negative", err, errcap);
+  if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
+  if (int rc = check_edges(what, E, conn, q, qprim, err, errcap)) return rc;
   if (!pcand || !unary) return fail(what + ": pcand and unary must not be NULL", err, errcap);
-  if (E > 0 && (!conn || !q || !qprim)) return fail(what + ": conn, q and qprim must not be NULL", err, errcap);
   return check_k(what, K, err, errcap);
-}
-
-int check_ncc(const std::string &what, const void *ncc, int H, int W, int D, int layout, const double *disparities,
-              const void *pcand, int K, int64_t E, const void *conn, const void *unary, const void *q, const void *qprim,
-              char *err, size_t errcap) {
-  if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
-  if (D < 1) return fail(what + ": D must be at least 1", err, errcap);
-  if (layout != 0 && layout != 1) return fail(what + ": layout must be 0 (H x W x D) or 1 (D x N, label fastest)", err, errcap);
-  if (!ncc || !disparities) return fail(what + ": ncc and disparities must not be NULL", err, errcap);
-  return check_inputs(what, H, W, pcand, K, E, conn, unary, q, qprim, err, errcap);
-}
-
-int check_gs(const std::string &what, const void *im0, const void *im1, int H, int W, int C, const double *P2, double d_step,
-             const void *pcand, int K, int64_t E, const void *conn, const void *unary, const void *q, const void *qprim,
-             char *err, size_t errcap) {
-  if (int rc = check_sizes(what, H, W, err, errcap)) return rc;
-  if (C < 1) return fail(what + ": C must be at least 1", err, errcap);
-  if (!im0 || !im1 || !P2) return fail(what + ": im0, im1 and P2 must not be NULL", err, errcap);
-  if (d_step == 0) return fail(what + ": d_step must not be 0 (the photo-consistency unary divides by it)", err, errcap);
-  return check_inputs(what, H, W, pcand, K, E, conn, unary, q, qprim, err, errcap);
 }
 
 int check_apply(const std::string &what, const void *pcand, int H, int W, int K, const void *labels, const void *out, char *err,
@@ -249,44 +202,6 @@ int check_apply(const std::string &what, const void *pcand, int H, int W, int K,
 // the device forms move a plane as two 16-byte accesses
 int check_aligned(const std::string &what, const char *name, const void *p, char *err, size_t errcap) {
   if (((uintptr_t)p & 15) != 0) return fail(what + ": " + name + " must be 16-byte aligned", err, errcap);
-  return 0;
-}
-
-std::string pixel_name(int64_t i, int H) {
-  return "pixel (row " + std::to_string(i % H) + ", column " + std::to_string(i / H) + ")";
-}
-
-// `name`: "planes" or "source m"
-int check_plane_map(const std::string &what, const std::string &name, const double *planes, int H, int W, char *err, size_t errcap) {
-  for (int64_t i = 0; i < (int64_t)H * W; ++i) {
-    const double *p = planes + 4 * i;
-    const bool finite = std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && std::isfinite(p[3]);
-    if (finite && p[2] != 0) continue;
-    return fail(what + (finite ? ": Infinite disparity (c == 0) in " + name + " at " : ": " + name + " is not finite at ") + pixel_name(i, H), err, errcap);
-  }
-  return 0;
-}
-
-int check_table(const std::string &what, const double *pcand, int H, int W, int K, char *err, size_t errcap) {
-  for (int64_t t = 0; t < (int64_t)H * W * K; ++t) {
-    const double *p = pcand + 4 * t;
-    const bool finite = std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && std::isfinite(p[3]);
-    if (finite && p[2] != 0) continue;
-    return fail(what + (finite ? ": Infinite disparity (c == 0) in pcand at " : ": pcand is not finite at ") + pixel_name(t / K, H) + ", label " + std::to_string(t % K + 1), err, errcap);
-  }
-  return 0;
-}
-
-int check_conn(const std::string &what, const uint32_t *conn, int64_t E, size_t n, char *err, size_t errcap) {
-  for (int64_t e = 0; e < 2 * E; ++e)
-    if (conn[e] >= n) return fail(what + ": conn names a pixel outside 0 .. H*W - 1 (edge " + std::to_string(e / 2) + ")", err, errcap);
-  return 0;
-}
-
-int check_labels(const std::string &what, const int32_t *labels, size_t n, int K, char *err, size_t errcap) {
-  for (size_t i = 0; i < n; ++i)
-    if (labels[i] < 1 || labels[i] > K)
-      return fail(what + ": label " + std::to_string(labels[i]) + " at pixel " + std::to_string(i) + " is outside 1 .. " + std::to_string(K), err, errcap);
   return 0;
 }
 
@@ -350,25 +265,6 @@ void launch_apply(const double *pcand, int H, int W, int K, const int32_t *label
   STEREO_HIP_CHECK(hipGetLastError());
 }
 
-// the table and the outputs of a host inputs entry: on the device, fetched after the launches
-struct HostProblem {
-  stereo::DevBuf<double> dcand, du, dq, dqp;
-  stereo::DevBuf<uint32_t> dc;
-  size_t nu, ne;
-  HostProblem(const double *pcand, size_t n, int K, int64_t E, const uint32_t *conn) : nu(n * K), ne((size_t)E * K) {
-    dcand.upload(pcand, 4 * nu);
-    du.alloc(nu);
-    if (E > 0) { dc.upload(conn, 2 * (size_t)E); dq.alloc(ne); dqp.alloc(ne); }
-  }
-  void fetch(double *unary, double *q, double *qprim) {
-    STEREO_HIP_CHECK(hipMemcpy(unary, du.p, nu * sizeof(double), hipMemcpyDeviceToHost));
-    if (ne > 0) {
-      STEREO_HIP_CHECK(hipMemcpy(q, dq.p, ne * sizeof(double), hipMemcpyDeviceToHost));
-      STEREO_HIP_CHECK(hipMemcpy(qprim, dqp.p, ne * sizeof(double), hipMemcpyDeviceToHost));
-    }
-  }
-};
-
 }  // namespace
 
 extern "C" {
@@ -377,7 +273,7 @@ int stereo_plane_candidates_gather_device(const double *planes, int H, int W, co
                                           int Ko, const double *sources, int M, const int32_t *taps, const int32_t *d_taps,
                                           int T, double *pcand, int32_t *bad, void *stream, char *err, size_t errcap) {
   const std::string what = "stereo_plane_candidates_gather_device";
-  if (int rc = check_gather(what, planes, H, W, offsets, Ko, sources, M, taps, T, pcand, err, errcap)) return rc;
+  if (int rc = check_gather(what, "planes", "pcand", planes, H, W, offsets, Ko, sources, M, taps, T, pcand, err, errcap)) return rc;
   if (!d_offsets) return fail(what + ": d_offsets must not be NULL", err, errcap);
   const bool taken = (int64_t)M * T > 0;
   if (taken && !d_taps) return fail(what + ": d_taps must not be NULL when M * T > 0", err, errcap);
@@ -394,7 +290,8 @@ int stereo_plane_candidates_inputs_ncc_device(const double *ncc, int H, int W, i
                                               int64_t E, const uint32_t *conn, double *unary, double *q, double *qprim,
                                               int32_t *bad, void *stream, char *err, size_t errcap) {
   const std::string what = "stereo_plane_candidates_inputs_ncc_device";
-  if (int rc = check_ncc(what, ncc, H, W, D, layout, disparities, pcand, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_inputs(what, H, W, pcand, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_volume(what, ncc, D, layout, disparities, err, errcap)) return rc;
   if (!d_disparities) return fail(what + ": d_disparities must not be NULL", err, errcap);
   if (int rc = check_aligned(what, "pcand", pcand, err, errcap)) return rc;
   return guarded("stereo_plane_candidates_inputs_ncc_device", err, errcap, [&] {
@@ -409,7 +306,8 @@ int stereo_plane_candidates_inputs_globalstereo_device(const double *im0, const 
                                                        double *unary, double *q, double *qprim, int32_t *bad, void *stream,
                                                        char *err, size_t errcap) {
   const std::string what = "stereo_plane_candidates_inputs_globalstereo_device";
-  if (int rc = check_gs(what, im0, im1, H, W, C, P2, d_step, pcand, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_inputs(what, H, W, pcand, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_gs(what, im0, im1, C, P2, d_step, err, errcap)) return rc;
   if (int rc = check_aligned(what, "pcand", pcand, err, errcap)) return rc;
   return guarded("stereo_plane_candidates_inputs_globalstereo_device", err, errcap, [&] {
     launch_gs(im0, im1, H, W, C, P2, d_min, d_step, col_thresh, pcand, K, E, conn, unary, q, qprim, bad, (hipStream_t)stream);
@@ -429,12 +327,12 @@ int stereo_plane_candidates_apply_device(const double *pcand, int H, int W, int 
 int stereo_plane_candidates_gather(const double *planes, int H, int W, const double *offsets, int Ko, const double *sources,
                                    int M, const int32_t *taps, int T, double *pcand, char *err, size_t errcap) {
   const std::string what = "stereo_plane_candidates_gather";
-  if (int rc = check_gather(what, planes, H, W, offsets, Ko, sources, M, taps, T, pcand, err, errcap)) return rc;
-  if (int rc = check_plane_map(what, "planes", planes, H, W, err, errcap)) return rc;
+  if (int rc = check_gather(what, "planes", "pcand", planes, H, W, offsets, Ko, sources, M, taps, T, pcand, err, errcap)) return rc;
   const size_t n = (size_t)H * W;
+  if (int rc = check_planes(what, "planes", planes, (int64_t)n, H, 0, err, errcap)) return rc;
   const bool taken = (int64_t)M * T > 0;
   for (int m = 0; taken && m < M; ++m)
-    if (int rc = check_plane_map(what, "source " + std::to_string(m), sources + 4 * (size_t)m * n, H, W, err, errcap)) return rc;
+    if (int rc = check_planes(what, "source " + std::to_string(m), sources + 4 * (size_t)m * n, (int64_t)n, H, 0, err, errcap)) return rc;
   const size_t K = (size_t)Ko + (size_t)M * T;
   return guarded("stereo_plane_candidates_gather", err, errcap, [&] {
     stereo::DevBuf<double> dp, doff, ds, dc;
@@ -450,17 +348,18 @@ int stereo_plane_candidates_inputs_ncc(const double *ncc, int H, int W, int D, i
                                        double unary_weight, const double *pcand, int K, int64_t E, const uint32_t *conn,
                                        double *unary, double *q, double *qprim, char *err, size_t errcap) {
   const std::string what = "stereo_plane_candidates_inputs_ncc";
-  if (int rc = check_ncc(what, ncc, H, W, D, layout, disparities, pcand, K, E, conn, unary, q, qprim, err, errcap)) return rc;
-  if (int rc = check_table(what, pcand, H, W, K, err, errcap)) return rc;
+  if (int rc = check_inputs(what, H, W, pcand, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_volume(what, ncc, D, layout, disparities, err, errcap)) return rc;
   const size_t n = (size_t)H * W;
+  if (int rc = check_planes(what, "pcand", pcand, (int64_t)n, H, K, err, errcap)) return rc;
   if (int rc = check_conn(what, conn, E, n, err, errcap)) return rc;
   return guarded("stereo_plane_candidates_inputs_ncc", err, errcap, [&] {
-    stereo::DevBuf<double> dn, dd;
-    dn.upload(ncc, n * D); dd.upload(disparities, D);
-    HostProblem prob(pcand, n, K, E, conn);
-    launch_ncc(dn.p, H, W, D, layout, disparities, dd.p, unary_weight, prob.dcand.p, K, E, prob.dc.p, prob.du.p, prob.dq.p,
-               prob.dqp.p, nullptr, nullptr);
-    prob.fetch(unary, q, qprim);
+    stereo::DevBuf<double> dn, dd, dcand;
+    dn.upload(ncc, n * D); dd.upload(disparities, D); dcand.upload(pcand, 4 * n * K);
+    HostOutputs out(n, K, E, conn);
+    launch_ncc(dn.p, H, W, D, layout, disparities, dd.p, unary_weight, dcand.p, K, E, out.dc.p, out.du.p, out.dq.p, out.dqp.p,
+               nullptr, nullptr);
+    out.fetch(unary, q, qprim);
   });
 }
 
@@ -469,17 +368,18 @@ int stereo_plane_candidates_inputs_globalstereo(const double *im0, const double 
                                                 int64_t E, const uint32_t *conn, double *unary, double *q, double *qprim,
                                                 char *err, size_t errcap) {
   const std::string what = "stereo_plane_candidates_inputs_globalstereo";
-  if (int rc = check_gs(what, im0, im1, H, W, C, P2, d_step, pcand, K, E, conn, unary, q, qprim, err, errcap)) return rc;
-  if (int rc = check_table(what, pcand, H, W, K, err, errcap)) return rc;
+  if (int rc = check_inputs(what, H, W, pcand, K, E, conn, unary, q, qprim, err, errcap)) return rc;
+  if (int rc = check_gs(what, im0, im1, C, P2, d_step, err, errcap)) return rc;
   const size_t n = (size_t)H * W;
+  if (int rc = check_planes(what, "pcand", pcand, (int64_t)n, H, K, err, errcap)) return rc;
   if (int rc = check_conn(what, conn, E, n, err, errcap)) return rc;
   return guarded("stereo_plane_candidates_inputs_globalstereo", err, errcap, [&] {
-    stereo::DevBuf<double> d0, d1;
-    d0.upload(im0, n * C); d1.upload(im1, n * C);
-    HostProblem prob(pcand, n, K, E, conn);
-    launch_gs(d0.p, d1.p, H, W, C, P2, d_min, d_step, col_thresh, prob.dcand.p, K, E, prob.dc.p, prob.du.p, prob.dq.p, prob.dqp.p,
-              nullptr, nullptr);
-    prob.fetch(unary, q, qprim);
+    stereo::DevBuf<double> d0, d1, dcand;
+    d0.upload(im0, n * C); d1.upload(im1, n * C); dcand.upload(pcand, 4 * n * K);
+    HostOutputs out(n, K, E, conn);
+    launch_gs(d0.p, d1.p, H, W, C, P2, d_min, d_step, col_thresh, dcand.p, K, E, out.dc.p, out.du.p, out.dq.p, out.dqp.p, nullptr,
+              nullptr);
+    out.fetch(unary, q, qprim);
   });
 }
 
@@ -487,8 +387,8 @@ int stereo_plane_candidates_apply(const double *pcand, int H, int W, int K, cons
                                   size_t errcap) {
   const std::string what = "stereo_plane_candidates_apply";
   if (int rc = check_apply(what, pcand, H, W, K, labels, out, err, errcap)) return rc;
-  if (int rc = check_table(what, pcand, H, W, K, err, errcap)) return rc;
   const size_t n = (size_t)H * W;
+  if (int rc = check_planes(what, "pcand", pcand, (int64_t)n, H, K, err, errcap)) return rc;
   if (int rc = check_labels(what, labels, n, K, err, errcap)) return rc;
   return guarded("stereo_plane_candidates_apply", err, errcap, [&] {
     stereo::DevBuf<double> dcand, dout;

@@ -2,7 +2,8 @@
 // per-pixel plane sets): the NCC sampler of dispmap_ncc (ncc_sample.h) and the photo-consistency term of
 // dispmap_globalstereo (gs_sample.h), one copy of each, behind one interface.  begin(): what the block prepares
 // once (the NCC source copies the D slice positions into LDS, for the reason band.hip gives); at(): the unary of
-// pixel px, whose point is (x, y), for a plane whose disparity there is `disp`.
+// pixel px, whose point is (x, y), for a plane whose disparity there is `disp`.  What the host works out before a
+// launch with the NCC source (slice_range(), kMaxStagedSlices) is in band_common.h.
 #pragma once
 #include <cstdint>
 
@@ -13,7 +14,6 @@
 namespace stereo {
 namespace band {
 
-constexpr int kMaxStagedSlices = 4096;   // 32 KiB of LDS; beyond it the kernel reads the slices where they are
 template <bool kStageSlices>
 struct NccSource {
   const double *ncc;
@@ -41,22 +41,6 @@ struct GsSource {
     return stereo::gs_unary_at(im0, im1, H, W, C, P2, d_min, d_step, col_thresh, px, x, y, disp);
   }
 };
-
-// what the host reads off the slice positions before a launch with the NCC source
-struct SliceRange {
-  double dmin, dmax;
-  int ascending;
-};
-inline SliceRange slice_range(const double *disparities, int D) {
-  double dmin = disparities[0], dmax = disparities[0];
-  bool ascending = disparities[0] == disparities[0];
-  for (int i = 1; i < D; ++i) {
-    dmin = disparities[i] < dmin ? disparities[i] : dmin;
-    dmax = disparities[i] > dmax ? disparities[i] : dmax;
-    ascending = ascending && disparities[i] > disparities[i - 1];
-  }
-  return {dmin, dmax, ascending ? 1 : 0};
-}
 
 }  // namespace band
 }  // namespace stereo

@@ -11,6 +11,7 @@ Host forms take NumPy arrays in MATLAB shapes (planes 4 x N, conn 2 x E zero bas
 the current device: ``planes`` and ``refined`` are contiguous float64 tensors of 4 N elements in the storage order of
 4 x N column major (shape (N, 4)), ``unary``, ``q`` and ``qprim`` flat float64 tensors in storage order, ``conn`` a flat
 int32 tensor of 2 E entries, ``labels`` a flat int32 tensor.  ``offsets`` are in the planes' own disparity units.
+The helpers of the wrappers, the level loop and the protocol PlaneBandProblem offers it are band.py's.
 """
 import ctypes as C
 
@@ -20,9 +21,9 @@ from . import _lib
 from . import carry as carry_mod
 from . import terms as T
 from ._lib import StereoHipError
-from .band import _conn, _flat, _vec, _volume, check_levels, to_device_vector
+from .band import (LevelsResult, _bad, _conn, _device_labels, _device_vectors, _edges, _flat, _out, _raise_bad, _vec, _volume,
+                   _vp, bind_inputs, check_levels, run_levels, to_device_vector)
 from .consistency import _p, _stream
-from .trws import TrwsPlan
 
 
 class NccSource:
@@ -158,16 +159,6 @@ def plane_band_apply(planes, labels, offsets):
 
 # ---------------------------------------------------------------- device forms
 
-def _device_offsets(offsets, d_offsets, stream):
-    import torch
-    if d_offsets is None:
-        d_offsets = to_device_vector(offsets)
-        if stream is not None:
-            torch.cuda.current_stream().synchronize()     # the copy ran on torch's current stream, the kernels will not
-        return d_offsets
-    return _flat(d_offsets, "d_offsets", torch.float64, offsets.shape[0])
-
-
 def plane_band_inputs_device(source, planes, offsets, conn, d_min=0.0, d_step=0.0, unary=None, q=None, qprim=None, bad=None,
                              stream=None, d_offsets=None, check=True):
     """stereo_plane_band_inputs_*_device on torch tensors (module docstring), launched on `stream` (a torch stream or a
@@ -183,36 +174,27 @@ def plane_band_inputs_device(source, planes, offsets, conn, d_min=0.0, d_step=0.
     planes = _flat(planes, "planes", torch.float64, 4 * N)
     offsets = _vec(offsets, "offsets")
     K = offsets.shape[0]
-    conn = _flat(conn, "conn", torch.int32)
-    if conn.numel() % 2:
-        raise StereoHipError("conn must hold 2 E entries")
-    E = conn.numel() // 2
+    conn, E = _edges(conn)
     dev = planes.device
     fresh = source.device()
     if stream is not None:
         torch.cuda.current_stream().synchronize()         # (the source's copies ran on torch's current stream)
-    d_offsets = _device_offsets(offsets, d_offsets, stream)
-    unary = torch.empty(max(K, 0) * N, dtype=torch.float64, device=dev) if unary is None else _flat(unary, "unary", torch.float64, K * N)
-    q = torch.empty(max(K, 0) * E, dtype=torch.float64, device=dev) if q is None else _flat(q, "q", torch.float64, K * E)
-    qprim = torch.empty(max(K, 0) * E, dtype=torch.float64, device=dev) if qprim is None else _flat(qprim, "qprim", torch.float64, K * E)
-    bad = torch.zeros(1, dtype=torch.int32, device=dev) if bad is None else _flat(bad, "bad", torch.int32, 1)
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    d_offsets, = _device_vectors(stream, (offsets, d_offsets, "d_offsets"))
+    unary, q, qprim = _out(unary, "unary", K * N, dev), _out(q, "q", K * E, dev), _out(qprim, "qprim", K * E, dev)
+    bad = _bad(bad, dev)
     err = _lib.errbuf()
-    tail = (vp(planes), _p(offsets), vp(d_offsets), C.c_int(K), C.c_int64(E), vp(conn), vp(unary), vp(q), vp(qprim), vp(bad),
+    tail = (_vp(planes), _p(offsets), _vp(d_offsets), C.c_int(K), C.c_int64(E), _vp(conn), _vp(unary), _vp(q), _vp(qprim), _vp(bad),
             C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
     if source.kind == "ncc":
-        rc = _lib.lib().stereo_plane_band_inputs_ncc_device(vp(fresh.d_vol), C.c_int(H), C.c_int(W), C.c_int(source.D),
+        rc = _lib.lib().stereo_plane_band_inputs_ncc_device(_vp(fresh.d_vol), C.c_int(H), C.c_int(W), C.c_int(source.D),
                                                             C.c_int(source.layout), _p(source.disparities),
-                                                            vp(fresh.d_disparities), C.c_double(source.unary_weight), *tail)
+                                                            _vp(fresh.d_disparities), C.c_double(source.unary_weight), *tail)
     else:
-        rc = _lib.lib().stereo_plane_band_inputs_globalstereo_device(vp(fresh.d_im0), vp(fresh.d_im1), C.c_int(H), C.c_int(W),
+        rc = _lib.lib().stereo_plane_band_inputs_globalstereo_device(_vp(fresh.d_im0), _vp(fresh.d_im1), C.c_int(H), C.c_int(W),
                                                                      C.c_int(source.C), _p(source.P2), C.c_double(d_min),
                                                                      C.c_double(d_step), C.c_double(source.col_thresh), *tail)
     _lib.check(rc, err)
-    if check:
-        n = int(bad.item())
-        if n:
-            raise StereoHipError("plane_band_inputs_device: %d plane(s) with c == 0 or a component that is not finite" % n)
+    _raise_bad(bad, check, "plane_band_inputs_device: %d plane(s) with c == 0 or a component that is not finite")
     return unary, q, qprim, bad
 
 
@@ -227,37 +209,31 @@ def plane_band_apply_device(planes, labels, offsets, refined=None, bad=None, str
     offsets = _vec(offsets, "offsets")
     K = offsets.shape[0]
     labels = _flat(labels, "labels", torch.int32, N)
-    d_offsets = _device_offsets(offsets, d_offsets, stream)
-    refined = torch.empty((N, 4), dtype=torch.float64, device=planes.device) if refined is None else _flat(refined, "refined", torch.float64, 4 * N)
-    bad = torch.zeros(1, dtype=torch.int32, device=planes.device) if bad is None else _flat(bad, "bad", torch.int32, 1)
-    vp = lambda t: C.c_void_p(t.data_ptr())
+    d_offsets, = _device_vectors(stream, (offsets, d_offsets, "d_offsets"))
+    refined, bad = _out(refined, "refined", 4 * N, planes.device, new=(N, 4)), _bad(bad, planes.device)
     err = _lib.errbuf()
-    rc = _lib.lib().stereo_plane_band_apply_device(vp(planes), C.c_int64(N), vp(labels), _p(offsets), vp(d_offsets), C.c_int(K),
-                                                   vp(refined), vp(bad), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    rc = _lib.lib().stereo_plane_band_apply_device(_vp(planes), C.c_int64(N), _vp(labels), _p(offsets), _vp(d_offsets), C.c_int(K),
+                                                   _vp(refined), _vp(bad), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
     _lib.check(rc, err)
-    if check:
-        n = int(bad.item())
-        if n:
-            raise StereoHipError("plane_band_apply_device: %d pixel(s) with a label outside 1 .. %d or a plane without a disparity" % (n, K))
+    _raise_bad(bad, check, "plane_band_apply_device: %d pixel(s) with a label outside 1 .. %d or a plane without a disparity", K)
     return refined, bad
 
 
 # ---------------------------------------------------------------- levels
 
-class PlaneBandResult:
-    """refine_plane_band's result: `planes` (4 x N, the last level's refined planes), `plane_maps` (one per level) and per
-    level `energy`, `lower_bound`, `iterations`, `labels` (N, one based), `paths` (TrwsPlan.path()) and `carried` (the
-    level started from the previous level's messages)."""
+class PlaneBandResult(LevelsResult):
+    """refine_plane_band's result: band.LevelsResult's lists, of which `maps` is known as `plane_maps` here (4 x N per
+    level), and `planes` (4 x N, the last level's refined planes)."""
 
     def __init__(self):
-        self.planes = None
-        self.plane_maps, self.labels = [], []
-        self.energy, self.lower_bound, self.iterations, self.paths, self.carried = [], [], [], [], []
+        super().__init__()
+        self.planes, self.plane_maps = None, self.maps
 
 
 class PlaneBandProblem:
     """One object's plane-band problems on the device: the source's data, the connectivity and the smoothness weights go
-    up once; build() makes a level's inputs from the current planes and binds them to `plan`, apply() moves the planes on."""
+    up once; build() makes a level's inputs from the current planes and binds them to `plan`, apply() moves the planes on.
+    (The protocol the level loop drives it by: band.run_levels.)"""
 
     def __init__(self, source, planes, conn, alphas=None, d_min=0.0, d_step=0.0):
         import torch
@@ -284,11 +260,16 @@ class PlaneBandProblem:
             self.d_receiver = torch.from_numpy(carry_mod.receivers(self.N, self.conn, 1)).cuda()
         return self.d_receiver
 
-    def carry_from(self, plan, labels):
-        """The carry.Carry from the level built last (solved by `plan` with `labels`, one based) into the next one; to
-        be called before the next build.  A plane moved along the disparity axis moves its own pixel's disparity by
-        exactly that offset, so the new level's offset 0 at pixel r lies at offsets[labels_r - 1] on the old axis.  None
-        where the plan's state cannot be carried."""
+    @staticmethod
+    def labels_of(level):
+        """K of the level `level` (here: a vector of offsets), before it is built."""
+        return level.shape[0]
+
+    def leave(self, plan, labels):
+        """What the level built last (solved by `plan` with `labels`, one based) leaves for the next one: the carry.Carry
+        into it, whatever its offsets; to be called before the next build.  A plane moved along the disparity axis moves
+        its own pixel's disparity by exactly that offset, so the new level's offset 0 at pixel r lies at
+        offsets[labels_r - 1] on the old axis.  None where the plan's state cannot be carried."""
         import torch
         d_m = carry_mod.save_messages(plan, self.N)
         if d_m is None:
@@ -296,25 +277,24 @@ class PlaneBandProblem:
         index = torch.from_numpy(np.asarray(labels).reshape(-1).astype(np.int64) - 1).cuda()
         return carry_mod.Carry(d_m, self.offsets, self.d_offsets[index].contiguous())
 
+    def carry_from(self, left, scales=False):
+        """The Carry into the next build from what leave() gave: that itself (it does not depend on the planes)."""
+        return left
+
     def build(self, offsets, plan, tol, carry=None):
         """The inputs of the level `offsets` around the current planes, bound to `plan`.  carry: a carry.Carry of the
         previous level; the plan then starts from the transferred messages, not from zero."""
-        import torch
         self.offsets = _vec(offsets, "offsets")
         self.d_offsets = to_device_vector(self.offsets)
         self.d_unary, self.d_q, self.d_qprim, _ = plane_band_inputs_device(
             self.source, self.d_planes, self.offsets, self.d_conn, self.d_min, self.d_step, d_offsets=self.d_offsets)
-        torch.cuda.current_stream().synchronize()
-        plan.bind_device(self.d_unary.data_ptr(), self.d_alphas.data_ptr(), tol, d_q=self.d_q.data_ptr(),
-                         d_qprim=self.d_qprim.data_ptr(), keepalive=[self.d_unary, self.d_q, self.d_qprim, self.d_alphas])
+        bind_inputs(self, plan, tol)
         if carry is not None:
             carry_mod.load_carried(plan, carry, self.offsets, self.receiver(), self.N, self.d_offsets)
 
     def apply(self, labels):
         """The planes moved by the labels of the level built last -> the new planes on the host, 4 x N."""
-        import torch
-        lab = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)).cuda()
-        self.d_planes, _ = plane_band_apply_device(self.d_planes, lab, self.offsets, d_offsets=self.d_offsets)
+        self.d_planes, _ = plane_band_apply_device(self.d_planes, _device_labels(labels), self.offsets, d_offsets=self.d_offsets)
         return np.asfortranarray(self.d_planes.cpu().numpy().T)
 
 
@@ -333,24 +313,6 @@ def refine_plane_band(source, planes, kernel, tol, levels, maxiter, max_relgap, 
     conn = T.construct_neighborhood(source.H, source.W) if conn is None else conn
     prob = PlaneBandProblem(source, planes, conn, alphas, d_min, d_step)
     out = PlaneBandResult()
-    plans = {}
-    previous = None
-    try:
-        for offsets in levels:
-            K = offsets.shape[0]
-            if K not in plans:
-                plans[K] = TrwsPlan(int(kernel), K, prob.N, prob.conn)
-            plan = plans[K]
-            prob.build(offsets, plan, tol, carry=previous)
-            out.carried.append(previous is not None)
-            plan.iterate(maxiter, max_relgap)
-            labels, en, lb, it = plan.result()
-            out.paths.append(plan.path())
-            out.labels.append(labels); out.energy.append(en); out.lower_bound.append(lb); out.iterations.append(it)
-            previous = prob.carry_from(plan, labels) if carry else None
-            out.plane_maps.append(prob.apply(labels))
-        out.planes = out.plane_maps[-1]
-    finally:
-        for plan in plans.values():
-            plan.close()
+    run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, carry)
+    out.planes = out.plane_maps[-1]
     return out

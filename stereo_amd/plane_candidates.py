@@ -15,21 +15,22 @@ labels.
 Host forms take NumPy arrays in MATLAB shapes (planes 4 x N, a table 4 x K x N, conn 2 x E zero based).  Device forms
 take torch tensors of the current device, as in plane_band.py: ``planes`` and ``out`` are contiguous float64 tensors of
 4 N elements (shape (N, 4)), M sources one contiguous (M, N, 4) tensor, a table a flat float64 tensor of 4 K N elements.
+The helpers of the wrappers and the level loop are band.py's, the checks of a level candidates.py's.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from . import band
+from . import candidates
 from . import plane_band
 from . import terms as T
 from ._lib import StereoHipError
-from .band import _conn, _flat, _vec, to_device_vector
-from .candidates import _taps, taps_to_device
+from .band import (_bad, _conn, _device_labels, _edges, _flat, _out, _raise_bad, _vec, _vp, bind_inputs, run_levels,
+                   to_device_vector)
+from .candidates import _device_vectors_of_gather, _taps
 from .consistency import _map, _p, _stream
 from .plane_band import PlaneBandProblem, PlaneBandResult, _planes, _rescale, _source
-from .trws import TrwsPlan
 
 
 class OrOwn:
@@ -143,10 +144,6 @@ def plane_candidates_apply(pcand, labels, shape):
 
 # ---------------------------------------------------------------- device forms
 
-def _vp(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-
-
 def _device_table(pcand, N):
     import torch
     pcand = _flat(pcand, "pcand", torch.float64)
@@ -176,26 +173,15 @@ def gather_device(planes, offsets, shape, sources=None, taps=(), pcand=None, bad
         sources = _flat(sources, "sources", torch.float64, M * 4 * N)
     K = Ko + M * Tn
     dev = planes.device
-    made_here = d_offsets is None or (d_taps is None and M * Tn)
-    d_offsets = to_device_vector(offsets) if d_offsets is None else _flat(d_offsets, "d_offsets", torch.float64, Ko)
-    if M * Tn:
-        d_taps = taps_to_device(taps) if d_taps is None else _flat(d_taps, "d_taps", torch.int32, 2 * Tn)
-    if made_here and stream is not None:
-        torch.cuda.current_stream().synchronize()     # the copies ran on torch's current stream, the kernel will not
-    pcand = (torch.empty(4 * max(K, 1) * N, dtype=torch.float64, device=dev) if pcand is None
-             else _flat(pcand, "pcand", torch.float64, 4 * K * N))
-    bad = torch.zeros(1, dtype=torch.int32, device=dev) if bad is None else _flat(bad, "bad", torch.int32, 1)
+    d_offsets, d_taps = _device_vectors_of_gather(stream, offsets, d_offsets, taps, d_taps, M * Tn)
+    pcand, bad = _out(pcand, "pcand", 4 * K * N, dev, new=4 * max(K, 1) * N), _bad(bad, dev)
     err = _lib.errbuf()
     rc = _lib.lib().stereo_plane_candidates_gather_device(
         _vp(planes), C.c_int(H), C.c_int(W), _p(offsets), _vp(d_offsets), C.c_int(Ko), _vp(sources) if M * Tn else None,
         C.c_int(M), _p(taps, C.c_int32) if M * Tn else None, _vp(d_taps) if M * Tn else None, C.c_int(Tn), _vp(pcand),
         _vp(bad), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
     _lib.check(rc, err)
-    if check:
-        n = int(bad.item())
-        if n:
-            raise StereoHipError("gather_device: the own plane or a source's plane has c == 0 or a component that is not "
-                                 "finite at %d pixel(s)" % n)
+    _raise_bad(bad, check, "gather_device: the own plane or a source's plane has c == 0 or a component that is not finite at %d pixel(s)")
     return pcand, bad
 
 
@@ -212,18 +198,13 @@ def plane_candidates_inputs_device(source, pcand, shape, conn, d_min=0.0, d_step
     _check_source_shape(source, H, W, "plane_candidates_inputs_device")
     N = H * W
     pcand, K = _device_table(pcand, N)
-    conn = _flat(conn, "conn", torch.int32)
-    if conn.numel() % 2:
-        raise StereoHipError("conn must hold 2 E entries")
-    E = conn.numel() // 2
+    conn, E = _edges(conn)
     dev = pcand.device
     fresh = source.device()
     if stream is not None:
         torch.cuda.current_stream().synchronize()         # (the source's copies ran on torch's current stream)
-    unary = torch.empty(K * N, dtype=torch.float64, device=dev) if unary is None else _flat(unary, "unary", torch.float64, K * N)
-    q = torch.empty(K * E, dtype=torch.float64, device=dev) if q is None else _flat(q, "q", torch.float64, K * E)
-    qprim = torch.empty(K * E, dtype=torch.float64, device=dev) if qprim is None else _flat(qprim, "qprim", torch.float64, K * E)
-    bad = torch.zeros(1, dtype=torch.int32, device=dev) if bad is None else _flat(bad, "bad", torch.int32, 1)
+    unary, q, qprim = _out(unary, "unary", K * N, dev), _out(q, "q", K * E, dev), _out(qprim, "qprim", K * E, dev)
+    bad = _bad(bad, dev)
     err = _lib.errbuf()
     tail = (_vp(pcand), C.c_int(K), C.c_int64(E), _vp(conn), _vp(unary), _vp(q), _vp(qprim), _vp(bad),
             C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
@@ -236,11 +217,7 @@ def plane_candidates_inputs_device(source, pcand, shape, conn, d_min=0.0, d_step
             _vp(fresh.d_im0), _vp(fresh.d_im1), C.c_int(H), C.c_int(W), C.c_int(source.C), _p(source.P2), C.c_double(d_min),
             C.c_double(d_step), C.c_double(source.col_thresh), *tail)
     _lib.check(rc, err)
-    if check:
-        n = int(bad.item())
-        if n:
-            raise StereoHipError("plane_candidates_inputs_device: a candidate has c == 0 or a component that is not finite "
-                                 "at %d pixel(s)" % n)
+    _raise_bad(bad, check, "plane_candidates_inputs_device: a candidate has c == 0 or a component that is not finite at %d pixel(s)")
     return unary, q, qprim, bad
 
 
@@ -252,74 +229,51 @@ def plane_candidates_apply_device(pcand, labels, shape, out=None, bad=None, stre
     N = H * W
     pcand, K = _device_table(pcand, N)
     labels = _flat(labels, "labels", torch.int32, N)
-    out = torch.empty((N, 4), dtype=torch.float64, device=pcand.device) if out is None else _flat(out, "out", torch.float64, 4 * N)
-    bad = torch.zeros(1, dtype=torch.int32, device=pcand.device) if bad is None else _flat(bad, "bad", torch.int32, 1)
+    out, bad = _out(out, "out", 4 * N, pcand.device, new=(N, 4)), _bad(bad, pcand.device)
     err = _lib.errbuf()
     rc = _lib.lib().stereo_plane_candidates_apply_device(_vp(pcand), C.c_int(H), C.c_int(W), C.c_int(K), _vp(labels), _vp(out),
                                                          _vp(bad), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
     _lib.check(rc, err)
-    if check:
-        n = int(bad.item())
-        if n:
-            raise StereoHipError("plane_candidates_apply_device: %d label(s) outside 1 .. %d" % (n, K))
+    _raise_bad(bad, check, "plane_candidates_apply_device: %d label(s) outside 1 .. %d", K)
     return out, bad
 
 
 # ---------------------------------------------------------------- levels
 
+def _check_source(s):
+    if isinstance(s, str):
+        if s != "base":
+            raise StereoHipError("plane candidates: a source is 'base' or 4 x N planes (got %r)" % (s,))
+    elif not isinstance(s, OrOwn) and (np.ndim(s) != 2 or np.shape(s)[0] != 4):
+        raise StereoHipError("plane candidates: a source is 'base' or 4 x N planes")
+
+
+_HOW = dict(check_source=_check_source, prefix="plane candidates", single=(str, np.ndarray, OrOwn))
+
+
 def check_level(level):
     """A plane-candidate level as dict(offsets: float64 vector, taps: T x 2 int32, sources: list of 'base' / 4 x N plane
-    arrays / OrOwn), checked as far as it can be without the image: the band's rules for the offsets, whole-number taps
-    below 2^15, K = Ko + M T within 1 .. max_offsets()."""
-    if not isinstance(level, dict) or set(level) - {"offsets", "taps", "sources"}:
-        raise StereoHipError("a plane-candidate level must be dict(offsets=, taps=, sources=) (got %r)" % (level,))
-    offsets = _vec(level.get("offsets", [0.0]), "a level's offsets")
-    if offsets.shape[0] < 1 or not (np.isfinite(offsets).all() and (np.diff(offsets) > 0).all() and (offsets == 0.0).any()):
-        raise StereoHipError("plane candidates: a vector of offsets must be finite, strictly ascending and contain 0 (got %s)"
-                             % (offsets.tolist(),))
-    taps = _taps(level.get("taps", ()))
-    if taps.size and np.abs(taps).max() >= 1 << 15:
-        raise StereoHipError("plane candidates: a tap's |dy| and |dx| must be below 2^15")
-    sources = level.get("sources", ())
-    if isinstance(sources, (str, np.ndarray, OrOwn)):
-        sources = [sources]
-    sources = list(sources)
-    for s in sources:
-        if isinstance(s, str):
-            if s != "base":
-                raise StereoHipError("plane candidates: a source is 'base' or 4 x N planes (got %r)" % (s,))
-        elif not isinstance(s, OrOwn) and (np.ndim(s) != 2 or np.shape(s)[0] != 4):
-            raise StereoHipError("plane candidates: a source is 'base' or 4 x N planes")
-    K = offsets.shape[0] + len(sources) * taps.shape[0]
-    if K > band.max_offsets():
-        raise StereoHipError("plane candidates: K = Ko + M * T must be 1 .. %d (got %d)" % (band.max_offsets(), K))
-    return dict(offsets=offsets, taps=taps, sources=sources)
+    arrays / OrOwn), checked as candidates.check_level checks a candidate level."""
+    return candidates.check_level(level, **_HOW)
 
 
 def check_levels(levels):
     """`levels` as a list of checked plane-candidate levels (check_level); at least one."""
-    if isinstance(levels, dict):
-        levels = [levels]
-    levels = [check_level(l) for l in levels]
-    if not levels:
-        raise StereoHipError("refine_plane_candidates: levels must hold at least one plane-candidate level")
-    return levels
+    return candidates.check_levels(levels, **_HOW)
 
 
 class PlaneCandidateProblem(PlaneBandProblem):
     """One object's plane-candidate problems on the device, with PlaneBandProblem's interface: the source's data, the
     connectivity and the smoothness weights go up once; build() gathers a level's table around the current planes, makes
     its inputs and binds them to `plan`; apply() reads the table and moves the planes on.  A level's labels have no
-    common offset grid, so it neither takes nor leaves carried messages: carry_from() gives None."""
+    common offset grid, so it neither takes nor leaves carried messages: leave() and carry_from() give None."""
 
     def __init__(self, source, planes, conn, alphas=None, d_min=0.0, d_step=0.0):
         super().__init__(source, planes, conn, alphas, d_min, d_step)
         self.shape = (self.source.H, self.source.W)
         self.d_pcand = None
 
-    @staticmethod
-    def labels_of(level):
-        return level["offsets"].shape[0] + len(level["sources"]) * level["taps"].shape[0]
+    labels_of = staticmethod(candidates.labels_of)
 
     def _source_tensor(self, level):
         import torch
@@ -339,7 +293,6 @@ class PlaneCandidateProblem(PlaneBandProblem):
     def build(self, level, plan, tol, carry=None):
         """The inputs of the plane-candidate level `level` (check_level's dict) around the current planes, bound to
         `plan`.  carry must be None."""
-        import torch
         if carry is not None:
             raise StereoHipError("plane candidates: a plane-candidate level does not take carried messages")
         self.offsets = level["offsets"]
@@ -348,18 +301,17 @@ class PlaneCandidateProblem(PlaneBandProblem):
                                         d_offsets=self.d_offsets)
         self.d_unary, self.d_q, self.d_qprim, _ = plane_candidates_inputs_device(
             self.source, self.d_pcand, self.shape, self.d_conn, self.d_min, self.d_step)
-        torch.cuda.current_stream().synchronize()
-        plan.bind_device(self.d_unary.data_ptr(), self.d_alphas.data_ptr(), tol, d_q=self.d_q.data_ptr(),
-                         d_qprim=self.d_qprim.data_ptr(), keepalive=[self.d_unary, self.d_q, self.d_qprim, self.d_alphas])
+        bind_inputs(self, plan, tol)
 
-    def carry_from(self, plan, labels):
+    def leave(self, plan, labels):
+        return None
+
+    def carry_from(self, left, scales=False):
         return None
 
     def apply(self, labels):
         """The planes the labels of the level built last select -> the new planes on the host, 4 x N."""
-        import torch
-        lab = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)).cuda()
-        self.d_planes, _ = plane_candidates_apply_device(self.d_pcand, lab, self.shape)
+        self.d_planes, _ = plane_candidates_apply_device(self.d_pcand, _device_labels(labels), self.shape)
         return np.asfortranarray(self.d_planes.cpu().numpy().T)
 
 
@@ -378,22 +330,6 @@ def refine_plane_candidates(source, planes, kernel, tol, levels, maxiter, max_re
     conn = T.construct_neighborhood(source.H, source.W) if conn is None else conn
     prob = PlaneCandidateProblem(source, planes, conn, alphas, d_min, d_step)
     out = PlaneBandResult()
-    plans = {}
-    try:
-        for level in levels:
-            K = prob.labels_of(level)
-            if K not in plans:
-                plans[K] = TrwsPlan(int(kernel), K, prob.N, prob.conn)
-            plan = plans[K]
-            prob.build(level, plan, tol)
-            out.carried.append(False)
-            plan.iterate(maxiter, max_relgap)
-            labels, en, lb, it = plan.result()
-            out.paths.append(plan.path())
-            out.labels.append(labels); out.energy.append(en); out.lower_bound.append(lb); out.iterations.append(it)
-            out.plane_maps.append(prob.apply(labels))
-        out.planes = out.plane_maps[-1]
-    finally:
-        for plan in plans.values():
-            plan.close()
+    run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap)
+    out.planes = out.plane_maps[-1]
     return out

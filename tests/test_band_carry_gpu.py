@@ -211,6 +211,82 @@ def test_batch_members_take_carried_messages_as_single_plans_do(hip):
     assert all(st is not None and st.d_messages.shape == (problems[0].E, len(LEVEL_2)) for st in out.stages)
 
 
+def chain_by_hand(prob, levels, kernel, tol):
+    """band.run_levels restated through the problem's protocol with a fresh plan for every level; the hand-over is taken
+    after apply(), where the loop takes it before"""
+    from stereo_amd.trws import TrwsPlan
+    rows, carry = [], None
+    for level in levels:
+        plan = TrwsPlan(kernel, prob.labels_of(level), prob.N, prob.conn)
+        try:
+            prob.build(level, plan, tol, carry=carry)
+            plan.iterate(ITERS, NEVER)
+            labels, en, lb, it = plan.result()
+            moved = prob.apply(labels)
+            carry = prob.carry_from(prob.leave(plan, labels))
+        finally:
+            plan.close()
+        rows.append((labels, en, lb, it, moved))
+    return rows
+
+
+@pytest.mark.parametrize("carry", [False, True])
+def test_levels_whose_K_repeats_equal_the_levels_chained_by_hand(carry, hip, monkeypatch):
+    """K = 3, 5, 3 on a 5 x 7 image: the loop reuses the first plan for the third level (two plans are made, both are
+    closed) and gives, bit for bit, what a fresh plan per level gives -- for the band and for the plane band, whose
+    hand-over the loop takes before apply() and the chain by hand after it."""
+    from stereo_amd import band, terms as T
+    from stereo_amd.plane_band import PlaneBandProblem
+    H, W, D = 5, 7, 6
+    ncc, disp, conn = BR.volume(H, W, D, 41), BR.disparities_for(D, False), T.construct_neighborhood(H, W)
+    base = BR.base_map(H, W, D, LEVEL_1[-1], 12)
+    levels = [np.array([-0.5, 0.0, 0.5]), LEVEL_1, LEVEL_2]
+    made = []
+
+    class Counted(band.TrwsPlan):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            made.append(self)
+            self.closed = 0
+
+        def close(self):
+            self.closed += 1
+            super().close()
+
+    monkeypatch.setattr(band, "TrwsPlan", Counted)
+    tol, kernel = 2.0, 1
+    got = hip.refine_band(ncc, disp, UNARY_WEIGHT, base, kernel, tol, levels, ITERS, NEVER, carry=carry)
+    assert [p.closed for p in made] == [1, 1]
+    planes = PR.planes_through(base, 6)
+    source = hip.NccSource(ncc, disp, UNARY_WEIGHT, 0, (H, W))
+    got_planes = hip.refine_plane_band(source, planes, kernel, tol, levels, ITERS, NEVER, carry=carry)
+    assert [p.closed for p in made] == [1, 1, 1, 1]
+    monkeypatch.undo()
+    wrap = (lambda prob: prob) if carry else NoCarry      # (without carry the loop's levels start from zero)
+    want = chain_by_hand(wrap(band.BandProblem(ncc, disp, UNARY_WEIGHT, base, conn)), levels, kernel, tol)
+    want_planes = chain_by_hand(wrap(PlaneBandProblem(source, planes, conn)), levels, kernel, tol)
+    for res, rows, maps in ((got, want, got.maps), (got_planes, want_planes, got_planes.plane_maps)):
+        assert res.carried == [False, carry, carry]
+        for level, (labels, en, lb, it, moved) in enumerate(rows):
+            assert np.array_equal(res.labels[level], labels) and same_bits(maps[level], moved), level
+            assert (res.energy[level], res.lower_bound[level], res.iterations[level]) == (en, lb, it), level
+    assert same_bits(got.dispmap, want[-1][4]) and same_bits(got_planes.planes, want_planes[-1][4])
+    assert (got.stage is not None) == carry
+
+
+class NoCarry:
+    """a problem whose levels leave nothing"""
+
+    def __init__(self, prob):
+        self.prob = prob
+
+    def __getattr__(self, name):
+        return getattr(self.prob, name)
+
+    def leave(self, plan, labels):
+        return None
+
+
 # ---------------------------------------------------------------- 3: the level that repeats itself
 
 def test_a_repeated_level_goes_on_as_the_uninterrupted_plan(hip):

@@ -239,3 +239,28 @@ def test_the_three_abi_numbers_agree_and_count_the_band_section():
     for name in ("stereo_band_inputs", "stereo_band_apply", "stereo_band_inputs_device", "stereo_band_apply_device",
                  "stereo_band_max_offsets"):
         assert re.search(r"\b%s\s*\(" % name, text) and hasattr(_lib.lib(), name)
+
+
+# ---------------------------------------------------------------- the sanitizer program
+
+def test_builder_argument_checks_are_clean_under_sanitizers(tmp_path):
+    """tools/sanitize_band_args.cpp: the checks and scans of the four level builders (band_common.h and the four .hip
+    files) under ASan + UBSan on the host, a stand-alone program; no device call is made."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc here")
+    exe = str(tmp_path / "sanitize_band_args")
+    csrc = os.path.join(ROOT, "stereo_amd", "csrc")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Xarch_host",
+           "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined", "-w",
+           "-I" + os.path.join(ROOT, "include"), "-I" + csrc,
+           *[os.path.join(csrc, name + ".hip") for name in ("band", "plane_band", "candidates", "plane_candidates")],
+           os.path.join(ROOT, "tools", "sanitize_band_args.cpp"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+    if b.returncode != 0 and "sanitize" in b.stderr.lower() and "cannot find" in b.stderr.lower():
+        pytest.skip("no sanitizer runtime here")
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "SANITIZE_BAND_ARGS_OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
