@@ -1403,6 +1403,11 @@ __device__ __forceinline__ double message_regs(const DevParams &p, int K, double
       const double delta = 1e-9 * (mag + fabs(alpha * p.lambda));
       const bool useful = act && h < vtrunc;
       unsigned long long mask = __builtin_amdgcn_ballot_w64(useful);
+      // Invariant: the compute waves issue no vector-memory instruction outside the serial fallback's counter.  m1
+      // (and m2, cnt, bad) are updated by every trip of every loop below, so they must stay in registers: their
+      // address goes only to routines that are inlined here.  An address handed to an out-of-line routine (the
+      // second look) puts the variable into the wave's private segment for its WHOLE life -- a store per trip and
+      // a load through L1/L2 behind the helper's flag, on the wave the visit waits for.
       double m1 = inf, m2 = inf;
       bool bad = !(delta < inf);
       if (SHAREDPOS && p.pos_gap > 0 && !(window >= 0 && __builtin_popcountll(mask) > kFlatFrom)) {
@@ -1614,8 +1619,12 @@ __device__ __forceinline__ double message_regs(const DevParams &p, int K, double
         if (streak < 4 || (streak & 31) == 0) {
           double delta2;
           bool rel;
-          if (second_look_applies(p.lambda, K, alpha, h, qsrc, t, vtrunc, delta, lane, delta2, rel))
-            need_serial = message_second_look(K, alpha, h, qsrc, t, vtrunc, delta2, rel, lane, m1);
+          if (second_look_applies(p.lambda, K, alpha, h, qsrc, t, vtrunc, delta, lane, delta2, rel)) {
+            // (the callee is out of line: it gets the address of a local of THIS branch, never m1's -- see m1 above)
+            double m1_look;
+            need_serial = message_second_look(K, alpha, h, qsrc, t, vtrunc, delta2, rel, lane, m1_look);
+            m1 = m1_look;
+          }
           MSTAMP(10);
           if (look_streak) *look_streak = need_serial ? streak + 1 : 0;
         } else {

@@ -59,10 +59,14 @@ __device__ __forceinline__ void granule_delay(const DevParams &p, int node) {
 //              positions / neighbour labels and stages them in LDS
 //   wave 9     storer:  while node i is computed, writes node i-1's new messages and scalars
 //              to HBM (write-through), drains, raises node i-1's completion flag
-//   wave 11    primal:  labelling + energy term of node i (previous iteration's primal pass);
-//              wave 10 idles so that the primal wave shares a SIMD with one compute wave only
-// One s_barrier per visit.  The compute waves never touch global memory, so no load or
-// store latency is ever exposed on the chain of dependent visits.
+//   wave 10    loader A: the node's OWN data (unary row, last sweep's outgoing rows, weights), requested two
+//              visits ahead -- nothing there waits for a flag -- and the prefix of Di summed once per node
+//   wave 11    primal:  labelling + energy term of node i (previous iteration's primal pass)
+// One s_barrier per visit.  The compute waves issue no vector-memory instruction outside the serial
+// fallback's counter (and the granule publish behind a finished message), so no load or store latency is
+// exposed on the chain of dependent visits.  That holds only while nothing the message routine keeps live
+// across its loops has its address taken by an out-of-line routine: such a variable lives in the wave's
+// private segment, which IS vector memory (message_regs, trws_dev.h: m1).
 // SPEC: the instantiation that knows the speculative schedule (trws_graph.h: Sweep::Spec; trws_spec.h) -- a kernel of its
 // own, launched only when a plan's sweeps use it: everything it adds (the runner's ticket, a segment's first visit,
 // the held-back flags, the rows kept for a second walk, the commit) costs the visit loops registers, and the plain
