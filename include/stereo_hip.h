@@ -37,8 +37,10 @@ extern "C" {
  * next), stereo_trws_state_receivers_host.  16: stereo_pyramid_reduce_volume / _device (image pyramid: a coarser
  * level's NCC volume as the block mean of the finer one).  17: stereo_candidates_gather / _inputs / _apply (candidate
  * bands: per-pixel label sets propagated from neighbours).  18: stereo_plane_candidates_gather / _inputs_ncc /
- * _inputs_globalstereo / _apply (plane candidates: per-pixel plane sets propagated from neighbours). */
-#define STEREO_HIP_ABI_VERSION 18
+ * _inputs_globalstereo / _apply (plane candidates: per-pixel plane sets propagated from neighbours).
+ * 19: stereo_pyramid_expand_planes / _device (a plane map carried to the next finer scale as planes),
+ * stereo_planes_fit_local / _device (the per-pixel local plane fit). */
+#define STEREO_HIP_ABI_VERSION 19
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -1037,6 +1039,69 @@ int stereo_pyramid_reduce_device(const double *im, int H, int W, int C, double *
 int stereo_pyramid_expand_device(const double *d_coarse, int Hc, int Wc, int H, int W, int mode,
                                  const double *im_fine, const double *im_coarse, int C, double *out,
                                  int32_t *source, void *stream, char *err, size_t errcap);
+
+/* ---- plane pyramid: a plane map to the next finer scale, and the local plane fit ------- *
+ * No reference counterpart.  A plane map is 4 x N doubles, column major: component j of pixel (y, x) at
+ * j + 4*(y + H*x), zero based; a plane [a b c d] has the disparity -((a*X + b*Y) + d) / c at the 1-based point
+ * (X, Y) = (x + 1, y + 1) (dispmap_super.m:318-328).  A plane is VALID when its four components are finite and
+ * c != 0.  fp64 without FMA contraction in the order written here: bit for bit the same lines in any language.
+ *
+ * stereo_pyramid_expand_planes: out (4 x N, N = H*W) and source (int32, H x W, may be NULL) from p_coarse (4 x Nc,
+ * Nc = Hc*Wc).  The size rule, the candidates 0 .. 3 of a fine pixel and the guided choice are stereo_pyramid_expand's
+ * (one copy in the library), with "the candidate's plane is valid" in the place of "its disparity is finite":
+ *   mode 0 (nearest): candidate 0 and source = 0; out is four NaN if that plane is not valid.
+ *   mode 1 (guided): among the valid candidates, the first one whose squared colour distance no later one undercuts;
+ *     none valid: out is four NaN, source = -1.
+ * The chosen plane [a b c d] is written as
+ *     [a, b, c, (2.0*d + 0.5*a) + 0.5*b]
+ * The fine pixel x (zero based) sits at the coarse zero-based coordinate (x + 0.5) / 2 - 0.5, that is at the 1-based
+ * coarse X_c = (X_f + 0.5) / 2 for the 1-based fine X_f, and one coarse disparity unit is two fine ones: the fine
+ * plane's disparity at every fine point is twice the coarse plane's at that point's coarse coordinate (exactly, for
+ * dyadic planes).  The transform is applied uniformly: also at the replicated last row or column of an odd size, where
+ * the box reduction's footprint is one fine pixel wide and the coarse pixel's centre strictly lies half a fine pixel
+ * further in.  A fronto-parallel [0 0 1 -v] becomes [0 0 1 -2v], the value stereo_pyramid_expand gives; for v == 0 the
+ * two additions leave d = +0.0 where negating the expanded map gives -0.0 (equal values, another sign bit).
+ * Refused with a message, before the device is looked for: stereo_pyramid_expand's refusals; any overlap of out with
+ * p_coarse or an image, or of source with out or p_coarse; in the device form a p_coarse or out that is not 16-byte
+ * aligned (a plane moves as two 16-byte accesses).
+ *
+ * stereo_planes_fit_local: out (4 x N) from planes (4 x N), radius r in 1 .. 8 and tau >= 0 (+inf allowed) in the
+ * planes' own disparity units.  z_n is plane n's disparity at its own pixel, by the rule above with s = a*X + b*Y,
+ * z = -(s + d) / c; NaN for a plane that is not valid.  For the pixel i = (y, x) with a valid plane, over the taps
+ * n = (y + dy, x + dx) inside the image, dx = -r .. r ascending in the outer loop and dy = -r .. r ascending in the
+ * inner one, with e = z_n - z_i, those with |e| <= tau (a NaN fails) are accumulated, each sum as S = S + term:
+ *     n += 1   Sx += dx   Sy += dy   Sxx += dx*dx   Sxy += dx*dy   Syy += dy*dy   Sz += e   Sxz += dx*e   Syz += dy*e
+ * (The six sums without e are whole numbers below 2^15: exact in fp64 whatever the order, so an implementation may
+ * keep them as integers and convert them once; the order matters for Sz, Sxz and Syz only.)
+ * Then the normal equations of e ~ alpha*dx + beta*dy + gamma are solved by cofactors:
+ *     c00 = Syy*n - Sy*Sy     c01 = Sxy*n - Sy*Sx     c02 = Sxy*Sy - Syy*Sx
+ *     det = (Sxx*c00 - Sxy*c01) + Sx*c02
+ *     c11 = Sxx*n - Sx*Sx     c12 = Sxx*Sy - Sxy*Sx   c22 = Sxx*Syy - Sxy*Sxy
+ *     alpha = ((c00*Sxz - c01*Syz) + c02*Sz) / det
+ *     beta  = ((c11*Syz - c01*Sxz) - c12*Sz) / det
+ *     gamma = ((c02*Sxz - c12*Syz) + c22*Sz) / det
+ * unless n < 3 or det > 0 does not hold: then alpha = beta = gamma = 0, the pixel's own fronto-parallel plane (so it
+ * is everywhere in an image one pixel wide or high, whose taps are collinear: det = 0).  The output is
+ *     [-alpha, -beta, 1, -(((z_i + gamma) - alpha*X) - beta*Y)]
+ * A pixel whose own plane is not valid keeps it, copied, and is counted in `bad`.  The fit sees only z: a slanted
+ * plane map and the fronto-parallel planes of the same surface give the same output.
+ * `bad`: in the host form a host int32 (may be NULL) that receives the count; in the device form a device int32 (may
+ * be NULL), set to zero on `stream` and then incremented once per such pixel, as in stereo_plane_band_*_device.
+ * Refused with a message, before the device is looked for: NULL planes or out; H or W below 1; H*W >= 2^31; a radius
+ * outside 1 .. 8; a tau that is negative or NaN; out overlapping planes; in the device form planes or out not
+ * 16-byte aligned. */
+int stereo_pyramid_expand_planes(const double *p_coarse, int Hc, int Wc, int H, int W, int mode,
+                                 const double *im_fine, const double *im_coarse, int C, double *out,
+                                 int32_t *source, char *err, size_t errcap);
+int stereo_planes_fit_local(const double *planes, int H, int W, int radius, double tau, double *out, int32_t *bad,
+                            char *err, size_t errcap);
+/* The same on device arrays of the caller, launched on `stream` (hipStream_t, NULL = default) without waiting
+ * for it. */
+int stereo_pyramid_expand_planes_device(const double *p_coarse, int Hc, int Wc, int H, int W, int mode,
+                                        const double *im_fine, const double *im_coarse, int C, double *out,
+                                        int32_t *source, void *stream, char *err, size_t errcap);
+int stereo_planes_fit_local_device(const double *planes, int H, int W, int radius, double tau, double *out,
+                                   int32_t *bad, void *stream, char *err, size_t errcap);
 
 /* ---- image pyramid: a level's volume as the block mean of the finer volume ------------ *
  * No reference counterpart.  `ncc` is an NCC volume of H x W pixels and D slices at `disparities`, layout 0

@@ -366,6 +366,10 @@ class dispmap_super:
         raise StereoHipError("solve_pyramid: %s reaches its second view through a projection, and its refinement is the "
                              "plane band; the image pyramid is defined for dispmap_ncc" % type(self).__name__)
 
+    def solve_plane_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none", unary="images", propagate=None):
+        raise StereoHipError("solve_plane_pyramid: %s reaches its second view through a projection; the plane pyramid is "
+                             "defined for dispmap_ncc" % type(self).__name__)
+
     def _plane_band_source(self):
         """The hook of refine_plane_band: (the object's unary source, the factor from the units of `levels` to the
         planes' disparity units or None for 'as they are')."""
@@ -551,6 +555,32 @@ class dispmap_ncc(dispmap_super):
                                              bands=bands, expand=expand, carry=carry, unary=unary,
                                              volume=self.ncc if unary == "blocks" else None, propagate=propagate)
         self.set_disparity(self._unflip(out.dispmap))
+        return out
+
+    def solve_plane_pyramid(self, levels, bands=None, maxiter=None, expand="guided", carry="none", unary="images", propagate=None):
+        """The assignment from the plane pyramid (no reference counterpart): solve_pyramid's coarsest
+        solve and level model, but what goes from scale to scale is a plane map (pyramid.expand_planes), and every finer
+        level l runs the plane-candidate levels propagate[l] (sources 'base', plane_candidates.Fit(...), 'wta' and
+        4 x N_l planes in the object's internal columns; None: no candidate pass) and then the plane bands bands[l], so
+        a slant found or fitted at one scale survives to the next.  The arguments are solve_pyramid's, with carry 'none'
+        or 'levels'; an object with smooth_weights other than 1 is refused as there.  A mirrored object works in its own
+        flipped columns: the taps' dx are flipped on the way in.  The result goes in through the assignment setter;
+        returns pyramid.solve_view_ncc_plane_pyramid's ViewPlanePyramidResult (planes in the object's internal columns)."""
+        from . import pyramid
+        from .candidates import _taps
+        unary = pyramid.check_unary(unary)
+        if not np.all(self.smooth_weights == 1.0):
+            raise StereoHipError("solve_plane_pyramid: the level model gives every edge one weight; smooth_weights other "
+                                 "than 1 do not carry to another scale")
+        propagate = pyramid.check_plane_propagate(propagate, pyramid.check_plan(levels, 1, bands, expand)[0])
+        if self._mirrored and propagate is not None:      # (checked above: lists of level dicts)
+            propagate = [[dict(c, taps=_taps(c["taps"]) * np.array([1, -1], np.int32)) if "taps" in c else c for c in passes]
+                         for passes in propagate]
+        out = pyramid.solve_view_ncc_plane_pyramid(self.images, self.disparities, self._kernel, self._unary_weight, self._tol,
+                                                   levels, self.maxiter if maxiter is None else maxiter, self._max_relgap,
+                                                   bands=bands, expand=expand, carry=carry, unary=unary,
+                                                   volume=self.ncc if unary == "blocks" else None, propagate=propagate)
+        self.assignment = out.planes
         return out
 
     def _plane_band_source(self):

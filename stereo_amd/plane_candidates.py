@@ -53,9 +53,46 @@ def fronto(m):
     return out
 
 
+class Fit:
+    """A source that is made when a level is built: the local plane fit (fit_local_device) of the
+    problem's CURRENT planes, so a second level fits the first level's result.  `radius`: 1 .. 8 pixels; `tau`: the
+    largest |difference| to the pixel's own disparity a tap may have to take part, in the planes' raw disparity units
+    (not the rescaled ones of dispmap_globalstereo's smoothness term); +inf takes every tap.  Geometric only: it reads
+    no unary, so every plane-candidate level takes it."""
+
+    def __init__(self, radius=2, tau=1.0):
+        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= MAX_FIT_RADIUS:
+            raise StereoHipError("plane candidates: Fit's radius must be a whole number 1 .. %d (got %r)" % (MAX_FIT_RADIUS, radius))
+        if isinstance(tau, bool) or not isinstance(tau, (int, float, np.integer, np.floating)) or not float(tau) >= 0.0:
+            raise StereoHipError("plane candidates: Fit's tau must be a number >= 0 (got %r)" % (tau,))
+        self.radius, self.tau = int(radius), float(tau)
+
+    def __repr__(self):
+        return "Fit(radius=%d, tau=%r)" % (self.radius, self.tau)
+
+
+MAX_FIT_RADIUS = 8
+
+
 def _shape(shape):
     H, W = (int(v) for v in shape)
     return H, W
+
+
+def fit_local(planes, shape, radius=2, tau=1.0):
+    """stereo_planes_fit_local for an image of `shape` = (H, W): every pixel's plane replaced by the least-squares plane
+    through the disparities its neighbours' planes have at their own pixels, |dx|, |dy| <= radius, of which those within
+    `tau` of the pixel's own take part (the planes' own disparity units).  -> (out 4 x N, Fortran order, bad): `bad`
+    counts the pixels whose own plane has c == 0 or a component that is not finite; they keep their plane."""
+    H, W = _shape(shape)
+    planes = _planes(planes, H * W)
+    out = np.zeros((4, max(H * W, 1)), order="F")
+    bad = C.c_int32(0)
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_planes_fit_local(_p(planes), C.c_int(H), C.c_int(W), C.c_int(int(radius)), C.c_double(float(tau)),
+                                            _p(out), C.byref(bad), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return out, int(bad.value)
 
 
 def _table(pcand, N):
@@ -238,22 +275,41 @@ def plane_candidates_apply_device(pcand, labels, shape, out=None, bad=None, stre
     return out, bad
 
 
+def fit_local_device(planes, shape, radius=2, tau=1.0, out=None, bad=None, stream=None, check=False):
+    """stereo_planes_fit_local_device: `planes` a contiguous float64 tensor of 4 N elements, launched on `stream` (a
+    torch stream or a raw handle; default: torch's current stream).  check=True reads the count of pixels whose own plane
+    has c == 0 or is not finite back (this waits for the stream) and raises; check=False (the default: such a pixel keeps
+    its plane, which is a defined result) leaves it in `bad` and does not wait.  -> (out (N, 4), bad)."""
+    import torch
+    H, W = _shape(shape)
+    N = H * W
+    planes = _flat(planes, "planes", torch.float64, 4 * N)
+    out, bad = _out(out, "out", 4 * N, planes.device, new=(N, 4)), _bad(bad, planes.device)
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_planes_fit_local_device(_vp(planes), C.c_int(H), C.c_int(W), C.c_int(int(radius)),
+                                                   C.c_double(float(tau)), _vp(out), _vp(bad), C.c_void_p(_stream(stream)), err,
+                                                   C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    _raise_bad(bad, check, "fit_local_device: %d plane(s) with c == 0 or a component that is not finite")
+    return out, bad
+
+
 # ---------------------------------------------------------------- levels
 
 def _check_source(s):
     if isinstance(s, str):
         if s != "base":
-            raise StereoHipError("plane candidates: a source is 'base' or 4 x N planes (got %r)" % (s,))
-    elif not isinstance(s, OrOwn) and (np.ndim(s) != 2 or np.shape(s)[0] != 4):
-        raise StereoHipError("plane candidates: a source is 'base' or 4 x N planes")
+            raise StereoHipError("plane candidates: a source is 'base' or 4 x N planes, or a Fit (got %r)" % (s,))
+    elif not isinstance(s, (OrOwn, Fit)) and (np.ndim(s) != 2 or np.shape(s)[0] != 4):
+        raise StereoHipError("plane candidates: a source is 'base' or 4 x N planes, or a Fit")
 
 
-_HOW = dict(check_source=_check_source, prefix="plane candidates", single=(str, np.ndarray, OrOwn))
+_HOW = dict(check_source=_check_source, prefix="plane candidates", single=(str, np.ndarray, OrOwn, Fit))
 
 
 def check_level(level):
-    """A plane-candidate level as dict(offsets: float64 vector, taps: T x 2 int32, sources: list of 'base' / 4 x N plane
-    arrays / OrOwn), checked as candidates.check_level checks a candidate level."""
+    """A plane-candidate level as dict(offsets: float64 vector, taps: T x 2 int32, sources: list of 'base' / Fit / 4 x N
+    plane arrays / OrOwn), checked as candidates.check_level checks a candidate level."""
     return candidates.check_level(level, **_HOW)
 
 
@@ -281,6 +337,9 @@ class PlaneCandidateProblem(PlaneBandProblem):
         for s in level["sources"]:
             if isinstance(s, str):
                 maps.append(self.d_planes.view(self.N, 4))
+                continue
+            if isinstance(s, Fit):             # (made now, from the planes the levels before this one left)
+                maps.append(fit_local_device(self.d_planes, self.shape, s.radius, s.tau)[0].view(self.N, 4))
                 continue
             fill = isinstance(s, OrOwn)
             s = _planes(s.planes if fill else s, self.N)

@@ -4,6 +4,8 @@ and ``solve_pair_ncc_pyramid``: the pair solved at the coarsest scale, the maps 
 levels at every finer scale.  ``reduce_volume`` / ``level_volumes`` make a coarser
 level's NCC volume as the 2 x 2 block mean of the finer one (``unary="blocks"``) where the default takes the NCC of the
 reduced images.  ``propagate=`` runs candidate levels (candidates.py) before a level's bands.
+``expand_planes`` carries a plane map to the next finer scale as planes, and ``solve_view_ncc_plane_pyramid`` is the
+one-view pyramid on them: plane-candidate levels and plane bands at every finer scale.
 
 Host forms take NumPy arrays: an image H x W x C (or H x W), a map H x W, any memory order.  Device forms take torch
 tensors of the current device in column-major storage: a map is a contiguous (W, H) tensor as lr_check_device takes
@@ -159,6 +161,79 @@ def expand_device(d_coarse, shape, mode="guided", im_fine=None, im_coarse=None, 
     rc = _lib.lib().stereo_pyramid_expand_device(vp(d_coarse), C.c_int(Hc), C.c_int(Wc), C.c_int(H), C.c_int(W), C.c_int(mode),
                                                  vp(im_fine), vp(im_coarse), C.c_int(Cn), vp(out), vp(source),
                                                  C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return out, source
+
+
+# ---------------------------------------------------------------- a plane map to the next finer scale
+
+def _coarse_planes(p_coarse, H, W):
+    from .plane_band import _planes
+    Hc, Wc = coarse_size(H, W)
+    p = np.asarray(p_coarse, dtype=np.float64)
+    if p.ndim != 2 or p.shape != (4, Hc * Wc):
+        raise StereoHipError("expand_planes: p_coarse must be 4 x (Hc * Wc) planes of the coarse size %d x %d of %d x %d "
+                             "(got %s)" % (Hc, Wc, H, W, p.shape))
+    return _planes(p), Hc, Wc
+
+
+def expand_planes(p_coarse, shape, mode="guided", im_fine=None, im_coarse=None, want_source=True):
+    """stereo_pyramid_expand_planes: the coarse plane map (4 x Nc, pixels column major) to the fine size `shape` =
+    (H, W) as planes -> (out 4 x N float64, source H x W int32 or None).  The modes and the images are expand's."""
+    mode = _mode(mode)
+    H, W = (int(v) for v in shape)
+    p_coarse, Hc, Wc = _coarse_planes(p_coarse, H, W)
+    Cn = 1
+    if mode == 1:
+        if im_fine is None or im_coarse is None:
+            raise StereoHipError("expand_planes: the guided mode needs im_fine and im_coarse")
+        im_fine, im_coarse = _image(im_fine, "im_fine"), _image(im_coarse, "im_coarse")
+        Cn = im_fine.shape[2]
+        if im_fine.shape != (H, W, Cn) or im_coarse.shape != (Hc, Wc, Cn):
+            raise StereoHipError("expand_planes: im_fine must be H x W x C and im_coarse of the coarse size with the same C "
+                                 "(got %s and %s)" % (im_fine.shape, im_coarse.shape))
+    else:
+        im_fine = im_coarse = None
+    out = np.zeros((4, max(H * W, 1)), order="F")
+    source = np.zeros((max(H, 0), max(W, 0)), np.int32, order="F") if want_source else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_pyramid_expand_planes(_p(p_coarse), C.c_int(Hc), C.c_int(Wc), C.c_int(H), C.c_int(W), C.c_int(mode),
+                                                 _p(im_fine), _p(im_coarse), C.c_int(Cn), _p(out), _p(source, C.c_int32), err,
+                                                 C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return out, source
+
+
+def expand_planes_device(p_coarse, shape, mode="guided", im_fine=None, im_coarse=None, out=None, source=None, stream=None,
+                         want_source=True):
+    """stereo_pyramid_expand_planes_device: `p_coarse` a contiguous float64 tensor of 4 Nc elements (shape (Nc, 4), as
+    in plane_band.py), the images (C, W, H) / (C, Wc, Hc) tensors, `shape` = (H, W), launched on `stream` without
+    waiting for it -> (out (N, 4) float64, source (W, H) int32 or None)."""
+    import torch
+    mode = _mode(mode)
+    H, W = (int(v) for v in shape)
+    Hc, Wc = coarse_size(H, W)
+    p_coarse = band._flat(p_coarse, "p_coarse", torch.float64, 4 * Hc * Wc)
+    Cn = 1
+    if mode == 1:
+        if im_fine is None or im_coarse is None:
+            raise StereoHipError("expand_planes_device: the guided mode needs im_fine and im_coarse")
+        im_fine = _device_image(im_fine, "im_fine")
+        Cn = im_fine.shape[0]
+        _device_image(im_fine, "im_fine", (Cn, W, H))
+        im_coarse = _device_image(im_coarse, "im_coarse", (Cn, Wc, Hc))
+    else:
+        im_fine = im_coarse = None
+    out = band._out(out, "out", 4 * H * W, p_coarse.device, new=(H * W, 4))
+    if source is None and want_source:
+        source = torch.empty((W, H), dtype=torch.int32, device=p_coarse.device)
+    elif source is not None:
+        source = _device_map(source, "source", np.int32, (W, H))
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_pyramid_expand_planes_device(vp(p_coarse), C.c_int(Hc), C.c_int(Wc), C.c_int(H), C.c_int(W),
+                                                        C.c_int(mode), vp(im_fine), vp(im_coarse), C.c_int(Cn), vp(out),
+                                                        vp(source), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
     _lib.check(rc, err)
     return out, source
 
@@ -498,6 +573,65 @@ def solve_pair_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
 
 # ---------------------------------------------------------------- one view (dispmap_ncc.solve_pyramid)
 
+def _check_volume_argument(volume, unary):
+    if volume is not None and unary != "blocks":
+        raise StereoHipError("pyramid: a volume is taken with unary='blocks' only ('images' makes every level's own)")
+
+
+def _view_setup(out, images, disparities, kernel, tol, levels, unary, volume):
+    """What the one-view solves share before the coarsest solve: the images reduced `levels` times, the level model in
+    `out` (disparities, tol, smooth_weight, unary, times["volumes"]) and the levels' volumes.
+    -> (host images per level, device images per level, the volumes' layout, level_volume(l) -> level l's volume)."""
+    host, dev = reduce_images(images[:2], levels)
+    out.unary = unary
+    for l in range(levels + 1):
+        tol_l, w_l = level_model(kernel, tol, l)
+        out.disparities.append(level_disparities(disparities, l))
+        out.tol.append(tol_l); out.smooth_weight.append(w_l)
+    out.times["volumes"] = 0.0
+    layout, volumes = 1, None
+
+    def level_volume(l):
+        """Level l's volume: a block volume, or ('images') made here from the level's images, one level at a time."""
+        t0 = time.perf_counter()
+        vol = volumes[l] if volumes is not None else T.ncc_volume(host[l][0], host[l][1], out.disparities[l], 2, layout=1)
+        out.times["volumes"] += time.perf_counter() - t0
+        return vol
+
+    if unary == "blocks":
+        t0 = time.perf_counter()
+        if volume is None:
+            volume = T.ncc_volume(host[0][0], host[0][1], disparities, 2, layout=1)
+        layout = 0 if np.ndim(volume) == 3 else 1
+        volumes = level_volumes(volume, host[0][0].shape[:2], disparities, levels, layout)
+        out.times["volumes"] = time.perf_counter() - t0
+    return host, dev, layout, level_volume
+
+
+def _solve_coarsest(out, host, level_volume, layout, kernel, unary_weight, maxiter, max_relgap, want_stage):
+    """The coarsest level of a one-view solve: one TrwsPlan on the level's slices; its labels, energy, bound, iterations,
+    path and carried = False go into `out`.  -> (the level's map H x W, its carry.Stage if want_stage else None)."""
+    L = len(out.disparities) - 1
+    H, W = host[L][0].shape[:2]
+    conn = T.construct_neighborhood(H, W)
+    vol = level_volume(L)
+    if layout == 0:
+        vol = vol.reshape((H * W, -1), order="F").T           # D x N for the upload
+    plan = TrwsPlan(int(kernel), out.disparities[L].shape[0], H * W, conn)
+    try:
+        plan.upload(unary_weight * (1.0 - vol), np.ones(conn.shape[1]) * out.smooth_weight[L], out.tol[L],
+                    positions=out.disparities[L])
+        plan.iterate(maxiter[L], max_relgap)
+        labels, en, lb, it = plan.result()
+        out.paths[L].append(plan.path())
+        out.carried[L].append(False)
+        stage = carry_mod.full_range_stage(plan, out.disparities[L], conn, (H, W)) if want_stage else None
+    finally:
+        plan.close()
+    out.labels[L].append(labels); out.energy[L].append(en); out.lower_bound[L].append(lb); out.iterations[L].append(it)
+    return out.disparities[L][labels.astype(np.int64) - 1].reshape(W, H).T, stage
+
+
 class ViewPyramidResult:
     """solve_view_ncc_pyramid's result: `dispmap` (level 0's last map) and per level l, index l: `maps` (the maps of the
     level's passes), `expanded` / `expand_source` (None at the coarsest level), `labels`, `energy`, `lower_bound`,
@@ -527,55 +661,14 @@ def solve_view_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
     propagate = check_propagate(propagate, levels)
     carry = check_carry(carry)
     unary = check_unary(unary)
-    if volume is not None and unary != "blocks":
-        raise StereoHipError("pyramid: a volume is taken with unary='blocks' only ('images' makes every level's own)")
+    _check_volume_argument(volume, unary)
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
     level_model(kernel, tol, 0)
     _lib.require_device()
-    host, dev = reduce_images(images[:2], levels)
     out = ViewPyramidResult(levels + 1)
-    out.unary = unary
-    for l in range(levels + 1):
-        tol_l, w_l = level_model(kernel, tol, l)
-        out.disparities.append(level_disparities(disparities, l))
-        out.tol.append(tol_l); out.smooth_weight.append(w_l)
-    out.times["volumes"] = 0.0
-    layout, volumes = 1, None
-
-    def level_volume(l):
-        """Level l's volume: a block volume, or ('images') made here from the level's images, one level at a time."""
-        t0 = time.perf_counter()
-        vol = volumes[l] if volumes is not None else T.ncc_volume(host[l][0], host[l][1], out.disparities[l], 2, layout=1)
-        out.times["volumes"] += time.perf_counter() - t0
-        return vol
-
-    if unary == "blocks":
-        t0 = time.perf_counter()
-        if volume is None:
-            volume = T.ncc_volume(host[0][0], host[0][1], disparities, 2, layout=1)
-        layout = 0 if np.ndim(volume) == 3 else 1
-        volumes = level_volumes(volume, host[0][0].shape[:2], disparities, levels, layout)
-        out.times["volumes"] = time.perf_counter() - t0
-    L = levels
-    H, W = host[L][0].shape[:2]
-    conn = T.construct_neighborhood(H, W)
-    vol = level_volume(L)
-    if layout == 0:
-        vol = vol.reshape((H * W, -1), order="F").T           # D x N for the upload
-    plan = TrwsPlan(int(kernel), out.disparities[L].shape[0], H * W, conn)
-    try:
-        plan.upload(unary_weight * (1.0 - vol), np.ones(conn.shape[1]) * out.smooth_weight[L], out.tol[L],
-                    positions=out.disparities[L])
-        plan.iterate(maxiter[L], max_relgap)
-        labels, en, lb, it = plan.result()
-        out.paths[L].append(plan.path())
-        out.carried[L].append(False)
-        stage = carry_mod.full_range_stage(plan, out.disparities[L], conn, (H, W)) if carry == "scales" else None
-    finally:
-        plan.close()
-    out.labels[L].append(labels); out.energy[L].append(en); out.lower_bound[L].append(lb); out.iterations[L].append(it)
-    current = out.disparities[L][labels.astype(np.int64) - 1].reshape(W, H).T
-    out.maps[L].append(current)
+    host, dev, layout, level_volume = _view_setup(out, images, disparities, kernel, tol, levels, unary, volume)
+    current, stage = _solve_coarsest(out, host, level_volume, layout, kernel, unary_weight, maxiter, max_relgap, carry == "scales")
+    out.maps[levels].append(current)
     for l in range(levels - 1, -1, -1):
         H, W = host[l][0].shape[:2]
         out.expanded[l], out.expand_source[l] = _expand_view(current, (H, W), mode, dev[l][0], dev[l + 1][0])
@@ -596,4 +689,124 @@ def solve_view_ncc_pyramid(images, disparities, kernel, unary_weight, tol, level
             getattr(out, name)[l] = [v for x in results for v in getattr(x, name)]
         current = r.dispmap
     out.dispmap = current
+    return out
+
+
+# ---------------------------------------------------------------- one view, planes carried and fitted
+
+class ViewPlanePyramidResult(ViewPyramidResult):
+    """solve_view_ncc_plane_pyramid's result: `planes` (4 x N, level 0's last plane map), `dispmap` (their disparities at
+    their own pixels, H x W) and per level l, index l: `plane_maps` (4 x N_l per pass; at the coarsest level the one
+    fronto-parallel map of its solve), `expanded` (4 x N_l) / `expand_source` (None at the coarsest level), `labels`,
+    `energy`, `lower_bound`, `iterations`, `paths`, `carried` (lists per pass, candidate passes before bands),
+    `disparities`, `tol`, `smooth_weight`; `unary` and `times["volumes"]` as in ViewPyramidResult."""
+
+    def __init__(self, n):
+        super().__init__(n)
+        self.planes, self.plane_maps = None, self.maps
+
+
+def plane_disparities(planes, shape):
+    """4 x N planes -> H x W: every plane's disparity at its own pixel, -((a X + b Y) + d) / c at the 1-based point."""
+    H, W = (int(v) for v in shape)
+    p = np.asarray(planes, dtype=np.float64)
+    X, Y = np.repeat(np.arange(1.0, W + 1), H), np.tile(np.arange(1.0, H + 1), W)
+    with np.errstate(all="ignore"):
+        return (-((p[0] * X + p[1] * Y) + p[3]) / p[2]).reshape(W, H).T
+
+
+def check_plane_propagate(propagate, levels):
+    """`propagate` of a plane pyramid solve -> per level 0 .. levels - 1 a list of plane-candidate levels as the caller
+    wrote them, each checked (plane_candidates.check_level) with 'wta' standing for a source that is made when the level
+    runs; None stays None."""
+    if propagate is None:
+        return None
+    from . import plane_candidates
+    try:
+        n = len(propagate)
+    except TypeError:
+        n = -1
+    if n != levels or isinstance(propagate, (dict, str)):
+        raise StereoHipError("pyramid: propagate must hold one sequence of plane-candidate levels per level 0 .. levels - 1 "
+                             "(%d, got %d)" % (levels, n))
+    checked = []
+    for l, passes in enumerate(propagate):
+        if passes is None:
+            passes = []
+        if isinstance(passes, dict):
+            passes = [passes]
+        try:
+            passes = list(passes)
+        except TypeError:
+            raise StereoHipError("pyramid: propagate[%d] must be a sequence of plane-candidate levels" % l)
+        for c in passes:
+            plane_candidates.check_level(_with_wta(c, "base"))
+        checked.append(passes)
+    return checked
+
+
+def _with_wta(level, wta):
+    """A plane-candidate level as the caller wrote it, its 'wta' sources replaced by `wta`."""
+    if not isinstance(level, dict) or "sources" not in level:
+        return level
+    from . import plane_candidates
+    sources = level["sources"]
+    if isinstance(sources, (str, np.ndarray, plane_candidates.OrOwn, plane_candidates.Fit)):
+        sources = [sources]
+    return dict(level, sources=[wta if isinstance(s, str) and s == "wta" else s for s in sources])
+
+
+def solve_view_ncc_plane_pyramid(images, disparities, kernel, unary_weight, tol, levels, maxiter, max_relgap, bands=None,
+                                 expand="guided", carry="none", unary="images", volume=None, propagate=None):
+    """One view, coarse to fine, as PLANES.  The reduction, the level model, the levels' volumes (unary,
+    volume) and the coarsest solve are solve_view_ncc_pyramid's; the coarsest map becomes plane_candidates.fronto(map).
+    Each finer level l then runs, in order: expand_planes_device with the view's images of the two scales (`expand`);
+    the plane-candidate levels of propagate[l] (plane_candidates.refine_plane_candidates on an NccSource of the level's
+    volume; a level's sources are 'base', plane_candidates.Fit(...), 'wta' -- the level volume's winner-take-all map as
+    OrOwn(fronto(...)) -- and 4 x N_l arrays); the plane bands bands[l] (plane_band.refine_plane_band), with tol_l and
+    the edge weight s^(k - 1); offsets are in the level's disparity units.  carry: 'none', or 'levels' for
+    refine_plane_band(carry=True) within a scale; 'scales' is refused (messages have no meaning across a plane
+    expansion yet).  propagate=None runs no candidate pass.  -> ViewPlanePyramidResult."""
+    from . import plane_band, plane_candidates
+    levels, maxiter, bands, mode = check_plan(levels, maxiter, bands, expand)
+    propagate = check_plane_propagate(propagate, levels)
+    if check_carry(carry) == "scales":
+        raise StereoHipError("plane pyramid: carry must be 'none' or 'levels'; 'scales' is not defined here (messages have "
+                             "no meaning across a plane expansion yet)")
+    unary = check_unary(unary)
+    _check_volume_argument(volume, unary)
+    disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
+    level_model(kernel, tol, 0)
+    _lib.require_device()
+    import torch
+    out = ViewPlanePyramidResult(levels + 1)
+    host, dev, layout, level_volume = _view_setup(out, images, disparities, kernel, tol, levels, unary, volume)
+    current, _ = _solve_coarsest(out, host, level_volume, layout, kernel, unary_weight, maxiter, max_relgap, False)
+    planes = plane_candidates.fronto(current)
+    out.plane_maps[levels].append(planes)
+    for l in range(levels - 1, -1, -1):
+        H, W = host[l][0].shape[:2]
+        d_coarse = torch.from_numpy(np.array(planes.T, order="C")).cuda()              # (Nc, 4): 4 x Nc column major
+        d_fine, d_source = expand_planes_device(d_coarse, (H, W), mode, dev[l][0], dev[l + 1][0])
+        planes = np.asfortranarray(d_fine.cpu().numpy().T)
+        out.expanded[l], out.expand_source[l] = planes, d_source.cpu().numpy().T
+        conn = T.construct_neighborhood(H, W)
+        vol, alphas = level_volume(l), np.ones(conn.shape[1]) * out.smooth_weight[l]
+        source = plane_band.NccSource(vol, out.disparities[l], unary_weight, layout, (H, W))
+        results = []
+        if propagate is not None and propagate[l]:
+            wta = None
+            if any(s is None for c in propagate[l] if isinstance(c, dict) for s in _with_wta(c, None).get("sources", ())):
+                wta = plane_candidates.OrOwn(plane_candidates.fronto(T.ncc_best_disp(vol, out.disparities[l], layout, (H, W))))
+            results.append(plane_candidates.refine_plane_candidates(source, planes, kernel, out.tol[l],
+                                                                    [_with_wta(c, wta) for c in propagate[l]], maxiter[l],
+                                                                    max_relgap, alphas=alphas, conn=conn))
+            planes = results[0].planes
+        results.append(plane_band.refine_plane_band(source, planes, kernel, out.tol[l], bands[l], maxiter[l], max_relgap,
+                                                    alphas=alphas, conn=conn, carry=carry == "levels"))
+        planes = results[-1].planes
+        for name in ("maps", "labels", "energy", "carried", "lower_bound", "iterations", "paths"):
+            getattr(out, name)[l] = [v for x in results for v in getattr(x, name)]
+    out.planes = planes
+    out.dispmap = plane_disparities(planes, host[0][0].shape[:2])
     return out
