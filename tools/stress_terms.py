@@ -1,7 +1,7 @@
 """Development tool: randomised parity stress of the term builders and the cost volume (rows a2-a13: plane -> disparity,
 pairwise terms, TRW-S positions, NCC volume / sampler / winner-takes-all, globalstereo unary) against the NumPy
 restatement oracle/terms.py on random image sizes, disparity lists and plane fields.  Tolerances as in
-tests/test_terms_gpu.py: bit exact where only + - * / are used, 1e-12 absolute for the NCC volume (values in [-1, 1]),
+tests/test_terms_gpu.py: bit exact where only + - * / are used, 1e-12 absolute for the NCC volume (values in [-1, 1]; its label-fastest layout bit for bit against the MATLAB layout),
 1e-12 relative for the globalstereo unary (exp / log).    python tools/stress_terms.py [seconds] [seed]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -62,17 +62,24 @@ while time.time() - t0 < budget:
         if not ok: fail(0, ("pairwise", H, W, kernel, d_min, d_step))
     elif which == 1:    # NCC volume, sampler, winner-takes-all
         H, W = int(rng.integers(1, 60)), int(rng.integers(2, 80))
-        D = int(rng.integers(1, 20))
-        disps = np.arange(0, D, dtype=np.float64) if rng.integers(0, 2) else np.sort(np.round(rng.uniform(0, min(W, 30), D) * 4) / 4)
+        D = int(rng.integers(1, 101))
+        if rng.integers(0, 2):      # integers from 0 (the staged kernels; more than one 64-label chunk from D = 65): every d < W
+            W = max(W, D + 1)
+            disps = np.arange(0, D, dtype=np.float64)
+        else:                       # distinct quarter steps in [0, min(W, 30)] (the per-tap kernel unless all fall on integers)
+            grid = np.arange(0, 4 * min(W, 30) + 1)
+            disps = np.sort(rng.choice(grid, size=min(D, len(grid)), replace=False)) / 4
         if len(np.unique(disps)) != len(disps):
             continue
         im0, im1, flat = images(H, W)
         want = ot.compute_ncc(im0, im1, disps)
         got = st.ncc_volume(im0, im1, disps)
+        lf = st.ncc_volume(im0, im1, disps, layout=1)      # label fastest: other kernels on integer lists, the same bits
         # (windows that straddle a flat region's edge have a variance of a few units against sums of 5e6: the quotient
         #  magnifies the last-bit differences of the box sums -- whose order of addition differs, and MATLAB's conv2's is
         #  not known either -- by 1e5: 9e-12 seen; 1e-9 allowed there, 1e-12 on textured images as in the tests)
         ok = got.shape == want.shape and np.max(np.abs(got - want)) < (1e-9 if flat else 1e-12)
+        ok = ok and np.array_equal(lf, got.reshape(H * W, len(disps), order="F").T)
         pts = ot.get_points(H, W)
         P = np.zeros((4, H * W)); P[2] = 1.0; P[0] = rng.normal() * 0.05
         P[3] = -rng.uniform(-1, disps.max() + 1, H * W)
