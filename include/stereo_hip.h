@@ -488,6 +488,14 @@ int stereo_trws_plan_debug_messages(stereo_trws_plan *plan, double *out, int64_t
  * would, or 0 with the refusal the plan gives in err. */
 int stereo_trws_family_rule(int kernel, int K, int message_mode, int fast_ok, int fast_switch, int strips,
                             int positions, double lambda, char *err, size_t errcap);
+/* Development aid, host only (no device): the rule that picks the kernel of stereo_ncc_volume and its launch geometry
+ * (stereo_amd/csrc/ncc_rule.h).  Facts: H, W, the D host disparities, patchsize, layout, cus (the device's compute-unit
+ * count), naive (STEREO_HIP_NCC_NAIVE is set), rowlanes (STEREO_HIP_NCC_ROWLANES is set).  *path = 0 ncc_volume_kernel
+ * (per tap), 1 ncc_cross_kernel, 2 ncc_lane_kernel; for path 2 *cols = columns per workgroup, *chunks = column chunks
+ * of the grid and *span = the largest max - min over the 64-label chunks of the disparities, all 0 for the other paths.
+ * Any output may be NULL.  Returns 0, or 1 with the reason in err for an argument stereo_ncc_volume refuses. */
+int stereo_ncc_volume_rule(int H, int W, const double *disparities, int D, int patchsize, int layout, int cus, int naive,
+                           int rowlanes, int *path, int *cols, int *chunks, int *span, char *err, size_t errcap);
 /* The gateway on several devices.  With STEREO_HIP_GPUS=G (2 .. 16) in the environment stereo_trws -- what trws_mex
  * reaches, cpp/trws_mex.cpp:149-164 -- cuts the problem into G row strips when the graph is the image grid of
  * dispmap_super.m:279-302 (nodes col * H + row, 4-neighbourhood, H >= 2 G; K <= 128, or <= 256 with one positions vector

@@ -23,6 +23,7 @@
 namespace {
 
 using stereo::fail;
+using stereo::guarded;
 using namespace stereo::band;   // band_common.h: the indices, the launch sizes, every check and scan, HostOutputs
 
 // The disparity of label k at a pixel whose base is b: plane_disp of [0 0 1 -(b + delta)].  The plane's

@@ -3,7 +3,7 @@
 // element index, the clamp of a tap, the launch sizes, what the host reads off the slice positions, every argument
 // check and scan, and the device buffers of a host entry's outputs.  The index prologue of the positions kernels is
 // not here: shared, it changed their instruction order.
-// (carry.hip and pyramid_volume.hip take the index, the launch sizes and guarded() from here.)
+// (carry.hip and pyramid_volume.hip take the index and the launch sizes from here.)
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -179,20 +179,6 @@ inline int check_planes(const std::string &what, const std::string &name, const 
     return fail(what + subject + pixel_name(t, H, K), err, errcap);
   }
   return 0;
-}
-
-template <class F>
-int guarded(const char *what, char *err, size_t errcap, F f) {
-  if (stereo_hip_device_count() < 1)
-    return fail(std::string(what) + ": no HIP device available (the HIP path has no CPU fallback)", err, errcap);
-  try {
-    f();
-    return 0;
-  } catch (const HipError &e) {
-    return fail(e.msg, err, errcap);
-  } catch (const std::exception &e) {
-    return fail(std::string(what) + ": " + e.what(), err, errcap);
-  }
 }
 
 inline unsigned grid_for(int64_t elements) {

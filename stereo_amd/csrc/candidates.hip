@@ -21,6 +21,7 @@
 namespace {
 
 using stereo::fail;
+using stereo::guarded;
 using namespace stereo::band;   // band_common.h: the indices, the launch sizes, every check and scan, HostOutputs
 
 // The disparity of a label whose candidate is c: plane_disp of [0 0 1 -c], i.e. c with the plane's sign of zero

@@ -23,7 +23,7 @@
 namespace {
 
 using stereo::fail;
-using stereo::band::guarded;
+using stereo::guarded;
 using stereo::band::kMaxGrid;
 using stereo::band::kTB;
 using stereo::carry::Args;

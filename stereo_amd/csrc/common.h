@@ -6,7 +6,10 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <exception>
 #include <string>
+
+#include "../../include/stereo_hip.h"
 
 namespace stereo {
 
@@ -51,6 +54,33 @@ struct DeviceScope {
     if (switched) (void)hipSetDevice(prev);
   }
 };
+
+// What every entry point that touches the device is wrapped in: no device is an error of its own (there is no CPU
+// fallback), and nothing is thrown across the C ABI -- an exception becomes the return code and the text in err.
+template <class F>
+int guarded(const char *what, char *err, size_t errcap, F &&f) {
+  if (stereo_hip_device_count() < 1)
+    return fail(std::string(what) + ": no HIP device available (the HIP path has no CPU fallback)", err, errcap);
+  try {
+    f();
+    return 0;
+  } catch (const HipError &e) {
+    return fail(e.msg, err, errcap);
+  } catch (const std::exception &e) {
+    return fail(std::string(what) + ": " + e.what(), err, errcap);
+  }
+}
+
+// ... and that returns only when the device is done: for the entries whose results are host buffers and resident state
+// built from caller memory (pairwise.hip, ncc_volume.hip, unary.hip, fusion.hip).
+template <class F>
+int guarded_sync(const char *what, char *err, size_t errcap, F &&f) {
+  return guarded(what, err, errcap, [&] {
+    f();
+    STEREO_HIP_CHECK(hipGetLastError());
+    STEREO_HIP_CHECK(hipDeviceSynchronize());
+  });
+}
 
 template <class T>
 struct DevBuf {

@@ -15,7 +15,7 @@
 namespace {
 
 using stereo::fail;
-using stereo::HipError;
+using stereo::guarded;
 
 constexpr int kFillRows = 64;       // rows of one fill workgroup: one per lane
 constexpr int kFillMaxChunks = 16;  // waves of one fill workgroup (1024 threads)
@@ -202,20 +202,6 @@ int fill_args(const char *what, const void *d_ref, const void *status, int H, in
   if (status == (const void *)source_or_null) return fail(std::string(what) + ": source must not be status (the fill does not work in place)", err, errcap);
   if (chunks < 1 || chunks > kFillMaxChunks) return fail(std::string(what) + ": chunks must be 1 .. " + std::to_string(kFillMaxChunks), err, errcap);
   return check_sizes(what, H, W, err, errcap);
-}
-
-template <class F>
-int guarded(const char *what, char *err, size_t errcap, F f) {
-  if (stereo_hip_device_count() < 1)
-    return fail(std::string(what) + ": no HIP device available (the HIP path has no CPU fallback)", err, errcap);
-  try {
-    f();
-    return 0;
-  } catch (const HipError &e) {
-    return fail(e.msg, err, errcap);
-  } catch (const std::exception &e) {
-    return fail(std::string(what) + ": " + e.what(), err, errcap);
-  }
 }
 
 void launch_check(const double *d_ref, const double *d_other, int H, int W, int direction, double tol, int32_t *status,

@@ -1,6 +1,6 @@
 // The photo-consistency unary of dispmap_globalstereo (dispmap_globalstereo.m:355-375, ephoto :405, and the
 // 'linear' branch of imrender/vgg/vgg_interp2.cxx:245-322 with oobv = -1000) at one pixel, as a device
-// function: one copy for every kernel that evaluates it at a plane's disparity (terms.hip:
+// function: one copy for every kernel that evaluates it at a plane's disparity (unary.hip:
 // globalstereo_unary_kernel; plane_band.hip: plane_band_unary_kernel).  Compiled with -ffp-contract=off,
 // so + - * / match numpy whichever kernel it is inlined into.
 #pragma once

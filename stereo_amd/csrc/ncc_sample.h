@@ -1,6 +1,6 @@
 // The NCC sampler (dispmap_ncc.m:222-276) and the plane -> disparity rule (dispmap_super.m:318-328) as
 // device functions: one copy for every kernel that evaluates the volume at a real disparity
-// (terms.hip: ncc_unary_kernel, ncc_best_disp_kernel; band.hip: band_unary_kernel; plane_band.hip:
+// (unary.hip: ncc_unary_kernel, ncc_best_disp_kernel; band.hip: band_unary_kernel; plane_band.hip:
 // plane_band_unary_kernel; pyramid_volume.hip: the two reduce_volume kernels).  Compiled with
 // -ffp-contract=off, so + - * / match numpy whichever kernel they are inlined into.
 #pragma once

@@ -23,6 +23,7 @@
 namespace {
 
 using stereo::fail;
+using stereo::guarded;
 using namespace stereo::band;   // band_common.h: the indices, the launch sizes, every check and scan, HostOutputs; the sources
 
 // The plane of label k at a pixel: one fp64 multiplication and one fp64 subtraction (no contraction: the file is

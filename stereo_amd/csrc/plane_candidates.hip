@@ -24,6 +24,7 @@
 namespace {
 
 using stereo::fail;
+using stereo::guarded;
 using namespace stereo::band;   // band_common.h: the indices, the launch sizes, every check and scan, HostOutputs; the sources
 
 // one plane in registers: [a b] and [c d], each a 16-byte access

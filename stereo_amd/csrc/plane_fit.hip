@@ -22,7 +22,7 @@ namespace {
 
 using stereo::fail;
 using stereo::band::check_sizes;
-using stereo::band::guarded;
+using stereo::guarded;
 
 constexpr int kTileY = 64, kTileX = 16, kThreads = 256, kColumnsPerWave = kTileX / (kThreads / kTileY);
 constexpr int kMaxRadius = 8;

@@ -19,7 +19,7 @@
 namespace {
 
 using stereo::fail;
-using stereo::HipError;
+using stereo::guarded;
 
 // ---------------------------------------------------------------- reduce
 //
@@ -237,20 +237,6 @@ int expand_planes_args(const char *name, const double *p_coarse, int Hc, int Wc,
   if (device && ((((uintptr_t)p_coarse) | ((uintptr_t)out)) & 15) != 0)
     return fail(what + ": p_coarse and out must be 16-byte aligned (a plane moves as two 16-byte accesses)", err, errcap);
   return 0;
-}
-
-template <class F>
-int guarded(const char *what, char *err, size_t errcap, F f) {
-  if (stereo_hip_device_count() < 1)
-    return fail(std::string(what) + ": no HIP device available (the HIP path has no CPU fallback)", err, errcap);
-  try {
-    f();
-    return 0;
-  } catch (const HipError &e) {
-    return fail(e.msg, err, errcap);
-  } catch (const std::exception &e) {
-    return fail(std::string(what) + ": " + e.what(), err, errcap);
-  }
 }
 
 dim3 grid_for(int rows, int64_t columns, int tb) {

@@ -25,7 +25,7 @@ namespace {
 using stereo::fail;
 using stereo::band::band_index;
 using stereo::band::BandIndex;
-using stereo::band::guarded;
+using stereo::guarded;
 using stereo::band::kTB;
 
 // out = 0.25 (((v00 + v10) + v01) + v11): the sampler's value at the four fine pixels (rows y0, y1 of the columns

@@ -165,19 +165,6 @@ __global__ void gb_weights_kernel(const float *sm, int H, int W, float *weights)
   }
 }
 
-template <class F>
-int guarded(const char *what, char *err, size_t errcap, F &&f) {
-  try {
-    if (stereo_hip_device_count() < 1) return fail(std::string(what) + ": no HIP device available", err, errcap);
-    f();
-    return 0;
-  } catch (const HipError &e) {
-    return fail(e.msg, err, errcap);
-  } catch (const std::exception &e) {
-    return fail(std::string(what) + ": " + e.what(), err, errcap);
-  }
-}
-
 void ms_own_device(const seg::MsLattice &lat, float *own, uint8_t *events) {
   const int L = lat.H * lat.W;
   DevBuf<float> ds, dout;

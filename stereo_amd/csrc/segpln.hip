@@ -574,19 +574,6 @@ __global__ void segpln_init_kernel(int64_t N, double *proposal) {
   if (i < N) { proposal[4 * i] = 0; proposal[4 * i + 1] = 0; proposal[4 * i + 2] = 1; proposal[4 * i + 3] = 0; }
 }
 
-template <class F>
-int guarded(const char *what, char *err, size_t errcap, F &&f) {
-  try {
-    if (stereo_hip_device_count() < 1) return fail(std::string(what) + ": no HIP device available", err, errcap);
-    f();
-    return 0;
-  } catch (const HipError &e) {
-    return fail(e.msg, err, errcap);
-  } catch (const std::exception &e) {
-    return fail(std::string(what) + ": " + e.what(), err, errcap);
-  }
-}
-
 }  // namespace
 }  // namespace stereo
 

@@ -55,9 +55,16 @@ def _four_runs(st, monkeypatch, im0, im1, disps):
 
 
 def _rules(H, W, disps, cus):
-    return {"layout 0": nx.host_rule(H, W, disps, cus, 0), "layout 1": nx.host_rule(H, W, disps, cus, 1),
-            "layout 1 rowlanes": nx.host_rule(H, W, disps, cus, 1, rowlanes=True),
-            "naive": nx.host_rule(H, W, disps, cus, 0, naive=True)}
+    rules = {"layout 0": nx.host_rule(H, W, disps, cus, 0), "layout 1": nx.host_rule(H, W, disps, cus, 1),
+             "layout 1 rowlanes": nx.host_rule(H, W, disps, cus, 1, rowlanes=True),
+             "naive": nx.host_rule(H, W, disps, cus, 0, naive=True)}
+    # the library's own rule with the device's compute-unit count says the same: "meant for" is what runs
+    ask = nx.library_rule()
+    own = {"layout 0": ask(H, W, disps, cus, 0), "layout 1": ask(H, W, disps, cus, 1),
+           "layout 1 rowlanes": ask(H, W, disps, cus, 1, rowlanes=True), "naive": ask(H, W, disps, cus, 0, naive=True)}
+    assert own == rules, "%dx%d D=%d, %d compute units: the library's rule gives %s, the restatement %s" % (
+        H, W, len(disps), cus, own, rules)
+    return rules
 
 
 def _path_name(run, rule):
@@ -83,7 +90,7 @@ def test_volume_against_exact_on_every_geometry(name, matrix, cus, hip, monkeypa
         path = _path_name(run, rules[run])
         if worst >= WORST.get(path, (-1.0,))[0]:
             WORST[path] = (worst, cond, name)
-    # the three staged runs keep one association (terms.hip, comment above ncc_lane_kernel): the same bits
+    # the three staged runs keep one association (ncc_volume.hip, comment above ncc_lane_kernel): the same bits
     for run in ("layout 1", "layout 1 rowlanes"):
         diff = np.argwhere(runs[run] != runs["layout 0"])
         assert diff.size == 0, "%s: %s (%s cols %s) differs from layout 0 (cross) in %d values, first at (row, col, i) = %s: %r against %r" % (
