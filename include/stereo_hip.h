@@ -40,7 +40,7 @@ extern "C" {
  * _inputs_globalstereo / _apply (plane candidates: per-pixel plane sets propagated from neighbours).
  * 19: stereo_pyramid_expand_planes / _device (a plane map carried to the next finer scale as planes),
  * stereo_planes_fit_local / _device (the per-pixel local plane fit). */
-#define STEREO_HIP_ABI_VERSION 19
+#define STEREO_HIP_ABI_VERSION 20
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -1139,6 +1139,46 @@ int stereo_pyramid_reduce_volume_device(const double *ncc, int H, int W, int D, 
                                         const double *d_disparities, const double *sample_at,
                                         const double *d_sample_at, int Kc, double *out, void *stream, char *err,
                                         size_t errcap);
+
+/* ---- scanline aggregation: directional chain min-marginals --------------------------- *
+ * No reference counterpart.  `unary` is D x N, label fastest (element (k, p) at k + D*p: layout 1, what TRW-S
+ * consumes), N = H*W, pixel id p = y + H*x.  `positions`: D doubles, finite, in any order (repeats allowed).
+ * kernel 1: v(d) = d, kernel 2: v(d) = d*d.  `directions`: R pairs (dy, dx), dy, dx in {-1, 0, 1}, not both 0,
+ * 1 <= R <= 8, duplicates allowed; `weights`: one w_r >= 0 per direction.
+ *     V_r[k, l] = w_r * min(v(|pos_k - pos_l|), tol)       (the product last, every operation rounded once)
+ * For direction r the predecessor of pixel (y, x) is (y - dy, x - dx):
+ *     L_r(p, k) = U(p, k)                                           where the predecessor is outside the image,
+ *     L_r(p, k) = U(p, k) + min_l (L_r(p - r, l) + V_r[k, l])       otherwise.
+ * The minimum over l is NOT subtracted: L_r(p, k) is the exact minimum energy, under the model's own pairwise term
+ * w_r * min(v(|pos_a - pos_b|), tol), of the half chain that runs along direction r from the image border to p and
+ * ends with x_p = k; L_r + L_-r - U is the min-marginal of the whole scanline.
+ *     S = (((L_1 + L_2) + L_3) + ...)      in list order, D x N
+ *     labels[p]     = the first minimum of S(p, .), ONE based
+ *     map[p]        = positions[labels[p] - 1], H x W column major
+ *     confidence[p] = the second-smallest entry of S(p, .) - min S(p, .): 0 where the minimum occurs twice, +Inf at
+ *                     D = 1 (the rule of stereo_trws_plan_keep_min_marginals)
+ * fp64 without FMA contraction.  Every candidate L + V is one add, U + min is one add, and a minimum of finite
+ * doubles does not depend on the order it is taken in: for finite inputs the results are these lines' bits.
+ *
+ * Refused with a message, before the device is looked for: H or W below 1; H*W >= 2^31; D outside 1 ..
+ * stereo_scanline_max_labels() (256); kernel other than 1 / 2; tol negative or NaN; R outside 1 .. 8; a direction
+ * outside the set above; a weight that is negative or not finite; NULL for a required array; S == unary; and in
+ * stereo_scanline_aggregate, whose arrays are on the host, a value of `unary` or `positions` that is not finite.
+ * H = 1, W = 1 and D = 1 are valid.  S, map and confidence may be NULL there. */
+int stereo_scanline_max_labels(void);
+int stereo_scanline_aggregate(const double *unary, int H, int W, int D, const double *positions, int kernel, double tol,
+                              const int32_t *directions, const double *weights, int R, double *S, int32_t *labels,
+                              double *map, double *confidence, char *err, size_t errcap);
+/* The same on device arrays of the caller (`unary`, `positions`, `S`, `labels`, `map`, `confidence`), launched on
+ * `stream` (hipStream_t, NULL = default) without waiting for it: one launch per direction and one for the reduction.
+ * `directions` and `weights` stay HOST arrays: they are the launches' parameters (at most 8 pairs and 8 doubles),
+ * checked as above and not read after the call returns.  S is required: it is the workspace the directions add into,
+ * and the output.  map and confidence may be NULL.  The inputs must be finite; for other values the call promises
+ * only labels in 1 .. D and no access outside its arrays. */
+int stereo_scanline_aggregate_device(const double *unary, int H, int W, int D, const double *positions, int kernel,
+                                     double tol, const int32_t *directions, const double *weights, int R, double *S,
+                                     int32_t *labels, double *map, double *confidence, void *stream, char *err,
+                                     size_t errcap);
 
 /* ---- device-resident fusion moves --------------------------------------- *
  * The state of one dispmap object kept in HBM across moves: connectivity, weights, points,

@@ -497,6 +497,18 @@ class dispmap_ncc(dispmap_super):
         """H x W x D: unary_weight * (1 - ncc), the unary of every fronto-parallel label, in the image's own columns."""
         return self._unary_weight * (1.0 - (self.ncc[:, ::-1] if self._mirrored else self.ncc))
 
+    def aggregate_scanlines(self, directions=None, weights=None):
+        """Scanline aggregation of this object's unary volume (no reference counterpart) with its
+        disparities, kernel and tolerance: scanline.aggregate on unary_volume(), in the image's own columns (so is a
+        direction's dx), along `directions` (default scanline.DIRECTIONS_8) with one weight per direction (default 1).
+        Nothing is stored in the object.  -> scanline.ScanlineResult with the summed volume (D x N)."""
+        from . import scanline
+        vol = self.unary_volume()
+        H, W, D = vol.shape
+        unary = np.asfortranarray(vol.transpose(2, 1, 0).reshape(D, W * H))
+        return scanline.aggregate(unary, (H, W), self.disparities, self._kernel, self._tol,
+                                  scanline.DIRECTIONS_8 if directions is None else directions, weights, want_volume=True)
+
     def refine_band(self, levels, maxiter=None, carry=False):
         """Sub-pixel refinement of the current map (no reference counterpart): for every vector of offsets in
         `levels` (strictly ascending, containing 0) TRW-S chooses per pixel among current disparity + offset, with this

@@ -1,0 +1,212 @@
+"""Scanline aggregation (no reference counterpart; the definition: include/stereo_hip.h): the exact
+min-sum dynamic programme of the model's own pairwise term along the scanlines of up to 8 directions, summed into a
+D x N volume, and the labels, map and confidence the sum gives; ``model_energy``, the energy of any labelling under the
+model TRW-S minimises; and ``solve_pair_ncc_scanline``, both views of a pair from the aggregation, cross-checked, with
+optional candidate and band levels around the scanline maps.
+
+A volume is D x N, label fastest (layout 1), N = H * W, pixel id = col * H + row.  A direction is (dy, dx): the
+predecessor of pixel (y, x) is (y - dy, x - dx).  Host forms take NumPy arrays; device forms take torch tensors of the
+current device: a volume as a flat contiguous float64 tensor of D * N elements, a map as a contiguous (W, H) tensor, as
+consistency.lr_check_device takes it.
+"""
+import ctypes as C
+import time
+
+import numpy as np
+
+from . import _lib
+from . import band
+from . import consistency
+from . import terms as T
+from ._lib import StereoHipError
+from .consistency import _device_map, _p, _stream
+
+DIRECTIONS_4 = ((0, 1), (0, -1), (1, 0), (-1, 0))
+DIRECTIONS_8 = DIRECTIONS_4 + ((1, 1), (-1, -1), (1, -1), (-1, 1))
+
+
+def max_labels():
+    """The largest D (stereo_scanline_max_labels)."""
+    return int(_lib.lib().stereo_scanline_max_labels())
+
+
+class ScanlineResult:
+    """`labels` (N, int32, one based), `dispmap` and `confidence` (H x W), `volume` (D x N, the summed costs S, or None).
+    From aggregate_device the four are tensors: N int32, (W, H), (W, H), flat D * N."""
+
+    def __init__(self, labels, dispmap, confidence, volume):
+        self.labels, self.dispmap, self.confidence, self.volume = labels, dispmap, confidence, volume
+
+
+def _directions(directions, weights):
+    """-> (2 R int32 array of (dy, dx) pairs, R float64 weights); the library checks the values."""
+    try:
+        d = np.array([[int(v) for v in pair] for pair in directions], dtype=np.int32).reshape(-1, 2)
+    except (TypeError, ValueError):
+        raise StereoHipError("scanline: directions must be a sequence of (dy, dx) pairs")
+    R = d.shape[0]
+    w = np.ones(R) if weights is None else np.array(weights, dtype=np.float64).reshape(-1)
+    if w.shape[0] != R:
+        raise StereoHipError("scanline: %d weights for %d directions" % (w.shape[0], R))
+    return np.ascontiguousarray(d.reshape(-1)), np.ascontiguousarray(w)
+
+
+def _shape(shape):
+    H, W = (int(v) for v in shape)
+    return H, W
+
+
+def aggregate(unary, shape, positions, kernel, tol, directions=DIRECTIONS_8, weights=None, want_volume=False):
+    """stereo_scanline_aggregate: `unary` D x N (label fastest) of `shape` = (H, W) pixels, `positions` the D label
+    positions, kernel 1 / 2 and `tol` the model's truncated linear / quadratic term, one weight per direction (default 1).
+    -> ScanlineResult on the host (`volume` only with want_volume)."""
+    H, W = _shape(shape)
+    unary = np.asarray(unary, dtype=np.float64)
+    positions = np.ascontiguousarray(np.asarray(positions, dtype=np.float64).reshape(-1))
+    D = positions.shape[0]
+    if unary.ndim != 2 or unary.shape != (D, max(H, 0) * max(W, 0)):
+        raise StereoHipError("scanline: unary must be D x N = %d x %d (got %s)" % (D, max(H, 0) * max(W, 0), unary.shape))
+    unary = np.asfortranarray(unary)
+    d, w = _directions(directions, weights)
+    n = max(H * W, 1)
+    labels = np.zeros(n, np.int32)
+    dispmap, conf = np.zeros((max(H, 0), max(W, 0)), order="F"), np.zeros((max(H, 0), max(W, 0)), order="F")
+    volume = np.zeros((D, H * W), order="F") if want_volume and H > 0 and W > 0 else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_scanline_aggregate(_p(unary), C.c_int(H), C.c_int(W), C.c_int(D), _p(positions), C.c_int(int(kernel)),
+                                              C.c_double(float(tol)), _p(d, C.c_int32), _p(w), C.c_int(w.shape[0]),
+                                              _p(volume), _p(labels, C.c_int32), _p(dispmap), _p(conf), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return ScanlineResult(labels[:H * W], dispmap, conf, volume)
+
+
+def aggregate_device(unary, shape, positions, kernel, tol, directions=DIRECTIONS_8, weights=None, volume=None, labels=None,
+                     dispmap=None, confidence=None, stream=None, d_positions=None):
+    """stereo_scanline_aggregate_device on torch tensors of the current device, launched on `stream` (a torch stream or a
+    raw handle; default: torch's current stream) without waiting for it.  `unary`: a flat float64 tensor of D * N
+    elements, which must be finite.  `positions` is a host vector; `d_positions` its device copy, made here when not given
+    (as band.band_inputs_device takes its short vectors).  `volume` (flat, D * N: the workspace and the summed costs),
+    `labels` (N int32), `dispmap` and `confidence` ((W, H) maps): tensors to write into; made here otherwise.
+    -> ScanlineResult of tensors."""
+    import torch
+    H, W = _shape(shape)
+    positions = np.ascontiguousarray(np.asarray(positions, dtype=np.float64).reshape(-1))
+    D = positions.shape[0]
+    N = max(H, 0) * max(W, 0)
+    unary = band._flat(unary, "unary", torch.float64, D * N)
+    d, w = _directions(directions, weights)
+    (d_positions,) = band._device_vectors(stream, (positions, d_positions, "d_positions"))
+    volume = band._out(volume, "volume", D * N, unary.device)
+    labels = torch.empty(N, dtype=torch.int32, device=unary.device) if labels is None else band._flat(labels, "labels", torch.int32, N)
+    dispmap = torch.empty((W, H), dtype=torch.float64, device=unary.device) if dispmap is None else _device_map(dispmap, "dispmap", np.float64, (W, H))
+    confidence = torch.empty((W, H), dtype=torch.float64, device=unary.device) if confidence is None else _device_map(confidence, "confidence", np.float64, (W, H))
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_scanline_aggregate_device(band._vp(unary), C.c_int(H), C.c_int(W), C.c_int(D), band._vp(d_positions),
+                                                     C.c_int(int(kernel)), C.c_double(float(tol)), _p(d, C.c_int32), _p(w),
+                                                     C.c_int(w.shape[0]), band._vp(volume), band._vp(labels), band._vp(dispmap),
+                                                     band._vp(confidence), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return ScanlineResult(labels, dispmap, confidence, volume)
+
+
+def model_energy(unary, conn, alphas, positions, kernel, tol, labels):
+    """The energy of the labelling `labels` (N, ONE based) under the model the header documents, on shared positions:
+    sum_i unary[labels_i, i] + sum_e alphas_e * min(v(|pos[labels_a] - pos[labels_b]|), tol) over the edges e = (a, b) of
+    `conn` (2 x E, zero based), v(d) = d (kernel 1) or d * d (kernel 2).  NumPy on the host, N + E terms: the currency of
+    a TRW-S result for a map that did not come from TRW-S."""
+    if int(kernel) not in (1, 2):
+        raise StereoHipError("model_energy: kernel must be 1 or 2 (got %r)" % (kernel,))
+    unary = np.asarray(unary, dtype=np.float64)
+    conn = np.asarray(conn).astype(np.int64)
+    positions = np.asarray(positions, dtype=np.float64).reshape(-1)
+    x = np.asarray(labels).reshape(-1).astype(np.int64) - 1
+    D, N = unary.shape
+    if conn.ndim != 2 or conn.shape[0] != 2 or positions.shape[0] != D or x.shape[0] != N:
+        raise StereoHipError("model_energy: unary D x N, conn 2 x E, D positions and N labels")
+    if x.size and (x.min() < 0 or x.max() >= D):
+        raise StereoHipError("model_energy: labels must be 1 .. %d" % D)
+    alphas = np.broadcast_to(np.asarray(alphas, dtype=np.float64).reshape(-1), (conn.shape[1],))
+    d = np.abs(positions[x[conn[0]]] - positions[x[conn[1]]])
+    pair = alphas * np.minimum(d if int(kernel) == 1 else d * d, float(tol))
+    return float(unary[x, np.arange(N)].sum() + pair.sum())
+
+
+def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, check_tol=1.0, directions=DIRECTIONS_8,
+                            smooth_weight=1.0, candidate_levels=None, band_levels=None, maxiter=30, max_relgap=0.0,
+                            volumes=None):
+    """Both views of a rectified pair without a full-range solve.  In this order: the two NCC volumes
+    (consistency.pair_volumes, or `volumes`); each view's unary_weight * (1 - ncc) aggregated on the device along
+    `directions`, every direction weighing `smooth_weight`; the two maps checked against each other with check_tol and
+    filled.  That first pass has energy = model_energy of the scanline labels on the image grid with every edge weighing
+    smooth_weight, lower_bound NaN, iterations 0 and path 0.  Then the optional candidate levels and the
+    optional band levels around the scanline map, both views as a two-member TrwsBatch per level with up
+    to `maxiter` iterations (consistency.run_band_levels, as solve_pair_ncc_pyramid runs them around an expanded map).
+    -> consistency.PairResult."""
+    import torch
+    from . import candidates
+    disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
+    if len(images) != 2:
+        raise StereoHipError("solve_pair_ncc_scanline: images must be the two views of a pair, left first (got %d)" % len(images))
+    shapes = [np.shape(im) for im in images]
+    if shapes[0] != shapes[1] or len(shapes[0]) != 3 or shapes[0][2] != 3:
+        raise StereoHipError("solve_pair_ncc_scanline: the two images must be H x W x 3 arrays of one size (got %s and %s)" % tuple(shapes))
+    if disparities.size < 1:
+        raise StereoHipError("solve_pair_ncc_scanline: no disparities")
+    H, W = shapes[0][:2]
+    K, N = disparities.shape[0], H * W
+    if candidate_levels is not None:
+        candidate_levels = candidates.check_levels(candidate_levels)
+    if band_levels is not None:
+        band_levels = band.check_levels(band_levels)
+    directions = [tuple(d) for d in directions]
+    weights = [float(smooth_weight)] * len(directions)
+    _lib.require_device()
+    out = consistency.PairResult()
+    clock = time.perf_counter
+    t0 = clock()
+    if volumes is None:
+        volumes = consistency.pair_volumes(images, disparities)
+    else:
+        volumes = [np.asarray(v, dtype=np.float64) for v in volumes]
+        if len(volumes) != 2 or any(v.shape != (K, N) for v in volumes):
+            raise StereoHipError("solve_pair_ncc_scanline: volumes must be the two D x N volumes of the pair (%d x %d)" % (K, N))
+    unaries = consistency.pair_unaries(images, disparities, unary_weight, volumes)
+    out.times["volumes"] = clock() - t0
+    conn = T.construct_neighborhood(H, W)
+    alphas = np.ones(conn.shape[1]) * float(smooth_weight)
+
+    t0 = clock()
+    d_positions = band.to_device_vector(disparities)
+    for view, unary in zip(out.views, unaries):
+        d_unary = torch.from_numpy(np.asfortranarray(unary).reshape(-1, order="F")).cuda()
+        r = aggregate_device(d_unary, (H, W), disparities, kernel, tol, directions, weights, d_positions=d_positions)
+        view.labels = r.labels.cpu().numpy()
+        view.dispmap = r.dispmap.cpu().numpy().T
+        view.maps.append(view.dispmap)
+    out.times["scanline"] = clock() - t0
+    t0 = clock()
+    for view, unary in zip(out.views, unaries):
+        view.energy.append(model_energy(unary, conn, alphas, disparities, kernel, tol, view.labels))
+        view.lower_bound.append(float("nan")); view.iterations.append(0); view.paths.append(0); view.carried.append(False)
+    out.times["energy"] = clock() - t0
+    t0 = clock()
+    for view, other, direction in ((out.left, out.right, 1), (out.right, out.left, -1)):
+        view.status, view.residual = consistency.lr_check(view.dispmap, other.dispmap, direction, check_tol)
+        view.filled, view.source = consistency.lr_fill(view.dispmap, view.status)
+    out.times["check_fill"] = clock() - t0
+
+    band_plans = {}
+    try:
+        if candidate_levels:
+            problems = [candidates.CandidateProblem(vol, disparities, unary_weight, view.dispmap, conn, alphas, layout=1)
+                        for vol, view in zip(volumes, out.views)]
+            consistency.run_band_levels(out, problems, candidate_levels, band_plans, kernel, conn, tol, maxiter, max_relgap,
+                                        check_tol, name="propagate")
+        if band_levels:
+            problems = [band.BandProblem(vol, disparities, unary_weight, view.dispmap, conn, alphas, layout=1)
+                        for vol, view in zip(volumes, out.views)]
+            consistency.run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol)
+    finally:
+        for plan in (p for pair in band_plans.values() for p in pair):
+            plan.close()
+    return out
