@@ -1277,11 +1277,12 @@ __device__ __forceinline__ void window_minplus(const double *hq, double alpha, d
 constexpr int kFlatFrom = STEREO_FLAT_FROM;
 struct CoopPart {
   int word = 0;   // bit 0: sharing; bit 1: this wave is the helper; bits 4-7: the helper's wave; bits 8-: what the flag must show
+  double *lds = nullptr;   // the kernel's dynamic LDS as the caller addresses it (a role function: pinned, trws_spec.h); set with bit 0
   __device__ __forceinline__ bool active() const { return word & 1; }
   __device__ __forceinline__ bool part() const { return (word >> 1) & 1; }
 };
 __device__ __forceinline__ void coop_publish(const CoopPart &c, double m1, double m2, int cnt, int lane) {
-  extern __shared__ __attribute__((aligned(16))) double coop_lds[];
+  double *coop_lds = c.lds;
   double *xd = coop_lds + kPipeXchgOff + ((c.word >> 4) & 15) * kPipeXchg;
   xd[lane] = m1; xd[kWave + lane] = m2; ((int *)(xd + 2 * kWave))[lane] = cnt;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1290,10 +1291,12 @@ __device__ __forceinline__ void coop_publish(const CoopPart &c, double m1, doubl
 // (the second smallest DISTINCT cost of the union: the part whose minimum is the overall minimum contributes its
 //  second smallest, the other its minimum)
 __device__ __forceinline__ void coop_collect(const CoopPart &c, double &m1, double &m2, int &cnt, int lane) {
-  extern __shared__ __attribute__((aligned(16))) double coop_lds[];
+  double *coop_lds = c.lds;
   const double *xd = coop_lds + kPipeXchgOff + ((c.word >> 4) & 15) * kPipeXchg;
   int *flag = (int *)(coop_lds + kPipeXflagOff) + ((c.word >> 4) & 15);
   int spins = 0;
+  // (one look per trip: unrolled sixteen times, the spin's exits cost the finishing wave a dozen scalar spills in front of it)
+#pragma nounroll
   while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != (c.word >> 8) && ++spins < kCoopSpinLimit) { }
   // (a partner that never publishes is a bug, not a state; what would be merged then is not a message: the launch gives up
   //  through the workgroup's abort word, like a dependency wait that ran out of time)

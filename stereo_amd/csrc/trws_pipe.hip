@@ -1,5 +1,7 @@
 // TRW-S pipelined sweep kernel for K <= 64 (both smoothness kernels): role-specialised waves, one
-// barrier per visit.  Part of libstereo_hip.so; overview in DESIGN.md 4.1, the run and visit frame in trws_visit.h.
+// barrier per visit, every role's visit loop a function of its own (pipe_compute, pipe_loader_b, pipe_loader_a,
+// pipe_storer, pipe_primal) that the kernel body (pipe_body) calls once per run.  Part of libstereo_hip.so; overview in
+// DESIGN.md 4.1, the run and visit frame in trws_visit.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -73,90 +75,79 @@ __device__ __forceinline__ void granule_delay(const DevParams &p, int node) {
 // schedule's kernels stay what they were.
 // BATCH: the body as trws_pipe_batch_kernel calls it, once per member of a batch (below): the one thing it adds is a mark
 // in ctl[2] -- the speculative kernel's verdict word, unused here -- once the workgroup holds a run of this member.
-template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED, bool SPEC = false, bool BATCH = false>
-__device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
-  static_assert(!SPEC || (SHARED && KERNEL == 1), "the speculative schedule exists for shared positions and the linear kernel");
-  static_assert(!(SPEC && BATCH), "batches keep the plain chain schedule");
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double *stage0 = lds;                                   // 2 stages
-  double *hand = lds + 2 * kStageDoubles;                 // ring of 4 x 8 x 64: the last visits' new messages
-  double *scal = hand + 4 * 8 * kWave;                    // 2 x kScalDoubles
-  double *hqtab = scal + 2 * kScalDoubles;                // per compute wave: 64 x (h, q, u, v)
-  int *ctl = (int *)(hqtab + kPipeCompute * kPipeTab);    // [0] run, [1] abort
-  int *dring = ctl + 4;                                   // the last three descriptors (the storer's comes from here, not from HBM)
-  double *zrow = (double *)(dring + 3 * kWave);           // 64 zeros: where the Di loop finds the message rows a node does not have
-  double *gtab = zrow + kWave;                            // gtab[k] = (double)1 / (double)k, k = 1 .. 8 (MRFEnergy.cpp:207-228), divided once
-  double *xchg = gtab + 16;                               // per compute wave (as helper): partial minima and match counts of a shared message
-  int *xflag = (int *)(xchg + kPipeCompute * kPipeXchg);  // ... and the flag behind them (CoopPart, trws_dev.h)
-  constexpr int D = BACKWARD ? 1 : 0;
-  // The runner of the speculative schedule holds ticket 0 of either direction, and the workgroup that draws it calls
-  // it HERE, before anything the visit loops keep in registers exists: a call in the ticket loop has all of that live
-  // across it, the compiler spills what the callee touches over its whole live range -- reloads inside the visit
-  // loops -- and which registers the callee touches changed with every edit of the runner (measured: a fifth of an
-  // iteration either way).  At this point only the kernel arguments are live.
-  bool have_ticket = false;
-  if (SPEC) {
-    if (threadIdx.x == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; }
-    if (draw_first_ticket<D>(p, ctl) == -1) chain_runner<PipeRunner, BACKWARD, PRIMAL, UPDATE>(p.self, epoch);
-    else have_ticket = true;
-  }
-  const int K = p.K;
-  const double inf = __builtin_huge_val();
-  const int tid = threadIdx.x, lane = tid & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-  constexpr int DW = TrwsGraph::kDescWords;
-  const int32_t *desc = p.desc[D];
-  const bool act = lane < K;
-  const double posk = (SHARED && act) ? p.pos[lane] : 0.0;
-  int look_streak = 0;  // failed second looks in a row (this compute wave): see message_regs
-  const int perm_shared = (SHARED && wave < kPipeCompute) ? (act ? (int)p.perm_pos[lane] : lane) : -1;  // source order by position, once
-  if (!SPEC && tid == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; }
-  if (tid < kWave) zrow[tid] = 0.0;
-  if (tid < 16) gtab[tid] = (double)1 / (double)(tid > 0 ? tid : 1);
-  if (tid < kPipeCompute) xflag[tid] = 0;
-  // A visit is bound by the instructions the CU's four SIMDs issue for all twelve waves (~4400 per visit
-  // before round 4, 45 % of them scalar), so the service waves are written branch-poor: no exec-mask region
-  // per row -- a lane beyond the last label works on label K - 1 again (loads read an element that exists,
-  // stores repeat lane K - 1's value at lane K - 1's address), a row the node does not have is skipped by
-  // ONE scalar branch on a uniform count or on a mask the host put into the descriptor (word 55: which
-  // incoming rows come from global memory), row addresses are one unsigned 32 x 32 -> 64 multiply and one
-  // shift-add on a per-lane base, and values one lane needs from another lane's descriptor word come by
-  // ds_bpermute instead of chains of eight compares and selects.
-#define PIPE_ROW(BASE, E) ((BASE) + (size_t)((unsigned long long)(unsigned)(E) * (unsigned long long)(unsigned)Kv))
-  if (wave < kPipeCompute && lane < 2 * kPipePad) {
-    // padding of the source tables (entries -16 .. -1 and 64 .. 79): never overwritten afterwards
-    double *e = hqtab + wave * kPipeTab + 4 * (lane < kPipePad ? lane : kWave + lane);
-    e[0] = inf; e[1] = 0; e[2] = 0; e[3] = 0;
-  }
-  if ((p.debug & 2) && !BACKWARD) p.prof = nullptr;  // profile backward sweeps only
-  if ((p.debug & 4) && BACKWARD) p.prof = nullptr;   // profile forward sweeps only
+//
+// ROLES: every role's visit loop is a real (noinline) function with a register allocation of its own, as the runner's
+// roles are (trws_spec.h).  In one function with the ticket loop, the commit, the profile epilogue and a by-value
+// parameter block of some seventy fields, the allocator spilled ~180 scalars into VGPR lanes by live ranges it cannot
+// weigh, and 55-70 v_readlane / v_writelane per visit sat on the finishing compute wave.
+// A role reads the parameter block from its copy in global memory -- through the constant address space and a uniform
+// address: scalar loads, as a kernel reads its arguments --, takes the run's values as arguments (they arrive in vector
+// registers and are declared uniform), addresses LDS through the dynamic allocation's own symbol, pinned, and hands back
+// what the kernel body needs of it: the busy cycles of the development profile, what the wave keeps from run to run
+// (the compute waves' look_streak) and whether it left through the abort word.  A spill in the caller is paid once per
+// run of hundreds of visits.
+struct PipeRoleResult {
+  unsigned long long busy;
+  int carry;
+  int aborted;
+};
+__device__ __forceinline__ PipeRoleResult pipe_role_result(unsigned long long busy, int carry, int aborted) {
+  PipeRoleResult r;
+  r.busy = busy; r.carry = carry; r.aborted = aborted;
+  return r;
+}
+// The parameter block as a role reads it: field by field from the constant address space at a uniform address -- every
+// load a scalar load, and a field the role does not use no load at all.  (EVERY field is named: one left out would read
+// as zero -- the copy is value-initialised -- in the roles and nowhere else.  Not a whole-struct copy: C++ cannot copy
+// a struct out of address space 4 (the copy constructor takes a generic reference), and the copy through a generic
+// pointer, left to the compiler to trace back to the constant address space, came out as flat loads into vector
+// registers, which the scalar constraints of the visit frame refuse.  trws_spec.h: uniform_params is the other such list.)
+typedef const __attribute__((address_space(4))) DevParams pipe_const_params;
+__device__ __forceinline__ DevParams pipe_role_params(const DevParams *pp_) {
+  static_assert(sizeof(DevParams) == 632, "a field was added to DevParams: name it below");
+  pipe_const_params *c = (pipe_const_params *)uniform_value(pp_);
+  DevParams q{};
+#define F(f) q.f = c->f;
+#define F2(f) q.f[0] = c->f[0]; q.f[1] = c->f[1];
+  F(K) F(Kp) F(kernel) F(lambda) F(unary) F(msg) F(q) F(qprim) F(pos) F(perm_q) F(perm_qp) F(perm_pos) F(alpha) F(mdir) F(tail) F(order)
+  F(fptr) F(fidx) F(bptr) F(bidx) F(gamma) F(lb_pos_node) F(lb_pos_edge) F(lbterms) F(eterms) F(x)
+  F2(run_ptr) F2(run_order) F2(nruns) F2(dep_ptr) F2(dep_rank) F2(in_slot)
+  F(done) F(ticket) F(abort_flag) F(spin_ticks) F(n_own) F(N) F(fallbacks) F(certificate) F(lean) F(prof) F2(desc) F(prof_run)
+  F(large_scratch) F(debug) F(timeline) F(window) F(uniform_step) F(win_ok) F(pos_gap) F(pos_first) F(pos_last) F2(ntickets)
+  F2(spec_kind) F2(spec_c0) F2(spec_c1) F(spec_len) F(spec_nseg) F(spec_max_len) F(spec_rows) F(spec_x) F(spec_undo) F(spec_stat)
+  F(tl_stride) F(self) F(peer_msg0) F(peer_msg1) F(peer_done0) F(peer_done1) F(peer_x0) F(peer_x1) F(gran) F(xgran) F2(run_rec)
+#undef F2
+#undef F
+  return q;
+}
 
-  for (;;) {
-    // (ctl[3]: the workgroup walks the speculative segment it holds a second time -- no new ticket)
-    TRWS_DRAW_TICKET(ctl, SPEC && (ctl[3] || have_ticket))
-    have_ticket = false;
-    // (the helpers' exchange flags show schedule positions: a second walk of a speculative segment visits the SAME
-    //  positions again, and a flag left by the first walk would pass for the helper's word of the second -- the
-    //  finishing wave would merge the first walk's partial minima, which are those of almost the same message.)
-    //  (development switch 131072: flags left as they are)
-    TRWS_RUN_ENTER(SPEC, ctl, if (tid < kPipeCompute && !(p.debug & 131072)) xflag[tid] = 0;)
-    TRWS_SPEC_SEGMENT
-    if (BATCH && tid == 0) ctl[2] = 1;
-    unsigned long long busy = 0;
+// A visit is bound by the instructions the CU's four SIMDs issue for all twelve waves (~4400 per visit
+// before round 4, 45 % of them scalar), so the service waves are written branch-poor: no exec-mask region
+// per row -- a lane beyond the last label works on label K - 1 again (loads read an element that exists,
+// stores repeat lane K - 1's value at lane K - 1's address), a row the node does not have is skipped by
+// ONE scalar branch on a uniform count or on a mask the host put into the descriptor (word 55: which
+// incoming rows come from global memory), row addresses are one unsigned 32 x 32 -> 64 multiply and one
+// shift-add on a per-lane base, and values one lane needs from another lane's descriptor word come by
+// ds_bpermute instead of chains of eight compares and selects.
+#define PIPE_ROW(BASE, E) ((BASE) + (size_t)((unsigned long long)(unsigned)(E) * (unsigned long long)(unsigned)Kv))
 #ifdef STEREO_HIP_VISIT_PROFILE
-    unsigned long long vacc[6] = {0, 0, 0, 0, 0, 0}, macc[5] = {0, 0, 0, 0, 0}, lacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define VSTAMP(i) do { const long long n_ = (long long)__builtin_readcyclecounter(); vacc[i] += (unsigned long long)(n_ - vmark); vmark = n_; } while (0)
 #define PIPE_VISIT_MARK long long vmark = (long long)__builtin_readcyclecounter();
+// (the stamps of the profile flavour are a role's own: it adds them up where the kernel body adds the busy cycles)
+#define PIPE_ROLE_STAMPS unsigned long long vacc[6] = {0, 0, 0, 0, 0, 0}, macc[5] = {0, 0, 0, 0, 0}, lacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#define PIPE_ROLE_STAMPS_OUT \
+  if (p.prof && lane == 0 && (p.prof_run < 0 || run == p.prof_run)) { \
+    if (wave == 0) for (int i = 0; i < 6; ++i) atomicAdd(p.prof + 48 + i, vacc[i]); \
+    if (wave == 0) for (int i = 0; i < 5; ++i) atomicAdd(p.prof + 56 + i, macc[i]); \
+    if (wave == kPipeCompute) for (int i = 0; i < 4; ++i) atomicAdd(p.prof + 16 + i, lacc[i]); \
+    if (wave == kPipeCompute + 1) for (int i = 4; i < 7; ++i) atomicAdd(p.prof + 16 + i, lacc[i]); \
+  }
 #else
 #define VSTAMP(i) do { } while (0)
 #define PIPE_VISIT_MARK
+#define PIPE_ROLE_STAMPS
+#define PIPE_ROLE_STAMPS_OUT
 #endif
-    int xprev = 0, xprev2 = 0;  // primal wave: labels of the previous two nodes of the run
-    int wnext = 0;              // loader: raw descriptor word of the node after next (prefetched)
-    if (wave == kPipeCompute) wnext = desc[(size_t)p0 * DW + lane];
-    // loader A (own data, two visits deep): descriptors of the next three nodes and the parked requests
-    int wa1 = 0, wa2 = 0, wa3 = 0;
-    double rdk = 0, rmv[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rqv[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rqpv[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rav = 0;
 #define PIPE_LOAD8(DST, PTR) DST = *(PTR)   /* plain loads: the compiler keeps them in flight across the barrier and waits at the first use */
 #define PIPE_REQUEST_OWN(W)                                                                          \
     do {                                                                                             \
@@ -172,23 +163,60 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
       }                                                                                              \
       rav = p.alpha[__shfl((W), 4 + (lane & 7), kWave)];  /* lane j: weight of the node's edge j (words of absent edges hold 0) */ \
     } while (0)
-    // storer: node pos's descriptor word (per lane), fetched during visit pos and used right behind the barrier that ends it
-    int sw = 0;
-    if (wave == kPipeCompute + 2) {
-      wa1 = desc[(size_t)p0 * DW + lane];
-      if (p0 + 1 < p1) wa2 = desc[(size_t)(p0 + 1) * DW + lane];
-      if (p0 + 2 < p1) wa3 = desc[(size_t)(p0 + 2) * DW + lane];
-      { const int Kv = K, lkv = lane < K ? lane : K - 1; PIPE_REQUEST_OWN(wa1); }
-    }
-    if (p.timeline && tid == 0) p.timeline[((size_t)D * p.tl_stride + run) * 2] = wall_clock64();
 
-    // every role walks the run in its own loop (trws_visit.h): four ring slots, the abort word looked at before the barrier
+// What every role is called with, and how it sets itself up: the parameter block, the run's values as uniform values,
+// the LDS carve of pipe_body (the one statement of the layout is there; kPipeLdsDoubles checks it), the names the visit
+// frame uses.  prof_on_: the kernel body's verdict on the development profile (switches 2 / 4: one direction only).
+#define PIPE_ROLE_PARAMS const DevParams *pp_, int epoch_, int p0_, int p1_, int run_, int seg_, int spec_in_, int second_walk_, int prof_on_
+#define PIPE_ROLE_ENTER                                                                                    \
+  extern __shared__ __attribute__((aligned(16))) double pipe_lds[];                                        \
+  DevParams p = pipe_role_params(pp_);                                                                     \
+  if (!__builtin_amdgcn_readfirstlane(prof_on_)) p.prof = nullptr;                                         \
+  const int epoch = __builtin_amdgcn_readfirstlane(epoch_), p0 = __builtin_amdgcn_readfirstlane(p0_),      \
+            p1 = __builtin_amdgcn_readfirstlane(p1_), run = __builtin_amdgcn_readfirstlane(run_),          \
+            seg = __builtin_amdgcn_readfirstlane(seg_), second_walk = __builtin_amdgcn_readfirstlane(second_walk_); \
+  const bool spec_in = __builtin_amdgcn_readfirstlane(spec_in_) != 0;                                      \
+  double *lds = pinned_lds(pipe_lds);                                                                      \
+  double *stage0 = lds, *hand = lds + 2 * kStageDoubles, *scal = hand + 4 * 8 * kWave;                     \
+  double *hqtab = scal + 2 * kScalDoubles;                                                                 \
+  int *ctl = (int *)(lds + kPipeCtlOff), *dring = ctl + 4;                                                 \
+  double *zrow = (double *)(dring + 3 * kWave), *gtab = zrow + kWave;                                      \
+  constexpr int D = BACKWARD ? 1 : 0, DW = TrwsGraph::kDescWords;                                          \
+  const int32_t *desc = p.desc[D];                                                                         \
+  const int K = p.K;                                                                                       \
+  const double inf = __builtin_huge_val();                                                                 \
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);                                                   \
+  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);                                            \
+  const bool act = lane < K;                                                                               \
+  unsigned long long busy = 0;                                                                             \
+  PIPE_ROLE_STAMPS                                                                                         \
+  (void)epoch; (void)run; (void)seg; (void)second_walk; (void)spec_in; (void)hqtab; (void)dring; (void)zrow; (void)gtab; \
+  (void)desc; (void)inf; (void)wave; (void)act; (void)DW;
+#define PIPE_ROLE_LEAVE(CARRY) \
+  PIPE_ROLE_STAMPS_OUT \
+  return pipe_role_result(busy, (CARRY), 0);
+
+// every role walks the run in its own loop (trws_visit.h): four ring slots, the abort word looked at before the barrier
 #define PIPE_VISITS_BEGIN \
     TRWS_VISITS_BEGIN(TRWS_BUSY_OPEN PIPE_VISIT_MARK, stage0, kStageDoubles, TRWS_RING4(hand, kWave), scal, TRWS_ABORT_LOOK(ctl) TRWS_OPAQUE_K)
 #define PIPE_VISITS_END \
-    TRWS_VISITS_END(TRWS_BUSY_CLOSE VSTAMP(4);, TRWS_ABORT_LEAVE(aborted_, ), __syncthreads(), VSTAMP(5);)
-    if (wave < kPipeCompute) {
-    // ---- compute
+    TRWS_VISITS_END(TRWS_BUSY_CLOSE VSTAMP(4);, TRWS_ABORT_LEAVE_WITH(aborted_, , pipe_role_result(0, 0, 1)), __syncthreads(), VSTAMP(5);)
+
+// ---- compute (waves 0-7).  look_streak_: failed second looks in a row of this wave (message_regs), kept from run to
+// run by the kernel body; posk, perm_shared: the lane's position and its place in the source order, read once per launch.
+template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED, bool SPEC>
+__device__ __attribute__((noinline)) PipeRoleResult pipe_compute(PIPE_ROLE_PARAMS, int look_streak_, double posk, int perm_shared) {
+    PIPE_ROLE_ENTER
+    int look_streak = __builtin_amdgcn_readfirstlane(look_streak_);
+#ifdef STEREO_HIP_VISIT_PROFILE
+    // wave 0's message stamps.  The array's address is made a value first: selected as it stands (wave == 0 ? macc : nullptr)
+    // in a function with a frame, this toolchain puts the s_add that forms the frame address between the compare and its
+    // s_cselect, the add overwrites SCC, and every wave gets the null pointer (seen in this flavour's assembly; the stamps read 0).
+    unsigned long long *macc_w0 = macc;
+    asm volatile("" : "+s"(macc_w0));
+    if (wave != 0) macc_w0 = nullptr;
+#endif
+    {
     PIPE_VISITS_BEGIN
       {
         // ------------------------------------------------------------ compute
@@ -260,13 +288,14 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
               if (SHARED && KERNEL == 1 && ((twin_mask >> j) & 1)) {
                 const int helper = j > partner ? j : partner;
                 cp.word = 1 | (j > partner ? 2 : 0) | (helper << 4) | (((pos + 1) & 0x7fffff) << 8);
+                cp.lds = lds;
               }
               VSTAMP(2);
               double newm = 0;
               const double v = message_regs<KERNEL, SHARED>(p, Kv, alpha, h, qsrc, qdst, perm, newm, lane,
                                                     hqtab + wave * kPipeTab + 4 * kPipePad, (SHARED && p.win_ok) ? p.window : -1, &look_streak
 #ifdef STEREO_HIP_VISIT_PROFILE
-                                                    , wave == 0 ? macc : nullptr
+                                                    , macc_w0
 #else
                                                     , nullptr
 #endif
@@ -296,8 +325,16 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
         }
       }
     PIPE_VISITS_END
-    } else if (wave == kPipeCompute) {
-    // ---- loader: stage node pos + 1
+    }
+    PIPE_ROLE_LEAVE(look_streak)
+}
+
+// ---- loader B (wave 8): stage node pos + 1 -- what comes from other runs, behind flags or as granules
+template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED, bool SPEC>
+__device__ __attribute__((noinline)) PipeRoleResult pipe_loader_b(PIPE_ROLE_PARAMS) {
+    PIPE_ROLE_ENTER
+    int wnext = desc[(size_t)p0 * DW + lane];   // raw descriptor word of the node after next (prefetched)
+    {
     PIPE_VISITS_BEGIN
       {
         // ------------------------------------------------------------ loader: stage node pos + 1
@@ -446,8 +483,22 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
         }
       }
     PIPE_VISITS_END
-    } else if (wave == kPipeCompute + 2) {
-    // ---- loader A: own data of node pos + 1
+    }
+    PIPE_ROLE_LEAVE(0)
+}
+
+// ---- loader A (wave 10): own data of node pos + 1, two visits deep -- descriptors of the next three nodes and the
+// parked requests
+template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED, bool SPEC>
+__device__ __attribute__((noinline)) PipeRoleResult pipe_loader_a(PIPE_ROLE_PARAMS) {
+    PIPE_ROLE_ENTER
+    int wa1 = 0, wa2 = 0, wa3 = 0;
+    double rdk = 0, rmv[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rqv[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rqpv[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rav = 0;
+    wa1 = desc[(size_t)p0 * DW + lane];
+    if (p0 + 1 < p1) wa2 = desc[(size_t)(p0 + 1) * DW + lane];
+    if (p0 + 2 < p1) wa3 = desc[(size_t)(p0 + 2) * DW + lane];
+    { const int Kv = K, lkv = lane < K ? lane : K - 1; PIPE_REQUEST_OWN(wa1); }
+    {
     PIPE_VISITS_BEGIN
       {
         // ------------------------------------------------------------ loader A: own data of node pos + 1
@@ -505,8 +556,17 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
         }
       }
     PIPE_VISITS_END
-    } else if (wave == kPipeCompute + 1) {
-    // ---- storer: node pos - 1
+    }
+    PIPE_ROLE_LEAVE(0)
+}
+
+// ---- storer (wave 9): node pos - 1.  sw: node pos's descriptor word (per lane), fetched during visit pos and used right
+// behind the barrier that ends it
+template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED, bool SPEC>
+__device__ __attribute__((noinline)) PipeRoleResult pipe_storer(PIPE_ROLE_PARAMS) {
+    PIPE_ROLE_ENTER
+    int sw = 0;
+    {
     PIPE_VISITS_BEGIN
       {
         // ------------------------------------------------------------ storer: node pos - 1
@@ -569,8 +629,16 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
         }
       }
     PIPE_VISITS_END
-    } else {
-    // ---- primal of node pos
+    }
+    PIPE_ROLE_LEAVE(0)
+}
+
+// ---- primal (wave 11): labelling + energy term of node pos.  xprev, xprev2: labels of the previous two nodes of the run
+template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED, bool SPEC>
+__device__ __attribute__((noinline)) PipeRoleResult pipe_primal(PIPE_ROLE_PARAMS, double posk) {
+    PIPE_ROLE_ENTER
+    int xprev = 0, xprev2 = 0;
+    {
     PIPE_VISITS_BEGIN
       {
         // ------------------------------------------------------------ primal of node pos
@@ -618,25 +686,103 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
       }
     PIPE_VISITS_END
     }
+    PIPE_ROLE_LEAVE(0)
+}
 #undef PIPE_VISITS_BEGIN
 #undef PIPE_VISITS_END
+#undef PIPE_ROLE_LEAVE
+#undef PIPE_ROLE_ENTER
+#undef PIPE_ROLE_STAMPS_OUT
+#undef PIPE_ROLE_STAMPS
+
+// ---- the kernel body: LDS tables, the ticket loop, the roles by wave, the commit of a speculative segment, the
+// development stamps.  pp: the block `p` was copied from, in global memory -- what the roles, the runner and the commit
+// read (a plan's own launches: p.self; a group's or a batch's: the strip's / member's entry of the launch's table).
+// TWO copies of the block, then: the ticket loop, the timeline and the stamps work from `p`, the roles from *pp.  What a
+// launch edits in its by-value copy only (trws_plan.hip: the timeline pointer cleared for STEREO_HIP_TRWS_TIMELINE=first)
+// the roles do not see; that is right only for fields no role reads, and `timeline` is the one such edit today.
+template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED, bool SPEC = false, bool BATCH = false>
+__device__ __forceinline__ void pipe_body(DevParams p, const DevParams *pp, int epoch) {
+  static_assert(!SPEC || (SHARED && KERNEL == 1), "the speculative schedule exists for shared positions and the linear kernel");
+  static_assert(!(SPEC && BATCH), "batches keep the plain chain schedule");
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  double *stage0 = lds;                                   // 2 stages
+  double *hand = lds + 2 * kStageDoubles;                 // ring of 4 x 8 x 64: the last visits' new messages
+  double *scal = hand + 4 * 8 * kWave;                    // 2 x kScalDoubles
+  double *hqtab = scal + 2 * kScalDoubles;                // per compute wave: 64 x (h, q, u, v)
+  int *ctl = (int *)(hqtab + kPipeCompute * kPipeTab);    // [0] run, [1] abort
+  int *dring = ctl + 4;                                   // the last three descriptors (the storer's comes from here, not from HBM)
+  double *zrow = (double *)(dring + 3 * kWave);           // 64 zeros: where the Di loop finds the message rows a node does not have
+  double *gtab = zrow + kWave;                            // gtab[k] = (double)1 / (double)k, k = 1 .. 8 (MRFEnergy.cpp:207-228), divided once
+  double *xchg = gtab + 16;                               // per compute wave (as helper): partial minima and match counts of a shared message
+  int *xflag = (int *)(xchg + kPipeCompute * kPipeXchg);  // ... and the flag behind them (CoopPart, trws_dev.h)
+  (void)stage0;
+  constexpr int D = BACKWARD ? 1 : 0;
+  // The runner of the speculative schedule holds ticket 0 of either direction, and the workgroup that draws it calls
+  // it HERE, before anything else: at this point only the kernel arguments are live.
+  bool have_ticket = false;
+  if (SPEC) {
+    if (threadIdx.x == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; }
+    if (draw_first_ticket<D>(p, ctl) == -1) chain_runner<PipeRunner, BACKWARD, PRIMAL, UPDATE>(pp, epoch);
+    else have_ticket = true;
+  }
+  const int K = p.K;
+  const double inf = __builtin_huge_val();
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const bool act = lane < K;
+  // (per lane, read once per launch and handed to the roles as vector arguments)
+  const double posk = (SHARED && act) ? p.pos[lane] : 0.0;
+  int look_streak = 0;  // failed second looks in a row (this compute wave): see message_regs
+  const int perm_shared = (SHARED && wave < kPipeCompute) ? (act ? (int)p.perm_pos[lane] : lane) : -1;  // source order by position, once
+  if (!SPEC && tid == 0) { ctl[1] = 0; ctl[2] = 0; ctl[3] = 0; }
+  if (tid < kWave) zrow[tid] = 0.0;
+  if (tid < 16) gtab[tid] = (double)1 / (double)(tid > 0 ? tid : 1);
+  if (tid < kPipeCompute) xflag[tid] = 0;
+  if (wave < kPipeCompute && lane < 2 * kPipePad) {
+    // padding of the source tables (entries -16 .. -1 and 64 .. 79): never overwritten afterwards
+    double *e = hqtab + wave * kPipeTab + 4 * (lane < kPipePad ? lane : kWave + lane);
+    e[0] = inf; e[1] = 0; e[2] = 0; e[3] = 0;
+  }
+  // development switches 2 / 4: profile backward / forward sweeps only
+  const int prof_on = (p.prof != nullptr && !((p.debug & 2) && !BACKWARD) && !((p.debug & 4) && BACKWARD)) ? 1 : 0;
+
+  for (;;) {
+    // (ctl[3]: the workgroup walks the speculative segment it holds a second time -- no new ticket)
+    TRWS_DRAW_TICKET(ctl, SPEC && (ctl[3] || have_ticket))
+    have_ticket = false;
+    // (the helpers' exchange flags show schedule positions: a second walk of a speculative segment visits the SAME
+    //  positions again, and a flag left by the first walk would pass for the helper's word of the second -- the
+    //  finishing wave would merge the first walk's partial minima, which are those of almost the same message.)
+    //  (development switch 131072: flags left as they are)
+    TRWS_RUN_ENTER(SPEC, ctl, if (tid < kPipeCompute && !(p.debug & 131072)) xflag[tid] = 0;)
+    TRWS_SPEC_SEGMENT
+    if (BATCH && tid == 0) ctl[2] = 1;
+    if (p.timeline && tid == 0) p.timeline[((size_t)D * p.tl_stride + run) * 2] = wall_clock64();
+    // every role walks the run in a function of its own (above); a wave is in one role for the whole launch
+#define PIPE_ROLE(NAME) NAME<KERNEL, BACKWARD, PRIMAL, UPDATE, SHARED, SPEC>
+#define PIPE_ROLE_ARGS pp, epoch, p0, p1, run, seg, spec_in ? 1 : 0, second_walk, prof_on
+    PipeRoleResult r;
+    if (wave < kPipeCompute) r = PIPE_ROLE(pipe_compute)(PIPE_ROLE_ARGS, look_streak, posk, perm_shared);
+    else if (wave == kPipeCompute) r = PIPE_ROLE(pipe_loader_b)(PIPE_ROLE_ARGS);
+    else if (wave == kPipeCompute + 2) r = PIPE_ROLE(pipe_loader_a)(PIPE_ROLE_ARGS);
+    else if (wave == kPipeCompute + 1) r = PIPE_ROLE(pipe_storer)(PIPE_ROLE_ARGS);
+    else r = PIPE_ROLE(pipe_primal)(PIPE_ROLE_ARGS, posk);
+#undef PIPE_ROLE_ARGS
+#undef PIPE_ROLE
+    if (__builtin_amdgcn_readfirstlane(r.aborted)) return;   // (the abort word: the wave leaves the kernel, trws_visit.h)
+    look_streak = r.carry;
     if (SPEC && seg >= 0) {
-      const int verdict = spec_commit<1, kPipeWaves, 2, BACKWARD, PRIMAL, UPDATE>(p.self, epoch, p0, p1, seg, spec_in ? 1 : 0, 2 * kPipeCtlOff);
+      const int verdict = spec_commit<1, kPipeWaves, 2, BACKWARD, PRIMAL, UPDATE>(pp, epoch, p0, p1, seg, spec_in ? 1 : 0, 2 * kPipeCtlOff);
       if (verdict == 2) return;
       if (verdict == 1) continue;   // (ctl[3] is set: the same run once more)
     }
     if (p.timeline && tid == 0) p.timeline[((size_t)D * p.tl_stride + run) * 2 + 1] = wall_clock64();
-    if (p.prof && lane == 0 && (p.prof_run < 0 || run == p.prof_run)) {
+    if (prof_on && lane == 0 && (p.prof_run < 0 || run == p.prof_run)) {
       // busy cycles before the barrier per role: compute (wave 0), loader, storer, primal; steps
       const int slot = wave == 0 ? 0 : wave == kPipeCompute ? 1 : wave == kPipeCompute + 1 ? 2 : wave == kPipeCompute + 3 ? 3 : -1;
-      if (slot >= 0) atomicAdd(p.prof + slot, busy);
-      atomicAdd(p.prof + 32 + wave, busy);  // every wave: cycles from barrier to barrier arrival
-#ifdef STEREO_HIP_VISIT_PROFILE
-      if (wave == 0) for (int i = 0; i < 6; ++i) atomicAdd(p.prof + 48 + i, vacc[i]);
-      if (wave == 0) for (int i = 0; i < 5; ++i) atomicAdd(p.prof + 56 + i, macc[i]);
-      if (wave == kPipeCompute) for (int i = 0; i < 4; ++i) atomicAdd(p.prof + 16 + i, lacc[i]);
-      if (wave == kPipeCompute + 1) for (int i = 4; i < 7; ++i) atomicAdd(p.prof + 16 + i, lacc[i]);
-#endif
+      if (slot >= 0) atomicAdd(p.prof + slot, r.busy);
+      atomicAdd(p.prof + 32 + wave, r.busy);  // every wave: cycles from barrier to barrier arrival
       if (wave == 0) atomicAdd(p.prof + 6, (unsigned long long)(p1 - p0));
     }
   }
@@ -644,17 +790,18 @@ __device__ __forceinline__ void pipe_body(DevParams p, int epoch) {
 
 template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED>
 __global__ __launch_bounds__(kPipeThreads) void trws_pipe_kernel(DevParams p, int epoch) {
-  pipe_body<KERNEL, BACKWARD, PRIMAL, UPDATE, SHARED>(p, epoch);
+  pipe_body<KERNEL, BACKWARD, PRIMAL, UPDATE, SHARED>(p, p.self, epoch);
 }
 
 template <bool BACKWARD, bool PRIMAL, bool UPDATE>
 __global__ __launch_bounds__(kPipeThreads) void trws_pipe_spec_kernel(DevParams p, int epoch) {
-  pipe_body<1, BACKWARD, PRIMAL, UPDATE, true, true>(p, epoch);
+  pipe_body<1, BACKWARD, PRIMAL, UPDATE, true, true>(p, p.self, epoch);
 }
 
 template <int KERNEL, bool BACKWARD, bool PRIMAL, bool UPDATE, bool SHARED>
 __global__ __launch_bounds__(kPipeThreads) void trws_pipe_group_kernel(GroupArgs ga, int epoch) {
-  pipe_body<KERNEL, BACKWARD, PRIMAL, UPDATE, SHARED>(ga.pp[group_strip(ga)], epoch);
+  const DevParams *pp = ga.pp + group_strip(ga);   // the strip's block
+  pipe_body<KERNEL, BACKWARD, PRIMAL, UPDATE, SHARED>(*pp, pp, epoch);
 }
 
 // Independent problems in one launch (stereo_trws_batch_*): the member frame of trws_visit.h around the
@@ -669,7 +816,7 @@ __global__ __launch_bounds__(kPipeThreads) void trws_pipe_batch_kernel(BatchArgs
   int *ctl = (int *)(lds + kPipeCtlOff);
   int *state = (int *)(lds + kPipeLdsDoubles);   // (behind the body's LDS: pipe_batch_lds_bytes)
   TRWS_MEMBERS_BEGIN(ba, group_strip(ba.g), state)
-    pipe_body<KERNEL, BACKWARD, PRIMAL, UPDATE, SHARED, false, true>(ba.g.pp[member], epoch);
+    pipe_body<KERNEL, BACKWARD, PRIMAL, UPDATE, SHARED, false, true>(ba.g.pp[member], ba.g.pp + member, epoch);   // (the member's block in the table)
   TRWS_MEMBERS_END(ba, ctl, state)
 }
 

@@ -679,7 +679,12 @@ static int strip_ready(stereo_trws_plan *P, const char *who, char *err, size_t e
 }
 
 // The parameters of a plan's OWN launches (speculative schedule included), with the block once more in global memory:
-// chain_runner / spec_commit read their parameters there; sent when it changes.
+// chain_runner / spec_commit and, in the K <= 64 kernels, every role of every launch (trws_pipe.hip) read their parameters
+// there; sent when it changes.  The copy is a blocking hipMemcpy and does not wait for a sweep issued ahead on a
+// non-blocking stream (issue_backward_ahead).  The last iteration of an iterate call issues nothing ahead; a call that
+// stops early on its gap leaves a sweep issued, and a block that CHANGES before the next call (another switch in the
+// environment, other inputs) would then be rewritten under that sweep -- as it always could under the speculative
+// runner; the block of an unchanged plan compares equal and is not sent again.
 static DevParams own_params(stereo_trws_plan *P, bool allow_sub = true) {
   const DevParams p = make_params(P, true, allow_sub);
   if (!P->self_sent || std::memcmp(P->h_self.p, &p, sizeof(DevParams)) != 0) {

@@ -113,6 +113,13 @@
         REPORT \
         return; \
       }
+// (the same where the visit loop stands in a role function of its own -- trws_pipe.hip --: the role hands VALUE back, and
+//  the kernel body that called it leaves the kernel)
+#define TRWS_ABORT_LEAVE_WITH(COND, REPORT, VALUE) \
+      if (COND) { \
+        REPORT \
+        return VALUE; \
+      }
 // Opaque copies of the label count, renewed every visit: what is derived from them -- per-lane row bases, the
 // label-count tests of the envelope code, ... -- is recomputed where it is used, one instruction each; left visible as
 // loop invariants, the compiler hoists dozens of such values out of the visit loop and keeps them in spilled
