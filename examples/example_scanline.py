@@ -1,12 +1,17 @@
 #!/usr/bin/env python
 """Scanline aggregation on the Teddy pair (tests/golden/teddy_pair.npz): both views, four ways to a map.
 
-    python examples/example_scanline.py [--disparities 60] [--maxiter 30] [--smooth-weight 1.0] [--record out.txt]
+    python examples/example_scanline.py [--disparities 60] [--maxiter 30] [--smooth-weight 1.0] [--levels trws|scanline|both]
+                                        [--record out.txt]
 
   (a) solve_pair_ncc: the full-range TRW-S solve, --maxiter iterations
   (b) solve_pair_ncc_scanline alone: 8 directions, every direction weighing --smooth-weight
   (c) (b) plus one K = 27 candidate level: offsets -1, 0, 1 and 12 taps on each of the sources 'base' and 'wta'
   (d) (c) plus the two sub-pixel band levels of examples/example_subpixel.py
+--levels says how the levels of (c) and (d) are solved: by TRW-S (the default, --maxiter iterations per level), by one
+scanline aggregation on the level's own inputs (level_solver="scanline"), or both ways side by side.  The
+output of --levels both behind DESIGN.md 6.11 is kept as profiles/scanline_levels_example.txt; whether a scanline level
+should become a default anywhere is decided later from that file, not here.
 
 The two NCC volumes are made once and handed to every variant (their time is printed once); each variant runs twice and
 the second run's wall time is the one reported, so that no variant pays for code objects and allocator warm-up.  Per
@@ -33,6 +38,7 @@ def main():
     ap.add_argument("--disparities", type=int, default=60)
     ap.add_argument("--maxiter", type=int, default=30)
     ap.add_argument("--smooth-weight", type=float, default=1.0)
+    ap.add_argument("--levels", choices=["trws", "scanline", "both"], default="trws", help="how the levels of (c) and (d) are solved")
     ap.add_argument("--record", help="write the printed lines to this file")
     args = ap.parse_args()
     import stereo_amd
@@ -46,7 +52,8 @@ def main():
         print(line, flush=True)
         lines.append(line)
 
-    say("example_scanline.py --disparities %d --maxiter %d --smooth-weight %g" % (args.disparities, args.maxiter, args.smooth_weight))
+    say("example_scanline.py --disparities %d --maxiter %d --smooth-weight %g --levels %s"
+        % (args.disparities, args.maxiter, args.smooth_weight, args.levels))
     t0 = time.perf_counter()
     volumes = consistency.pair_volumes(images, disparities)
     say("the two NCC volumes (shared by every variant): %.3f s" % (time.perf_counter() - t0))
@@ -56,11 +63,17 @@ def main():
         ("(a) solve_pair_ncc, %d iterations" % args.maxiter,
          lambda: stereo_amd.solve_pair_ncc(images, disparities, 1, 40.0, 8.0, args.maxiter, 0.0, check_tol=0.5, volumes=volumes)),
         ("(b) scanline alone", lambda: scanline.solve_pair_ncc_scanline(images, disparities, 1, 40.0, 8.0, **common)),
-        ("(c) scanline + candidates K = 27",
-         lambda: scanline.solve_pair_ncc_scanline(images, disparities, 1, 40.0, 8.0, candidate_levels=CANDIDATES, **common)),
-        ("(d) (c) + two sub-pixel band levels",
-         lambda: scanline.solve_pair_ncc_scanline(images, disparities, 1, 40.0, 8.0, candidate_levels=CANDIDATES, band_levels=BANDS, **common)),
     ]
+    for solver in (["trws", "scanline"] if args.levels == "both" else [args.levels]):
+        tag = "" if args.levels == "trws" else ", levels by %s" % solver
+        variants += [
+            ("(c) scanline + candidates K = 27" + tag,
+             lambda solver=solver: scanline.solve_pair_ncc_scanline(images, disparities, 1, 40.0, 8.0, candidate_levels=CANDIDATES,
+                                                                    level_solver=solver, **common)),
+            ("(d) (c) + two sub-pixel band levels" + tag,
+             lambda solver=solver: scanline.solve_pair_ncc_scanline(images, disparities, 1, 40.0, 8.0, candidate_levels=CANDIDATES,
+                                                                    band_levels=BANDS, level_solver=solver, **common)),
+        ]
     reference = None
     for name, run in variants:
         run()
@@ -76,9 +89,9 @@ def main():
                 status, _ = stereo_amd.lr_check(ref.dispmap, other.dispmap, direction, tol, want_residual=False)
                 shares.append(float(np.mean(status == 0)))
         far = float(np.mean(np.abs(out.left.dispmap - reference) > 2.0))
-        say("%-38s model energy of the left map %.4f; consistent at 0.5: left %.4f right %.4f, at 1.0: left %.4f right %.4f; "
+        say("%-58s model energy of the left map %.4f; consistent at 0.5: left %.4f right %.4f, at 1.0: left %.4f right %.4f; "
             "left pixels further than 2 from (a): %.4f; wall %.3f s" % (name, model.energy(), shares[0], shares[1], shares[2], shares[3], far, seconds))
-        say("%-38s passes: energy %s iterations %s; stages: %s"
+        say("%-58s passes: energy %s iterations %s; stages: %s"
             % ("", ["%.4f" % e for e in out.left.energy], [int(i) for i in out.left.iterations],
                "  ".join("%s %.3f s" % kv for kv in out.times.items())))
     if args.record:

@@ -39,8 +39,9 @@ extern "C" {
  * bands: per-pixel label sets propagated from neighbours).  18: stereo_plane_candidates_gather / _inputs_ncc /
  * _inputs_globalstereo / _apply (plane candidates: per-pixel plane sets propagated from neighbours).
  * 19: stereo_pyramid_expand_planes / _device (a plane map carried to the next finer scale as planes),
- * stereo_planes_fit_local / _device (the per-pixel local plane fit). */
-#define STEREO_HIP_ABI_VERSION 20
+ * stereo_planes_fit_local / _device (the per-pixel local plane fit).  20: stereo_scanline_aggregate / _device.
+ * 21: stereo_scanline_edges_* (scanline aggregation on per-edge positions and weights). */
+#define STEREO_HIP_ABI_VERSION 21
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -1179,6 +1180,80 @@ int stereo_scanline_aggregate_device(const double *unary, int H, int W, int D, c
                                      double tol, const int32_t *directions, const double *weights, int R, double *S,
                                      int32_t *labels, double *map, double *confidence, void *stream, char *err,
                                      size_t errcap);
+
+/* ---- scanline aggregation on per-edge positions ----------------------------------------- *
+ * The same dynamic programme on the general model a TRW-S plan is bound to.  No reference counterpart.
+ * Inputs: `unary` K x N, label fastest, N = H*W, pixel id p = y + H*x; `conn` 2 x E, zero based; `q` and `qprim`
+ * K x E, label fastest; `alphas` E doubles, finite and >= 0; kernel 1: v(d) = d, kernel 2: v(d) = d*d; tol >= 0;
+ * 1 <= K <= stereo_scanline_edges_max_labels() (64).
+ * Edge cost, for e = (i1, i2) = (conn[2e], conn[2e+1]):
+ *     c_e(x_i1, x_i2) = alphas_e * min(v(|qprim(x_i1, e) - q(x_i2, e)|), tol)   (the product last, every operation
+ *                                                                                rounded once)
+ * Graph: every edge joins two 4-neighbours of the H x W grid; a neighbour pair carries at most one edge in each
+ * orientation (none, one or two edges); edges come in any order.  An edge that is a self-loop, out of range, not
+ * between 4-neighbours (the last row of one column and the first of the next are no neighbours), or a second edge in
+ * an occupied slot is refused.
+ * Edge table: `table`, 4*N int32, two slots for each of two axes per pixel p.  Axis 0 is the pair (p - 1, p) in a
+ * column, axis 1 the pair (p - H, p) in a row.  Slot 0 is the id of the edge oriented from the smaller pixel id to the
+ * larger, slot 1 the reverse; -1 where the edge is absent or the neighbour lies outside the image.
+ *     table[slot + 2*(axis + 2*p)]
+ * Step table, for pixel p with label k and its predecessor p' with label l:
+ *     T[k, l] = c_a(.) + c_b(.)        a, b the two slots of the pair, each with its arguments in its own orientation;
+ *                                      an absent slot contributes +0.0 (two non-negative terms: any order)
+ * Recurrence: `directions` are R pairs (dy, dx) out of (0, 1), (0, -1), (1, 0), (-1, 0), 1 <= R <= 8, duplicates
+ * allowed; the model has no diagonal edges, so a diagonal is refused.  There are no per-direction weights: `alphas`
+ * are the weights.  The predecessor of (y, x) is (y - dy, x - dx):
+ *     L_r(p, k) = U(p, k)                                         where p' is outside the image,
+ *     L_r(p, k) = U(p, k) + min_l (L_r(p', l) + T[k, l])          otherwise.
+ * The minimum is not subtracted.  A pair without any edge has T = 0: the chain is not cut, L is still the half
+ * chain's exact minimum energy.
+ *     S = ((L_1 + L_2) + ...)    in list order, K x N
+ *     labels[p]     = the first minimum of S(p, .), ONE based
+ *     confidence[p] = the second-smallest entry of S(p, .) - min S(p, .): 0 at a tie, +Inf at K = 1
+ * There is no map: positions are per edge, the caller applies the labels as a level does.
+ * Every candidate L + T is one add, U + min is one add, T is one add of two products, a minimum of finite doubles is
+ * order-free: for finite inputs S, labels and confidence are these lines' bits (fp64 without FMA contraction).
+ *
+ * Refused with a message, before the device is looked for: H or W below 1; H*W >= 2^31; K outside 1 .. 64; kernel
+ * other than 1 / 2; tol negative or NaN; R outside 1 .. 8; a direction outside the four; E < 0 or E >= 2^31; NULL for
+ * a required array (E = 0 allows NULL conn, q, qprim, alphas; every T is then 0 and S(p, .) is R * U(p, .) plus one
+ * constant per pixel, the minima of the pixels before p along each direction); S == unary. */
+int stereo_scanline_edges_max_labels(void);
+/* The edge table of `conn` on the host, no device needed: `table` (4*H*W int32) is written.  The message names the
+ * first offending edge. */
+int stereo_scanline_edges_table(const uint32_t *conn, int64_t E, int H, int W, int32_t *table, char *err,
+                                size_t errcap);
+/* The same on device arrays, launched on `stream` without waiting for it: `table` is filled with -1, `bad` (one
+ * int32) zeroed, then one thread per edge writes its slot; an invalid edge, or one whose slot is taken, adds one to
+ * `bad` and writes nothing. */
+int stereo_scanline_edges_table_device(const uint32_t *conn, int64_t E, int H, int W, int32_t *table, int32_t *bad,
+                                       void *stream, char *err, size_t errcap);
+/* On host arrays.  Builds the table itself (an invalid `conn` is refused with the table's message) and also refuses
+ * a value of `unary`, `q` or `qprim` that is not finite and an alpha that is negative or not finite.  S and
+ * confidence may be NULL. */
+int stereo_scanline_edges_aggregate(int kernel, const double *unary, int H, int W, int K, int64_t E,
+                                    const uint32_t *conn, const double *q, const double *qprim, const double *alphas,
+                                    double tol, const int32_t *directions, int R, double *S, int32_t *labels,
+                                    double *confidence, char *err, size_t errcap);
+/* The same on device arrays of the caller with the table made before (stereo_scanline_edges_table_device, `bad` 0),
+ * launched on `stream` without waiting for it: one launch per direction and one for the reduction.  `directions`
+ * stays a HOST array.  S is required (the workspace the directions add into, and the output); confidence may be
+ * NULL.  The inputs must be finite; for other values the call promises only labels in 1 .. K and no access outside
+ * its arrays, as long as the table's entries are -1 or edge ids below E. */
+int stereo_scanline_edges_aggregate_device(int kernel, const double *unary, int H, int W, int K, int64_t E,
+                                           const int32_t *table, const double *q, const double *qprim,
+                                           const double *alphas, double tol, const int32_t *directions, int R,
+                                           double *S, int32_t *labels, double *confidence, void *stream, char *err,
+                                           size_t errcap);
+/* The N unary terms unary[labels_p - 1, p], then the E edge terms c_e(labels_i1, labels_i2) of a labelling, into
+ * `terms` (N + E doubles on the device), each with the definition's operations; the level's model energy is their sum.
+ * `bad` (one int32, zeroed on the stream first) counts labels outside 1 .. K; a term such a label, or an endpoint
+ * outside 0 .. N-1, takes part in is written as 0.  Refused: N < 1 or N >= 2^31, K outside 1 .. 64, kernel, tol and
+ * E as above, NULL for a required array (E = 0 allows NULL conn, q, qprim, alphas). */
+int stereo_scanline_edges_energy_device(int kernel, const double *unary, int K, int64_t N, int64_t E,
+                                        const uint32_t *conn, const double *q, const double *qprim,
+                                        const double *alphas, double tol, const int32_t *labels, double *terms,
+                                        int32_t *bad, void *stream, char *err, size_t errcap);
 
 /* ---- device-resident fusion moves --------------------------------------- *
  * The state of one dispmap object kept in HBM across moves: connectivity, weights, points,

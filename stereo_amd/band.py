@@ -257,7 +257,19 @@ class BandResult(LevelsResult):
         self.dispmap = self.stage = None
 
 
-def run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, carry=False, start=None):
+SOLVERS = ("trws", "scanline")
+
+
+def check_solver(solver, carry=False, start=None):
+    """`solver` of a level loop: "trws", or "scanline" (DESIGN.md 6.11), which has no messages to carry."""
+    if solver not in SOLVERS:
+        raise StereoHipError("solver must be 'trws' or 'scanline' (got %r)" % (solver,))
+    if solver == "scanline" and (carry or start is not None):
+        raise StereoHipError("solver='scanline' has no messages to carry: carry and a carried start need solver='trws'")
+    return solver
+
+
+def run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, carry=False, start=None, solver="trws"):
     """The level loop of refine_band, refine_plane_band, refine_candidates and refine_plane_candidates.  For each of the
     checked `levels`: a TrwsPlan(kernel, K, N, conn) -- one per distinct K, made here and closed here -- is bound to the
     level's inputs, iterated up to `maxiter` times (`max_relgap` as in trws) and read, `out`'s (LevelsResult) lists
@@ -269,7 +281,20 @@ def run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, carry=False,
     to `plan`, which starts from the carry.Carry `carry` if that is not None; leave(plan, labels) -> what the solved
     level leaves for the next one, taken before apply() (a plan is reused for equal K and the next bind wipes it);
     apply(labels) moves the problem on and returns the new map for the host; carry_from(left) -> the Carry into the
-    next build from what leave() gave, taken after apply() (None for None)."""
+    next build from what leave() gave, taken after apply() (None for None).
+
+    solver="scanline" (DESIGN.md 6.11): no TrwsPlan is made.  build(level, None, tol) leaves the level's inputs bound
+    to nothing and the level is one scanline aggregation over the four axis directions on them (scanline.solve_level:
+    K <= 64, `prob.conn` a grid's, its edge table built once and kept on the problem).  out.energy gets the labels'
+    model energy, lower_bound NaN, iterations 0, paths 0 and carried False; carry and start are refused."""
+    if check_solver(solver, carry, start) == "scanline":
+        from . import scanline
+        for level in levels:
+            labels, en, lb, it = scanline.solve_level(prob, level, kernel, tol).result()
+            out.carried.append(False); out.paths.append(0)
+            out.labels.append(labels); out.energy.append(en); out.lower_bound.append(lb); out.iterations.append(it)
+            out.maps.append(prob.apply(labels))
+        return None
     plans, previous, left = {}, start, None
     try:
         for level in levels:
@@ -294,8 +319,11 @@ def run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, carry=False,
 
 def bind_inputs(prob, plan, tol):
     """The inputs a build() has just made (prob.d_unary, d_q, d_qprim; torch's current stream has to finish them first)
-    bound to `plan` with the problem's smoothness weights."""
+    bound to `plan` with the problem's smoothness weights.  plan None: the inputs stay as they are, bound to nothing
+    (a level that another solver takes from the problem's tensors)."""
     import torch
+    if plan is None:
+        return
     torch.cuda.current_stream().synchronize()
     plan.bind_device(prob.d_unary.data_ptr(), prob.d_alphas.data_ptr(), tol, d_q=prob.d_q.data_ptr(),
                      d_qprim=prob.d_qprim.data_ptr(), keepalive=[prob.d_unary, prob.d_q, prob.d_qprim, prob.d_alphas])
@@ -347,8 +375,8 @@ class BandProblem:
         """K of the level `level` (here: a vector of offsets), before it is built."""
         return level.shape[0]
 
-    def build(self, offsets, plan, tol, zero_columns=None, carry=None):
-        """The inputs of the level `offsets` around the current base, bound to `plan`.  zero_columns: a bool tensor (N,),
+    def build(self, offsets, plan=None, tol=0.0, zero_columns=None, carry=None):
+        """The inputs of the level `offsets` around the current base, bound to `plan` (None: to nothing).  zero_columns: a bool tensor (N,),
         pixels whose unary column is set to zero.  carry: a carry.Carry of the previous stage (whose messages were saved
         BEFORE this call: a plan is reused for equal K and the bind wipes it); the plan then starts from the transferred
         messages as a state of phase 1 with 0 iterations, not from zero."""
@@ -390,7 +418,7 @@ class BandProblem:
 
 
 def refine_band(ncc, disparities, unary_weight, base, kernel, tol, levels, maxiter, max_relgap, alphas=None, layout=0,
-                conn=None, carry=False, carry_start=None):
+                conn=None, carry=False, carry_start=None, solver="trws"):
     """Refines the map `base` level by level: for each vector of offsets in `levels` the band problem around the current
     map is built on the device (stereo_band_inputs_device), bound to a TrwsPlan(kernel, K, N, conn) -- one plan per
     distinct K -- iterated up to `maxiter` times (`max_relgap` as in trws) and applied (stereo_band_apply_device); the
@@ -398,7 +426,9 @@ def refine_band(ncc, disparities, unary_weight, base, kernel, tol, levels, maxit
     conn: 2 x E zero based, default the image grid (construct_neighborhood).  carry=True: every level after the first
     starts from the previous level's messages, moved onto its own offsets, not from zero; the last
     level's carry.Stage is then kept as the result's `stage`.  carry_start: (a carry.Stage, scales) the first level
-    starts from -- a solve on this grid, or with scales=True on the grid one box reduction coarser.  -> BandResult."""
+    starts from -- a solve on this grid, or with scales=True on the grid one box reduction coarser.  solver: "trws", or
+    "scanline" -- every level one scanline aggregation on its inputs (run_levels; no carry).  -> BandResult."""
+    check_solver(solver, carry, carry_start)
     levels = check_levels(levels)
     base = _map(base, "base")
     H, W = base.shape
@@ -406,6 +436,6 @@ def refine_band(ncc, disparities, unary_weight, base, kernel, tol, levels, maxit
     prob = BandProblem(ncc, disparities, unary_weight, base, conn, alphas, layout)
     out = BandResult()
     start = prob.carry_from(carry_start[0], carry_start[1]) if carry_start is not None else None
-    out.stage = run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, carry, start)
+    out.stage = run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, carry, start, solver)
     out.dispmap = out.maps[-1]
     return out

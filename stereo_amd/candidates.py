@@ -301,8 +301,9 @@ class CandidateProblem(band.BandProblem):
                 maps.append(torch.from_numpy(np.ascontiguousarray(s.T)).cuda())
         return torch.stack(maps).contiguous() if maps and level["taps"].shape[0] else None
 
-    def build(self, level, plan, tol, zero_columns=None, carry=None):
-        """The inputs of the candidate level `level` (check_level's dict) around the current base, bound to `plan`.
+    def build(self, level, plan=None, tol=0.0, zero_columns=None, carry=None):
+        """The inputs of the candidate level `level` (check_level's dict) around the current base, bound to `plan` (None:
+        to nothing).
         zero_columns: as in BandProblem.build.  carry must be None."""
         if carry is not None:
             raise StereoHipError("candidates: a candidate level does not take carried messages")
@@ -330,19 +331,21 @@ class CandidateProblem(band.BandProblem):
 
 
 def refine_candidates(ncc, disparities, unary_weight, base, kernel, tol, levels, maxiter, max_relgap, alphas=None, layout=0,
-                      conn=None):
+                      conn=None, solver="trws"):
     """Refines the map `base` level by level: for each candidate level in `levels` -- dict(offsets=, taps=, sources=),
     a source being an H x W map, 'base' (the current map) or 'wta' (the volume's ncc_best_disp map, computed once) --
     the table is gathered around the current map on the device, its problem built (stereo_candidates_inputs_device),
     bound to a TrwsPlan(kernel, K, N, conn) -- one plan per distinct K -- iterated up to `maxiter` times and applied;
     the selected map is the next level's base.  Nothing K x N or K x E touches the host.  conn: 2 x E zero based,
-    default the image grid.  Every level starts from zero messages.  -> band.BandResult (`carried` all False)."""
+    default the image grid.  Every level starts from zero messages.  solver: "trws", or "scanline" -- every level one scanline
+    aggregation on its inputs (band.run_levels).  -> band.BandResult (`carried` all False)."""
+    band.check_solver(solver)
     levels = check_levels(levels)
     base = _map(base, "base")
     H, W = base.shape
     conn = T.construct_neighborhood(H, W) if conn is None else conn
     prob = CandidateProblem(ncc, disparities, unary_weight, base, conn, alphas, layout)
     out = band.BandResult()
-    run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap)
+    run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, solver=solver)
     out.dispmap = out.maps[-1]
     return out

@@ -212,7 +212,7 @@ def collect_views(out, plans, to_map, check_tol, stage):
 
 
 def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
-                    zero_occluded=False, carry=False, stages=None, scales=False, name="band"):
+                    zero_occluded=False, carry=False, stages=None, scales=False, name="band", solver="trws"):
     """The band passes of a pair solve: for every vector of offsets both views (`problems`: one band.BandProblem each,
     standing around the view's current map) build their band problem on the device and run up to `maxiter` iterations
     as a two-member TrwsBatch; the labels are applied, the refined maps checked with `check_tol` and filled
@@ -224,8 +224,25 @@ def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, m
     carry: every level after the first starts from the view's previous level's messages; the members
     take them as batch members take any state.  stages: per view the carry.Stage the FIRST level starts from (None:
     from zero) -- a solve on this grid, or with scales=True on the grid one box reduction coarser.  out.stages: per
-    view the Stage of the last level (with carry)."""
+    view the Stage of the last level (with carry).
+    solver="scanline" (DESIGN.md 6.11): no plan is made and band_plans stays as it is; each view's level is aggregated in
+    turn on the current stream (scanline.solve_level) and collected as a plan's result is: the labels' model energy,
+    bound NaN, iterations 0, path 0.  carry and stages are refused."""
     import torch
+    from . import band
+    if band.check_solver(solver, carry, stages) == "scanline":
+        from . import scanline
+        for level, offsets in enumerate(band_levels):
+            t0 = time.perf_counter()
+            solved = []
+            for prob, view in zip(problems, out.views):
+                occluded = torch.from_numpy(view.status.T.reshape(-1) == OCCLUDED).cuda() if zero_occluded else None
+                solved.append(scanline.solve_level(prob, offsets, kernel, tol, zero_columns=occluded))
+                view.carried.append(False)
+            out.times["%s_%d" % (name, level + 1)] = time.perf_counter() - t0
+            collect_views(out, solved, lambda i, labels: problems[i].apply(labels), check_tol,
+                          "%s_%d_check_fill" % (name, level + 1))
+        return
     N = problems[0].N
     previous = [prob.carry_from(st, scales) for prob, st in zip(problems, stages)] if stages is not None else [None, None]
     for level, offsets in enumerate(band_levels):

@@ -36,6 +36,7 @@
 #include <string>
 
 #include "common.h"
+#include "scanline_finish.h"
 #include "stereo_hip.h"
 
 namespace {
@@ -321,15 +322,20 @@ void launch_all(const double *unary, int H, int W, int D, const double *position
                 double *confidence, hipStream_t s) {
   for (int r = 0; r < R; ++r)
     launch_direction(unary, positions, H, W, D, kernel, tol, weights[r], directions[2 * r], directions[2 * r + 1], r > 0, S, s);
-  const int64_t N = (int64_t)H * W;
+  stereo::scanline_finish(S, positions, D, (int64_t)H * W, labels, map, confidence, s);
+}
+
+}  // namespace
+
+// (scanline_finish.h: the reduction as scanline_edges.hip launches it too)
+void stereo::scanline_finish(const double *S, const double *positions, int D, int64_t N, int32_t *labels, double *map,
+                             double *confidence, hipStream_t s) {
   const int lg = lanes_log2(D);
   const int64_t per_block = (int64_t)(kFinishBlock / kWave) * (kWave >> lg);
   hipLaunchKernelGGL(scanline_finish_kernel, dim3((unsigned)((N + per_block - 1) / per_block)), dim3(kFinishBlock), 0, s, S,
                      positions, D, N, lg, labels, map, confidence);
   STEREO_HIP_CHECK(hipGetLastError());
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -354,11 +354,11 @@ class dispmap_super:
         self.filled_dispmap, self.filled_source = consistency.lr_fill(d, self.consistency) if fill else (None, None)
         return self.consistency, self.filled_dispmap
 
-    def refine_band(self, levels, maxiter=None, carry=False):
+    def refine_band(self, levels, maxiter=None, carry=False, solver="trws"):
         raise StereoHipError("refine_band: %s does not take its unary from the NCC sampler; band refinement is defined "
                              "for dispmap_ncc" % type(self).__name__)
 
-    def refine_candidates(self, levels, maxiter=None):
+    def refine_candidates(self, levels, maxiter=None, solver="trws"):
         raise StereoHipError("refine_candidates: %s does not take its unary from the NCC sampler; candidate bands are "
                              "defined for dispmap_ncc" % type(self).__name__)
 
@@ -375,14 +375,15 @@ class dispmap_super:
         planes' disparity units or None for 'as they are')."""
         raise StereoHipError("refine_plane_band: %s names no unary source" % type(self).__name__)
 
-    def refine_plane_band(self, levels, maxiter=None, carry=False):
+    def refine_plane_band(self, levels, maxiter=None, carry=False, solver="trws"):
         """Sub-pixel refinement that keeps each pixel's plane (no reference counterpart): for every
         vector of offsets in `levels` (strictly ascending, containing 0) TRW-S chooses per pixel among the pixel's own
         plane moved by an offset along the disparity axis, [a b c d - c offset], with this object's unary, kernel,
         tolerance, smoothness weights, rescaling and max_relgap, up to `maxiter` (default self.maxiter) iterations per
         level.  The levels are in the units of the object's smoothness term: disparities for dispmap_ncc, the rescaled
         units in which disp_thresh lives for dispmap_globalstereo.  carry=True: every level after the first starts from
-        the previous level's messages (DESIGN.md 6.5).  The result goes in through the assignment setter;
+        the previous level's messages.  solver="scanline": every level is one scanline aggregation on its
+        inputs, not a TRW-S solve (DESIGN.md 6.11; no carry).  The result goes in through the assignment setter;
         returns plane_band.refine_plane_band's PlaneBandResult (planes in the object's internal columns)."""
         from . import plane_band
         levels = plane_band.check_levels(levels)
@@ -392,7 +393,7 @@ class dispmap_super:
         out = plane_band.refine_plane_band(source, self.assignment, self._kernel, self.tol, levels,
                                            self.maxiter if maxiter is None else maxiter, self._max_relgap,
                                            alphas=self.smooth_weights, conn=self.neighborhood, d_min=self.d_min,
-                                           d_step=self.d_step, carry=carry)
+                                           d_step=self.d_step, carry=carry, solver=solver)
         self.assignment = out.planes
         return out
 
@@ -401,14 +402,15 @@ class dispmap_super:
         columns, with the source forms of the class resolved to 4 x N planes."""
         return level
 
-    def refine_plane_candidates(self, levels, maxiter=None):
+    def refine_plane_candidates(self, levels, maxiter=None, solver="trws"):
         """Plane propagation around the current assignment (no reference counterpart): for every
         plane-candidate level in `levels` -- dict(offsets=, taps=, sources=), a source being 'base' (the current planes)
         or 4 x N planes -- TRW-S chooses per pixel among the pixel's own plane moved by an offset along the disparity
         axis and the sources' planes at the taps, copied unchanged (a neighbour's surface extended to this pixel), with
         this object's unary, kernel, tolerance, smoothness weights, rescaling and max_relgap, up to `maxiter` (default
         self.maxiter) iterations per level.  The offsets are in the units of refine_plane_band's levels.  4 x N sources
-        are in the object's internal columns, as `assignment` is.  The result goes in through the assignment setter;
+        are in the object's internal columns, as `assignment` is.  solver="scanline": every level is one scanline
+        aggregation on its inputs (DESIGN.md 6.11).  The result goes in through the assignment setter;
         returns plane_candidates.refine_plane_candidates's PlaneBandResult (planes in the object's internal columns)."""
         from . import plane_candidates
         if isinstance(levels, dict):
@@ -420,7 +422,7 @@ class dispmap_super:
         out = plane_candidates.refine_plane_candidates(source, self.assignment, self._kernel, self.tol, levels,
                                                        self.maxiter if maxiter is None else maxiter, self._max_relgap,
                                                        alphas=self.smooth_weights, conn=self.neighborhood, d_min=self.d_min,
-                                                       d_step=self.d_step)
+                                                       d_step=self.d_step, solver=solver)
         self.assignment = out.planes
         return out
 
@@ -509,28 +511,30 @@ class dispmap_ncc(dispmap_super):
         return scanline.aggregate(unary, (H, W), self.disparities, self._kernel, self._tol,
                                   scanline.DIRECTIONS_8 if directions is None else directions, weights, want_volume=True)
 
-    def refine_band(self, levels, maxiter=None, carry=False):
+    def refine_band(self, levels, maxiter=None, carry=False, solver="trws"):
         """Sub-pixel refinement of the current map (no reference counterpart): for every vector of offsets in
         `levels` (strictly ascending, containing 0) TRW-S chooses per pixel among current disparity + offset, with this
         object's volume, unary weight, kernel, tolerance, smoothness weights and max_relgap, up to `maxiter` (default
         self.maxiter) iterations per level.  carry=True: every level after the first starts from the previous level's
-        messages.  The result goes in through set_disparity; returns band.refine_band's
+        messages.  solver="scanline": every level is one scanline aggregation on its inputs, not a TRW-S
+        solve (no carry).  The result goes in through set_disparity; returns band.refine_band's
         BandResult (its maps are in the object's internal columns: flipped for a mirrored object)."""
         from . import band
         base = self.disparitymap_from_assignment(self.assignment).reshape(self.sz[1], self.sz[0]).T    # internal columns
         out = band.refine_band(self.ncc, self.disparities, self._unary_weight, base, self._kernel, self._tol, levels,
                                self.maxiter if maxiter is None else maxiter, self._max_relgap, alphas=self.smooth_weights,
-                               conn=self.neighborhood, carry=carry)
+                               conn=self.neighborhood, carry=carry, solver=solver)
         self.set_disparity(self._unflip(out.dispmap))
         return out
 
-    def refine_candidates(self, levels, maxiter=None):
+    def refine_candidates(self, levels, maxiter=None, solver="trws"):
         """Propagation around the current map (no reference counterpart): for every candidate level in
         `levels` -- dict(offsets=, taps=, sources=), a source being 'base' (the current map), 'wta' (this volume's
         best_disp_from_ncc map) or an H x W map in the coordinates current_dispmap() speaks -- TRW-S chooses per pixel
         among current disparity + offset and the sources' values at the taps, with this object's volume, unary weight,
         kernel, tolerance, smoothness weights and max_relgap, up to `maxiter` (default self.maxiter) iterations per
-        level.  The result goes in through set_disparity; returns candidates.refine_candidates's BandResult (its maps
+        level.  solver="scanline": every level is one scanline aggregation on its inputs.
+        The result goes in through set_disparity; returns candidates.refine_candidates's BandResult (its maps
         are in the object's internal columns: flipped for a mirrored object; the caller's maps and the taps' dx are
         in the image's own columns and are flipped on the way in)."""
         from . import candidates
@@ -541,7 +545,7 @@ class dispmap_ncc(dispmap_super):
         base = self.disparitymap_from_assignment(self.assignment).reshape(self.sz[1], self.sz[0]).T    # internal columns
         out = candidates.refine_candidates(self.ncc, self.disparities, self._unary_weight, base, self._kernel, self._tol, levels,
                                            self.maxiter if maxiter is None else maxiter, self._max_relgap,
-                                           alphas=self.smooth_weights, conn=self.neighborhood)
+                                           alphas=self.smooth_weights, conn=self.neighborhood, solver=solver)
         self.set_disparity(self._unflip(out.dispmap))
         return out
 

@@ -22,7 +22,7 @@ from . import carry as carry_mod
 from . import terms as T
 from ._lib import StereoHipError
 from .band import (LevelsResult, _bad, _conn, _device_labels, _device_vectors, _edges, _flat, _out, _raise_bad, _vec, _volume,
-                   _vp, bind_inputs, check_levels, run_levels, to_device_vector)
+                   _vp, bind_inputs, check_levels, check_solver, run_levels, to_device_vector)
 from .consistency import _p, _stream
 
 
@@ -281,8 +281,8 @@ class PlaneBandProblem:
         """The Carry into the next build from what leave() gave: that itself (it does not depend on the planes)."""
         return left
 
-    def build(self, offsets, plan, tol, carry=None):
-        """The inputs of the level `offsets` around the current planes, bound to `plan`.  carry: a carry.Carry of the
+    def build(self, offsets, plan=None, tol=0.0, carry=None):
+        """The inputs of the level `offsets` around the current planes, bound to `plan` (None: to nothing).  carry: a carry.Carry of the
         previous level; the plan then starts from the transferred messages, not from zero."""
         self.offsets = _vec(offsets, "offsets")
         self.d_offsets = to_device_vector(self.offsets)
@@ -299,7 +299,7 @@ class PlaneBandProblem:
 
 
 def refine_plane_band(source, planes, kernel, tol, levels, maxiter, max_relgap, alphas=None, conn=None, d_min=0.0, d_step=0.0,
-                      carry=False):
+                      carry=False, solver="trws"):
     """Refines the plane map `planes` (4 x N) level by level: for each vector of offsets in `levels` (the planes' own
     disparity units) the plane-band problem around the current planes is built on the device
     (stereo_plane_band_inputs_*_device), bound to a TrwsPlan(kernel, K, N, conn) -- one plan per distinct K -- iterated up
@@ -307,12 +307,14 @@ def refine_plane_band(source, planes, kernel, tol, levels, maxiter, max_relgap, 
     the next level's.  The source's data goes to the device once; nothing K x N or K x E touches the host.  conn: 2 x E
     zero based, default the image grid (construct_neighborhood); d_min / d_step: the rescaling of the positions and of
     the globalstereo unary.  carry=True: every level after the first starts from the previous level's messages, moved
-    onto its own offsets, not from zero.  -> PlaneBandResult."""
+    onto its own offsets, not from zero.  solver: "trws", or "scanline" -- every level one scanline
+    aggregation on its inputs (band.run_levels; no carry).  -> PlaneBandResult."""
+    check_solver(solver, carry)
     levels = check_levels(levels)
     source = _source(source)
     conn = T.construct_neighborhood(source.H, source.W) if conn is None else conn
     prob = PlaneBandProblem(source, planes, conn, alphas, d_min, d_step)
     out = PlaneBandResult()
-    run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, carry)
+    run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, carry, solver=solver)
     out.planes = out.plane_maps[-1]
     return out

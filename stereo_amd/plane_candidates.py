@@ -26,7 +26,7 @@ from . import candidates
 from . import plane_band
 from . import terms as T
 from ._lib import StereoHipError
-from .band import (_bad, _conn, _device_labels, _edges, _flat, _out, _raise_bad, _vec, _vp, bind_inputs, run_levels,
+from .band import (_bad, _conn, _device_labels, _edges, _flat, _out, _raise_bad, _vec, _vp, bind_inputs, check_solver, run_levels,
                    to_device_vector)
 from .candidates import _device_vectors_of_gather, _taps
 from .consistency import _map, _p, _stream
@@ -349,9 +349,9 @@ class PlaneCandidateProblem(PlaneBandProblem):
             maps.append(t)
         return torch.stack(maps).contiguous() if maps and level["taps"].shape[0] else None
 
-    def build(self, level, plan, tol, carry=None):
+    def build(self, level, plan=None, tol=0.0, carry=None):
         """The inputs of the plane-candidate level `level` (check_level's dict) around the current planes, bound to
-        `plan`.  carry must be None."""
+        `plan` (None: to nothing).  carry must be None."""
         if carry is not None:
             raise StereoHipError("plane candidates: a plane-candidate level does not take carried messages")
         self.offsets = level["offsets"]
@@ -375,7 +375,7 @@ class PlaneCandidateProblem(PlaneBandProblem):
 
 
 def refine_plane_candidates(source, planes, kernel, tol, levels, maxiter, max_relgap, alphas=None, conn=None, d_min=0.0,
-                            d_step=0.0):
+                            d_step=0.0, solver="trws"):
     """Refines the plane map `planes` (4 x N) level by level: for each plane-candidate level in `levels` --
     dict(offsets=, taps=, sources=), a source being 'base' (the current planes) or 4 x N planes -- the table is gathered
     around the current planes on the device, its problem built (stereo_plane_candidates_inputs_*_device), bound to a
@@ -383,12 +383,14 @@ def refine_plane_candidates(source, planes, kernel, tol, levels, maxiter, max_re
     and applied; the selected planes are the next level's.  The source's data goes to the device once; nothing K x N or
     K x E touches the host.  conn: 2 x E zero based, default the image grid; d_min / d_step: the rescaling of the
     positions and of the globalstereo unary.  Every level starts from zero messages.
+    solver: "trws", or "scanline" -- every level one scanline aggregation on its inputs (band.run_levels).
     -> plane_band.PlaneBandResult (`carried` all False)."""
+    check_solver(solver)
     levels = check_levels(levels)
     source = _source(source)
     conn = T.construct_neighborhood(source.H, source.W) if conn is None else conn
     prob = PlaneCandidateProblem(source, planes, conn, alphas, d_min, d_step)
     out = PlaneBandResult()
-    run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap)
+    run_levels(prob, levels, out, kernel, tol, maxiter, max_relgap, solver=solver)
     out.planes = out.plane_maps[-1]
     return out

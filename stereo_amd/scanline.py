@@ -131,9 +131,239 @@ def model_energy(unary, conn, alphas, positions, kernel, tol, labels):
     return float(unary[x, np.arange(N)].sum() + pair.sum())
 
 
+# ---------------------------------------------------------------- per-edge positions
+
+def edges_max_labels():
+    """The largest K of the per-edge form (stereo_scanline_edges_max_labels)."""
+    return int(_lib.lib().stereo_scanline_edges_max_labels())
+
+
+def _directions_edges(directions):
+    try:
+        d = np.array([[int(v) for v in pair] for pair in directions], dtype=np.int32).reshape(-1, 2)
+    except (TypeError, ValueError):
+        raise StereoHipError("scanline: directions must be a sequence of (dy, dx) pairs")
+    return np.ascontiguousarray(d.reshape(-1)), d.shape[0]
+
+
+def _counter(bad, dev, stream):
+    """band._bad; a counter made here is zeroed on torch's current stream, which has to be done before another
+    `stream` touches it."""
+    import torch
+    made = bad is None
+    bad = band._bad(bad, dev)
+    if made and stream is not None:
+        torch.cuda.current_stream().synchronize()
+    return bad
+
+
+def edge_table(conn, shape):
+    """stereo_scanline_edges_table on the host (no device needed): `conn` 2 x E zero based on the H x W grid `shape`
+    -> the 4 N int32 table the header documents.  An edge the grid does not have is refused, named."""
+    H, W = _shape(shape)
+    conn = band._conn(conn)
+    table = np.zeros(4 * max(H, 0) * max(W, 0), np.int32)
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_scanline_edges_table(_p(conn, C.c_uint32), C.c_int64(conn.shape[1]), C.c_int(H), C.c_int(W),
+                                                _p(table, C.c_int32), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return table
+
+
+def edge_table_device(d_conn, E, shape, table=None, bad=None, stream=None, check=True):
+    """stereo_scanline_edges_table_device: `d_conn` a flat int32 tensor of 2 E entries (as the level builders keep it).
+    check=True reads the count of invalid edges back (this waits for the stream) and raises; the host form names them.
+    -> (table: 4 N int32 tensor, bad)."""
+    import torch
+    H, W = _shape(shape)
+    N = max(H, 0) * max(W, 0)
+    d_conn = band._flat(d_conn, "conn", torch.int32, 2 * int(E))
+    table = torch.empty(4 * N, dtype=torch.int32, device=d_conn.device) if table is None else band._flat(table, "table", torch.int32, 4 * N)
+    bad = _counter(bad, d_conn.device, stream)
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_scanline_edges_table_device(band._vp(d_conn), C.c_int64(int(E)), C.c_int(H), C.c_int(W), band._vp(table),
+                                                       band._vp(bad), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    band._raise_bad(bad, check, "edge_table_device: %d edge(s) that the %d x %d grid does not have, or has already "
+                    "(scanline.edge_table names the first)", H, W)
+    return table, bad
+
+
+def aggregate_edges(unary, shape, conn, q, qprim, alphas, kernel, tol, directions=DIRECTIONS_4, want_volume=False):
+    """stereo_scanline_edges_aggregate: `unary` K x N (label fastest) of `shape` = (H, W) pixels, `conn` 2 x E zero
+    based, `q` / `qprim` K x E, `alphas` E weights, kernel 1 / 2 and `tol` the model's truncated term.
+    -> ScanlineResult on the host with dispmap None (`volume` only with want_volume)."""
+    H, W = _shape(shape)
+    unary = np.asarray(unary, dtype=np.float64)
+    N = max(H, 0) * max(W, 0)
+    if unary.ndim != 2 or unary.shape[1] != N:
+        raise StereoHipError("scanline: unary must be K x N = K x %d (got %s)" % (N, unary.shape))
+    K = unary.shape[0]
+    conn = band._conn(conn)
+    E = conn.shape[1]
+    q, qprim = np.asarray(q, dtype=np.float64), np.asarray(qprim, dtype=np.float64)
+    alphas = np.ascontiguousarray(np.asarray(alphas, dtype=np.float64).reshape(-1))
+    if q.shape != (K, E) or qprim.shape != (K, E) or alphas.shape[0] != E:
+        raise StereoHipError("scanline: q and qprim must be K x E = %d x %d and alphas E values" % (K, E))
+    unary, q, qprim = np.asfortranarray(unary), np.asfortranarray(q), np.asfortranarray(qprim)
+    d, R = _directions_edges(directions)
+    labels = np.zeros(max(N, 1), np.int32)
+    conf = np.zeros((max(H, 0), max(W, 0)), order="F")
+    volume = np.zeros((K, N), order="F") if want_volume and N > 0 else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_scanline_edges_aggregate(C.c_int(int(kernel)), _p(unary), C.c_int(H), C.c_int(W), C.c_int(K), C.c_int64(E),
+                                                    _p(conn, C.c_uint32), _p(q), _p(qprim), _p(alphas), C.c_double(float(tol)),
+                                                    _p(d, C.c_int32), C.c_int(R), _p(volume), _p(labels, C.c_int32), _p(conf), err,
+                                                    C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return ScanlineResult(labels[:N], None, conf, volume)
+
+
+def aggregate_edges_device(unary, shape, table, q, qprim, alphas, kernel, tol, directions=DIRECTIONS_4, volume=None, labels=None,
+                           confidence=None, stream=None):
+    """stereo_scanline_edges_aggregate_device on torch tensors of the current device, launched on `stream` (a torch
+    stream or a raw handle; default: torch's current stream) without waiting for it.  `unary`: flat float64, K * N;
+    `table`: edge_table_device's; `q`, `qprim`: flat, K * E; `alphas`: E (E is its length, K = unary's length / N).
+    `volume` (flat K * N: the workspace and the summed costs), `labels` (N int32) and `confidence` ((W, H)): tensors to
+    write into; made here otherwise.  -> ScanlineResult of tensors, dispmap None."""
+    import torch
+    H, W = _shape(shape)
+    N = max(H, 0) * max(W, 0)
+    unary = band._flat(unary, "unary", torch.float64)
+    if N < 1 or unary.numel() % N or unary.numel() < N:
+        raise StereoHipError("scanline: unary must hold K * N = K * %d elements (got %d)" % (N, unary.numel()))
+    K = unary.numel() // N
+    alphas = band._flat(alphas, "alphas", torch.float64)
+    E = alphas.numel()
+    table = band._flat(table, "table", torch.int32, 4 * N)
+    q, qprim = band._flat(q, "q", torch.float64, K * E), band._flat(qprim, "qprim", torch.float64, K * E)
+    d, R = _directions_edges(directions)
+    volume = band._out(volume, "volume", K * N, unary.device)
+    labels = torch.empty(N, dtype=torch.int32, device=unary.device) if labels is None else band._flat(labels, "labels", torch.int32, N)
+    confidence = torch.empty((W, H), dtype=torch.float64, device=unary.device) if confidence is None else _device_map(confidence, "confidence", np.float64, (W, H))
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_scanline_edges_aggregate_device(C.c_int(int(kernel)), band._vp(unary), C.c_int(H), C.c_int(W), C.c_int(K),
+                                                           C.c_int64(E), band._vp(table), band._vp(q), band._vp(qprim), band._vp(alphas),
+                                                           C.c_double(float(tol)), _p(d, C.c_int32), C.c_int(R), band._vp(volume),
+                                                           band._vp(labels), band._vp(confidence), C.c_void_p(_stream(stream)), err,
+                                                           C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return ScanlineResult(labels, None, confidence, volume)
+
+
+def model_energy_edges(unary, conn, q, qprim, alphas, kernel, tol, labels, want_terms=False):
+    """The energy of the labelling `labels` (N, ONE based) under the general model the header documents:
+    sum_i unary[labels_i, i] + sum_e alphas_e * min(v(|qprim[labels_a, e] - q[labels_b, e]|), tol) over the edges
+    e = (a, b) of `conn` (2 x E, zero based); `unary` K x N, `q` / `qprim` K x E.  NumPy on the host: the general-model
+    sibling of model_energy.  want_terms: -> (energy, the N + E terms, each with the definition's operations)."""
+    if int(kernel) not in (1, 2):
+        raise StereoHipError("model_energy_edges: kernel must be 1 or 2 (got %r)" % (kernel,))
+    unary = np.asarray(unary, dtype=np.float64)
+    conn = np.asarray(conn).astype(np.int64)
+    q, qprim = np.asarray(q, dtype=np.float64), np.asarray(qprim, dtype=np.float64)
+    x = np.asarray(labels).reshape(-1).astype(np.int64) - 1
+    if unary.ndim != 2 or conn.ndim != 2 or conn.shape[0] != 2:
+        raise StereoHipError("model_energy_edges: unary K x N, conn 2 x E, q and qprim K x E, E alphas and N labels")
+    K, N = unary.shape
+    E = conn.shape[1]
+    alphas = np.asarray(alphas, dtype=np.float64).reshape(-1)
+    if q.shape != (K, E) or qprim.shape != (K, E) or alphas.shape[0] != E or x.shape[0] != N:
+        raise StereoHipError("model_energy_edges: unary K x N, conn 2 x E, q and qprim K x E, E alphas and N labels")
+    if x.size and (x.min() < 0 or x.max() >= K):
+        raise StereoHipError("model_energy_edges: labels must be 1 .. %d" % K)
+    if conn.size and (conn.min() < 0 or conn.max() >= N):
+        raise StereoHipError("model_energy_edges: conn must be 0 .. %d" % (N - 1))
+    e = np.arange(E)
+    d = np.abs(qprim[x[conn[0]], e] - q[x[conn[1]], e])
+    with np.errstate(over="ignore"):
+        pair = alphas * np.minimum(d if int(kernel) == 1 else d * d, float(tol))
+    terms = np.concatenate([unary[x, np.arange(N)], pair])
+    energy = float(terms[:N].sum() + pair.sum())
+    return (energy, terms) if want_terms else energy
+
+
+def level_energy_device(unary, conn, q, qprim, alphas, kernel, tol, labels, terms=None, bad=None, stream=None, check=True):
+    """stereo_scanline_edges_energy_device: the N + E terms of the labelling `labels` (N int32 tensor, one based) under
+    the inputs of a level -- flat tensors `unary` K * N, `conn` 2 E int32, `q` / `qprim` K * E, `alphas` E -- written on
+    the device and summed on the host (this waits for the stream).  check=True raises for a label outside 1 .. K.
+    -> (energy, terms: N + E float64 tensor)."""
+    import torch
+    labels = band._flat(labels, "labels", torch.int32)
+    N = labels.numel()
+    unary = band._flat(unary, "unary", torch.float64)
+    if N < 1 or unary.numel() % N or unary.numel() < N:
+        raise StereoHipError("level_energy_device: unary must hold K * N = K * %d elements (got %d)" % (N, unary.numel()))
+    K = unary.numel() // N
+    conn, E = band._edges(conn)
+    alphas = band._flat(alphas, "alphas", torch.float64, E)
+    q, qprim = band._flat(q, "q", torch.float64, K * E), band._flat(qprim, "qprim", torch.float64, K * E)
+    terms = band._out(terms, "terms", N + E, unary.device)
+    bad = _counter(bad, unary.device, stream)
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_scanline_edges_energy_device(C.c_int(int(kernel)), band._vp(unary), C.c_int(K), C.c_int64(N), C.c_int64(E),
+                                                        band._vp(conn), band._vp(q), band._vp(qprim), band._vp(alphas),
+                                                        C.c_double(float(tol)), band._vp(labels), band._vp(terms), band._vp(bad),
+                                                        C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    if stream is not None:
+        stream.synchronize() if hasattr(stream, "synchronize") else torch.cuda.ExternalStream(int(stream)).synchronize()
+    host = terms.cpu().numpy()
+    band._raise_bad(bad, check, "level_energy_device: %d label(s) outside 1 .. %d", K)
+    return float(host[:N].sum() + host[N:].sum()), terms
+
+
+class ScanlineLevel:
+    """One level solved by scanline aggregation, with the three things the level loops read from a TrwsPlan:
+    result() -> (labels, energy, NaN, 0), path() -> 0.  `problem_table` keeps a problem's edge table."""
+
+    def __init__(self, labels, energy):
+        self.labels, self.energy = labels, energy
+
+    def result(self):
+        return self.labels, self.energy, float("nan"), 0
+
+    def path(self):
+        return 0
+
+
+def problem_shape(prob):
+    """(H, W) of a level problem (band / candidates keep H and W, the plane problems their source)."""
+    return (prob.H, prob.W) if hasattr(prob, "H") else (prob.source.H, prob.source.W)
+
+
+def problem_table(prob):
+    """The edge table of a level problem's `d_conn`, built once and kept on the problem.  A `conn` that is not the
+    image grid's is refused with the host table's message."""
+    if getattr(prob, "d_edge_table", None) is None:
+        shape = problem_shape(prob)
+        table, bad = edge_table_device(prob.d_conn, prob.E, shape, check=False)
+        if int(bad.item()):
+            edge_table(prob.conn, shape)        # (raises, naming the edge)
+            raise StereoHipError("scanline: the problem's conn is not a grid's")
+        prob.d_edge_table = table
+    return prob.d_edge_table
+
+
+def solve_level(prob, level, kernel, tol, zero_columns=None):
+    """One level of `prob` (the protocol of band.run_levels) solved by aggregation over DIRECTIONS_4 on torch's current
+    stream: build(plan=None), aggregate_edges_device on what it left, the level's model energy from the terms kernel.
+    -> ScanlineLevel (labels on the host, N int32 one based)."""
+    K = prob.labels_of(level)
+    if K > edges_max_labels():
+        raise StereoHipError("solver='scanline': a level of %d labels (at most %d)" % (K, edges_max_labels()))
+    table = problem_table(prob)
+    if zero_columns is None:
+        prob.build(level, None, tol)
+    else:
+        prob.build(level, None, tol, zero_columns=zero_columns)
+    r = aggregate_edges_device(prob.d_unary, problem_shape(prob), table, prob.d_q, prob.d_qprim, prob.d_alphas, kernel, tol)
+    energy, _ = level_energy_device(prob.d_unary, prob.d_conn, prob.d_q, prob.d_qprim, prob.d_alphas, kernel, tol, r.labels)
+    return ScanlineLevel(r.labels.cpu().numpy(), energy)
+
+
 def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, check_tol=1.0, directions=DIRECTIONS_8,
                             smooth_weight=1.0, candidate_levels=None, band_levels=None, maxiter=30, max_relgap=0.0,
-                            volumes=None):
+                            volumes=None, level_solver="trws"):
     """Both views of a rectified pair without a full-range solve.  In this order: the two NCC volumes
     (consistency.pair_volumes, or `volumes`); each view's unary_weight * (1 - ncc) aggregated on the device along
     `directions`, every direction weighing `smooth_weight`; the two maps checked against each other with check_tol and
@@ -141,7 +371,8 @@ def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, chec
     smooth_weight, lower_bound NaN, iterations 0 and path 0.  Then the optional candidate levels and the
     optional band levels around the scanline map, both views as a two-member TrwsBatch per level with up
     to `maxiter` iterations (consistency.run_band_levels, as solve_pair_ncc_pyramid runs them around an expanded map).
-    -> consistency.PairResult."""
+    level_solver="scanline": both kinds of level are solved by aggregation on their own inputs, not by TRW-S
+    (aggregate_edges_device).  -> consistency.PairResult."""
     import torch
     from . import candidates
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
@@ -158,6 +389,7 @@ def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, chec
         candidate_levels = candidates.check_levels(candidate_levels)
     if band_levels is not None:
         band_levels = band.check_levels(band_levels)
+    band.check_solver(level_solver)
     directions = [tuple(d) for d in directions]
     weights = [float(smooth_weight)] * len(directions)
     _lib.require_device()
@@ -201,11 +433,12 @@ def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, chec
             problems = [candidates.CandidateProblem(vol, disparities, unary_weight, view.dispmap, conn, alphas, layout=1)
                         for vol, view in zip(volumes, out.views)]
             consistency.run_band_levels(out, problems, candidate_levels, band_plans, kernel, conn, tol, maxiter, max_relgap,
-                                        check_tol, name="propagate")
+                                        check_tol, name="propagate", solver=level_solver)
         if band_levels:
             problems = [band.BandProblem(vol, disparities, unary_weight, view.dispmap, conn, alphas, layout=1)
                         for vol, view in zip(volumes, out.views)]
-            consistency.run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol)
+            consistency.run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
+                                        solver=level_solver)
     finally:
         for plan in (p for pair in band_plans.values() for p in pair):
             plan.close()
