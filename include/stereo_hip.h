@@ -40,8 +40,10 @@ extern "C" {
  * _inputs_globalstereo / _apply (plane candidates: per-pixel plane sets propagated from neighbours).
  * 19: stereo_pyramid_expand_planes / _device (a plane map carried to the next finer scale as planes),
  * stereo_planes_fit_local / _device (the per-pixel local plane fit).  20: stereo_scanline_aggregate / _device.
- * 21: stereo_scanline_edges_* (scanline aggregation on per-edge positions and weights). */
-#define STEREO_HIP_ABI_VERSION 21
+ * 21: stereo_scanline_edges_* (scanline aggregation on per-edge positions and weights).
+ * 22: stereo_contrast_edge_weights / stereo_contrast_step_weights (smoothness weights from an image),
+ * stereo_scanline_aggregate_weighted / _device (scanline aggregation with a weight per pixel and direction). */
+#define STEREO_HIP_ABI_VERSION 22
 
 /* ---- library ---------------------------------------------------------- */
 
@@ -1254,6 +1256,76 @@ int stereo_scanline_edges_energy_device(int kernel, const double *unary, int K, 
                                         const uint32_t *conn, const double *q, const double *qprim,
                                         const double *alphas, double tol, const int32_t *labels, double *terms,
                                         int32_t *bad, void *stream, char *err, size_t errcap);
+
+/* ---- image-guided smoothness: contrast weights and weighted scanlines ------------------ *
+ * No reference counterpart.  An image is H x W x C doubles, column major, as stereo_pyramid_reduce takes it: element
+ * (y, x, c) at y + H*(x + W*c), C >= 1, finite; N = H*W, pixel id p = y + H*x.
+ * Contrast of two pixels a, b:
+ *     g(a, b) = max_c |im(a, c) - im(b, c)|        (one subtraction per channel; the maximum of finite doubles does
+ *                                                   not depend on its order: g is symmetric and bit-defined)
+ * Ramp rho(g) with the parameters w_high >= 0, w_low >= 0, 0 <= g0 <= g1, all finite, tested in this order:
+ *     g <= g0             ->  w_high
+ *     otherwise g >= g1   ->  w_low
+ *     otherwise           ->  w_high + (w_low - w_high) * ((g - g0) / (g1 - g0))
+ * Every operation is rounded once, nothing is contracted, there is no exp: the same bits in any language (the
+ * expression order of tests/contrast_restate.py is the definition).  g0 == g1 is a step, a two-level rule like
+ * col_thresh; w_low > w_high is not refused.  rho is finite and >= 0.
+ *
+ * stereo_contrast_edge_weights: alphas[e] = rho(g(conn[2e], conn[2e+1])) for the E edges of `conn` (2 x E, zero
+ * based), any graph on the image's pixels.  One thread per edge.  The host form refuses an endpoint outside
+ * 0 .. N-1, naming the edge, and an image value that is not finite.  The device form takes `bad` (one int32 on the
+ * device, zeroed on the stream first, as in stereo_scanline_edges_table_device): an edge with an endpoint outside
+ * 0 .. N-1, or whose contrast is not finite, writes 0.0 and adds one to `bad`.
+ *
+ * stereo_contrast_step_weights: wstep, R x N doubles, element (r, p) at p + N*r, for the R directions (dy, dx) of
+ * `directions` (a HOST array in both forms; the 8 of stereo_scanline_aggregate, 1 <= R <= 8), one launch for all R:
+ *     wstep[r, p] = rho(g(p, p - r))     where the predecessor (y - dy, x - dx) is inside the image,
+ *     wstep[r, p] = 0.0                  where it is not.
+ * The host form refuses an image value that is not finite; in the device form the image must be finite.
+ * For an axis direction wstep[r, p] is the alphas of the grid edge between p and its predecessor, in either
+ * orientation: the aggregation below and a TRW-S plan uploaded with those alphas then speak about one energy.
+ *
+ * Refused with a message, before the device is looked for: H, W or C below 1; H*W >= 2^31; E < 0; NULL for a
+ * required array (conn may be NULL at E = 0); a parameter that is negative or not finite, or g0 > g1; R outside
+ * 1 .. 8 or a direction outside the 8; an output that is an input (alphas == im or conn, wstep == im). */
+typedef struct stereo_contrast_params {
+  double w_high, w_low, g0, g1;
+} stereo_contrast_params;
+int stereo_contrast_edge_weights(const double *im, int H, int W, int C, const uint32_t *conn, int64_t E,
+                                 const stereo_contrast_params *params, double *alphas, char *err, size_t errcap);
+int stereo_contrast_step_weights(const double *im, int H, int W, int C, const int32_t *directions, int R,
+                                 const stereo_contrast_params *params, double *wstep, char *err, size_t errcap);
+/* The same on device arrays of the caller (`im`, `conn`, `alphas`, `bad`, `wstep`), launched on `stream`
+ * (hipStream_t, NULL = default) without waiting for it. */
+int stereo_contrast_edge_weights_device(const double *im, int H, int W, int C, const uint32_t *conn, int64_t E,
+                                        const stereo_contrast_params *params, double *alphas, int32_t *bad,
+                                        void *stream, char *err, size_t errcap);
+int stereo_contrast_step_weights_device(const double *im, int H, int W, int C, const int32_t *directions, int R,
+                                        const stereo_contrast_params *params, double *wstep, void *stream, char *err,
+                                        size_t errcap);
+
+/* stereo_scanline_aggregate_weighted: stereo_scanline_aggregate with `step_weights` (R x N doubles, element (r, p) at
+ * p + N*r, finite and >= 0) in the place of the one weight per direction.  Everything else is that entry's, with
+ *     L_r(p, k) = U(p, k)                                                                    no predecessor,
+ *     L_r(p, k) = U(p, k) + min_l (L_r(p - r, l) + wstep[r, p] * min(v(|pos_k - pos_l|), tol))     otherwise
+ * (the product last, the minimum not subtracted): the step INTO p along direction r weighs wstep[r, p].  S, labels,
+ * map and confidence are defined as there.  An entry of `step_weights` at a pixel without a predecessor is not read.
+ * A step weight of exactly 0 is legal and gives L = U + min_l L(p - r, l).  With wstep[r, .] constant = w_r the
+ * results are stereo_scanline_aggregate's bits.
+ * Refused: stereo_scanline_aggregate's refusals (step_weights in the place of weights); S == step_weights; and in
+ * the host form an entry of `step_weights` that is read and is negative or not finite.  The device form promises for
+ * such values, as for other non-finite inputs, only labels in 1 .. D and no access outside its arrays. */
+int stereo_scanline_aggregate_weighted(const double *unary, int H, int W, int D, const double *positions, int kernel,
+                                       double tol, const int32_t *directions, const double *step_weights, int R,
+                                       double *S, int32_t *labels, double *map, double *confidence, char *err,
+                                       size_t errcap);
+/* On device arrays of the caller (`step_weights` too; `directions` stays a HOST array), as
+ * stereo_scanline_aggregate_device. */
+int stereo_scanline_aggregate_weighted_device(const double *unary, int H, int W, int D, const double *positions,
+                                              int kernel, double tol, const int32_t *directions,
+                                              const double *step_weights, int R, double *S, int32_t *labels,
+                                              double *map, double *confidence, void *stream, char *err,
+                                              size_t errcap);
 
 /* ---- device-resident fusion moves --------------------------------------- *
  * The state of one dispmap object kept in HBM across moves: connectivity, weights, points,

@@ -265,7 +265,7 @@ def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, m
 
 
 def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_relgap, check_tol=1.0, refine_iters=0,
-                   band_levels=None, smooth_weight=1.0, carry=False, volumes=None):
+                   band_levels=None, smooth_weight=None, carry=False, volumes=None, contrast=None):
     """Both views of a rectified pair: two NCC unary volumes, two TRW-S plans on the image grid with the shared
     positions `disparities`, iterated as one TrwsBatch; labels to maps; each map checked against the other and filled.
     refine_iters > 0: per view, the solver state is saved, the unary columns of the occluded pixels are zeroed and
@@ -275,7 +275,10 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
     the band problem around their map on the device, from their own volume, and run up to `maxiter` iterations as a
     two-member TrwsBatch; the refined maps are checked with check_tol and filled.  With refine_iters > 0 the unary
     columns of the pixels the preceding check found occluded are zeroed in the band as well.
-    smooth_weight: the weight of every edge (a pyramid level's model).
+    smooth_weight: the weight of every edge (default 1; DESIGN.md 6.4: a pyramid level's model).
+    contrast: a contrast.Contrast in the place of smooth_weight -- giving both is refused.  Each view's
+    edge weights are contrast.edge_weights of its own image on the image grid; the full-range plan, the occlusion-aware
+    re-solve and the band levels of a view are uploaded with them.
     carry=True: the first band level starts from the full-range solve's messages (its disparities are the old offsets,
     the old base is zero), every later one from the level before it; the result's `stages` keeps what
     the last pass leaves.  The full-range passes themselves are what they are without it.
@@ -306,15 +309,21 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
     unaries = pair_unaries(images, disparities, unary_weight, volumes)
     out.times["volumes"] = clock() - t0
     conn = T.construct_neighborhood(H, W)
-    alphas = np.ones(conn.shape[1]) * float(smooth_weight)
+    if contrast is not None and smooth_weight is not None:
+        raise StereoHipError("solve_pair_ncc: smooth_weight or contrast, not both")
+    if contrast is None:
+        alphas = [np.ones(conn.shape[1]) * (1.0 if smooth_weight is None else float(smooth_weight))] * 2     # per view
+    else:
+        from . import contrast as contrast_mod
+        alphas = [contrast_mod.edge_weights(im, conn, contrast) for im in images]
     plans = [TrwsPlan(int(kernel), K, N, conn) for _ in range(2)]
     band_plans = {}
     by_index = lambda i, labels: disparities[labels.astype(np.int64) - 1].reshape(W, H).T
 
     try:
         t0 = clock()
-        for plan, unary in zip(plans, unaries):
-            plan.upload(unary, alphas, tol, positions=disparities)
+        for plan, unary, a in zip(plans, unaries, alphas):
+            plan.upload(unary, a, tol, positions=disparities)
         with TrwsBatch(plans) as batch:
             batch.iterate(maxiter, max_relgap)
         out.times["solve"] = clock() - t0
@@ -323,9 +332,9 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
             view.carried.append(False)
         if refine_iters > 0:
             t0 = clock()
-            for plan, unary, view in zip(plans, unaries, out.views):
+            for plan, unary, view, a in zip(plans, unaries, out.views, alphas):
                 state = plan.save_state()
-                plan.upload(occlusion_aware_unary(unary, view.status), alphas, tol, positions=disparities)
+                plan.upload(occlusion_aware_unary(unary, view.status), a, tol, positions=disparities)
                 plan.load_state(state)
             with TrwsBatch(plans) as batch:   # a fresh batch: a member that max_relgap stopped takes part again
                 batch.iterate(refine_iters, max_relgap)
@@ -337,8 +346,8 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
             from . import carry as carry_mod
             out.stages = [carry_mod.full_range_stage(plan, disparities, conn, (H, W)) for plan in plans]
         if band_levels is not None:
-            problems = [band.BandProblem(vol, disparities, unary_weight, view.dispmap, conn, alphas, layout=1)
-                        for vol, view in zip(volumes, out.views)]
+            problems = [band.BandProblem(vol, disparities, unary_weight, view.dispmap, conn, a, layout=1)
+                        for vol, view, a in zip(volumes, out.views, alphas)]
             run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
                             zero_occluded=refine_iters > 0, carry=carry, stages=out.stages if carry else None)
     finally:

@@ -499,17 +499,36 @@ class dispmap_ncc(dispmap_super):
         """H x W x D: unary_weight * (1 - ncc), the unary of every fronto-parallel label, in the image's own columns."""
         return self._unary_weight * (1.0 - (self.ncc[:, ::-1] if self._mirrored else self.ncc))
 
-    def aggregate_scanlines(self, directions=None, weights=None):
+    def set_contrast(self, c):
+        """Image-guided smoothness (no reference counterpart): smooth_weights become
+        contrast.edge_weights(reference image, neighborhood, c) -- the object's own reference image, which for a mirrored
+        object is the flipped one its neighborhood indexes.  Everything that reads smooth_weights follows; the pyramids
+        refuse such an object as they refuse any smooth_weights other than 1."""
+        from . import contrast
+        self.smooth_weights = contrast.edge_weights(self.images[0], self.neighborhood, c)
+
+    def aggregate_scanlines(self, directions=None, weights=None, contrast=None):
         """Scanline aggregation of this object's unary volume (no reference counterpart) with its
         disparities, kernel and tolerance: scanline.aggregate on unary_volume(), in the image's own columns (so is a
         direction's dx), along `directions` (default scanline.DIRECTIONS_8) with one weight per direction (default 1).
+        contrast: a contrast.Contrast in the place of `weights` (both: refused) -- the weighted aggregation (DESIGN.md
+        6.12) with the step weights of the reference image in its own columns.
         Nothing is stored in the object.  -> scanline.ScanlineResult with the summed volume (D x N)."""
         from . import scanline
         vol = self.unary_volume()
         H, W, D = vol.shape
         unary = np.asfortranarray(vol.transpose(2, 1, 0).reshape(D, W * H))
-        return scanline.aggregate(unary, (H, W), self.disparities, self._kernel, self._tol,
-                                  scanline.DIRECTIONS_8 if directions is None else directions, weights, want_volume=True)
+        directions = scanline.DIRECTIONS_8 if directions is None else directions
+        if contrast is not None:
+            from . import contrast as contrast_mod
+            if weights is not None:
+                raise StereoHipError("aggregate_scanlines: weights or contrast, not both")
+            image = self.images[0][:, ::-1] if self._mirrored else self.images[0]
+            wstep = contrast_mod.step_weights(image, directions, contrast)
+            return scanline.aggregate_weighted(unary, (H, W), self.disparities, self._kernel, self._tol, wstep, directions,
+                                               want_volume=True)
+        return scanline.aggregate(unary, (H, W), self.disparities, self._kernel, self._tol, directions, weights,
+                                  want_volume=True)
 
     def refine_band(self, levels, maxiter=None, carry=False, solver="trws"):
         """Sub-pixel refinement of the current map (no reference counterpart): for every vector of offsets in

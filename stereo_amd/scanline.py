@@ -2,7 +2,8 @@
 min-sum dynamic programme of the model's own pairwise term along the scanlines of up to 8 directions, summed into a
 D x N volume, and the labels, map and confidence the sum gives; ``model_energy``, the energy of any labelling under the
 model TRW-S minimises; and ``solve_pair_ncc_scanline``, both views of a pair from the aggregation, cross-checked, with
-optional candidate and band levels around the scanline maps.
+optional candidate and band levels around the scanline maps.  ``aggregate_weighted`` takes a weight per
+pixel and direction in the place of one weight per direction; contrast.step_weights makes such weights from an image.
 
 A volume is D x N, label fastest (layout 1), N = H * W, pixel id = col * H + row.  A direction is (dy, dx): the
 predecessor of pixel (y, x) is (y - dy, x - dx).  Host forms take NumPy arrays; device forms take torch tensors of the
@@ -105,6 +106,64 @@ def aggregate_device(unary, shape, positions, kernel, tol, directions=DIRECTIONS
                                                      C.c_int(int(kernel)), C.c_double(float(tol)), _p(d, C.c_int32), _p(w),
                                                      C.c_int(w.shape[0]), band._vp(volume), band._vp(labels), band._vp(dispmap),
                                                      band._vp(confidence), C.c_void_p(_stream(stream)), err, C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return ScanlineResult(labels, dispmap, confidence, volume)
+
+
+def aggregate_weighted(unary, shape, positions, kernel, tol, step_weights, directions=DIRECTIONS_8, want_volume=False):
+    """stereo_scanline_aggregate_weighted: aggregate with `step_weights` (R x N, finite and >= 0: row r
+    holds per pixel the weight of the step into it along directions[r]; contrast.step_weights makes them from an
+    image) in the place of one weight per direction.  -> ScanlineResult on the host (`volume` only with want_volume)."""
+    H, W = _shape(shape)
+    unary = np.asarray(unary, dtype=np.float64)
+    positions = np.ascontiguousarray(np.asarray(positions, dtype=np.float64).reshape(-1))
+    D = positions.shape[0]
+    N = max(H, 0) * max(W, 0)
+    if unary.ndim != 2 or unary.shape != (D, N):
+        raise StereoHipError("scanline: unary must be D x N = %d x %d (got %s)" % (D, N, unary.shape))
+    unary = np.asfortranarray(unary)
+    d, R = _directions_edges(directions)
+    wstep = np.asarray(step_weights, dtype=np.float64)
+    if wstep.shape != (R, N):
+        raise StereoHipError("scanline: step_weights must be R x N = %d x %d (got %s)" % (R, N, wstep.shape))
+    wstep = np.ascontiguousarray(wstep)
+    labels = np.zeros(max(N, 1), np.int32)
+    dispmap, conf = np.zeros((max(H, 0), max(W, 0)), order="F"), np.zeros((max(H, 0), max(W, 0)), order="F")
+    volume = np.zeros((D, N), order="F") if want_volume and N > 0 else None
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_scanline_aggregate_weighted(_p(unary), C.c_int(H), C.c_int(W), C.c_int(D), _p(positions),
+                                                       C.c_int(int(kernel)), C.c_double(float(tol)), _p(d, C.c_int32), _p(wstep),
+                                                       C.c_int(R), _p(volume), _p(labels, C.c_int32), _p(dispmap), _p(conf), err,
+                                                       C.c_size_t(len(err)))
+    _lib.check(rc, err)
+    return ScanlineResult(labels[:N], dispmap, conf, volume)
+
+
+def aggregate_weighted_device(unary, shape, positions, kernel, tol, step_weights, directions=DIRECTIONS_8, volume=None,
+                              labels=None, dispmap=None, confidence=None, stream=None, d_positions=None):
+    """stereo_scanline_aggregate_weighted_device: aggregate_device with `step_weights`, a flat float64 tensor of R * N
+    elements (element (r, p) at p + N * r, as contrast.step_weights_device writes it), in the place of `weights`.
+    -> ScanlineResult of tensors."""
+    import torch
+    H, W = _shape(shape)
+    positions = np.ascontiguousarray(np.asarray(positions, dtype=np.float64).reshape(-1))
+    D = positions.shape[0]
+    N = max(H, 0) * max(W, 0)
+    unary = band._flat(unary, "unary", torch.float64, D * N)
+    d, R = _directions_edges(directions)
+    step_weights = band._flat(step_weights, "step_weights", torch.float64, R * N)
+    (d_positions,) = band._device_vectors(stream, (positions, d_positions, "d_positions"))
+    volume = band._out(volume, "volume", D * N, unary.device)
+    labels = torch.empty(N, dtype=torch.int32, device=unary.device) if labels is None else band._flat(labels, "labels", torch.int32, N)
+    dispmap = torch.empty((W, H), dtype=torch.float64, device=unary.device) if dispmap is None else _device_map(dispmap, "dispmap", np.float64, (W, H))
+    confidence = torch.empty((W, H), dtype=torch.float64, device=unary.device) if confidence is None else _device_map(confidence, "confidence", np.float64, (W, H))
+    err = _lib.errbuf()
+    rc = _lib.lib().stereo_scanline_aggregate_weighted_device(band._vp(unary), C.c_int(H), C.c_int(W), C.c_int(D),
+                                                              band._vp(d_positions), C.c_int(int(kernel)), C.c_double(float(tol)),
+                                                              _p(d, C.c_int32), band._vp(step_weights), C.c_int(R),
+                                                              band._vp(volume), band._vp(labels), band._vp(dispmap),
+                                                              band._vp(confidence), C.c_void_p(_stream(stream)), err,
+                                                              C.c_size_t(len(err)))
     _lib.check(rc, err)
     return ScanlineResult(labels, dispmap, confidence, volume)
 
@@ -362,19 +421,25 @@ def solve_level(prob, level, kernel, tol, zero_columns=None):
 
 
 def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, check_tol=1.0, directions=DIRECTIONS_8,
-                            smooth_weight=1.0, candidate_levels=None, band_levels=None, maxiter=30, max_relgap=0.0,
-                            volumes=None, level_solver="trws"):
+                            smooth_weight=None, candidate_levels=None, band_levels=None, maxiter=30, max_relgap=0.0,
+                            volumes=None, level_solver="trws", contrast=None):
     """Both views of a rectified pair without a full-range solve.  In this order: the two NCC volumes
     (consistency.pair_volumes, or `volumes`); each view's unary_weight * (1 - ncc) aggregated on the device along
-    `directions`, every direction weighing `smooth_weight`; the two maps checked against each other with check_tol and
-    filled.  That first pass has energy = model_energy of the scanline labels on the image grid with every edge weighing
+    `directions`, every direction weighing `smooth_weight` (default 1); the two maps checked against each other with
+    check_tol and filled.  That first pass has energy = model_energy of the scanline labels on the image grid with every edge weighing
     smooth_weight, lower_bound NaN, iterations 0 and path 0.  Then the optional candidate levels and the
     optional band levels around the scanline map, both views as a two-member TrwsBatch per level with up
     to `maxiter` iterations (consistency.run_band_levels, as solve_pair_ncc_pyramid runs them around an expanded map).
     level_solver="scanline": both kinds of level are solved by aggregation on their own inputs, not by TRW-S
-    (aggregate_edges_device).  -> consistency.PairResult."""
+    (aggregate_edges_device).
+    contrast: a contrast.Contrast in the place of smooth_weight -- giving both is refused.  Each view's
+    step weights (contrast.step_weights_device) and edge weights (contrast.edge_weights_device on the image grid) come
+    from that view's own image, in the columns its unary is in; the aggregation is aggregate_weighted_device, and
+    model_energy and the candidate and band levels, with either level_solver, get that view's edge weights as alphas.
+    -> consistency.PairResult."""
     import torch
     from . import candidates
+    from . import contrast as contrast_mod
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
     if len(images) != 2:
         raise StereoHipError("solve_pair_ncc_scanline: images must be the two views of a pair, left first (got %d)" % len(images))
@@ -391,7 +456,10 @@ def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, chec
         band_levels = band.check_levels(band_levels)
     band.check_solver(level_solver)
     directions = [tuple(d) for d in directions]
-    weights = [float(smooth_weight)] * len(directions)
+    if contrast is not None and smooth_weight is not None:
+        raise StereoHipError("solve_pair_ncc_scanline: smooth_weight or contrast, not both")
+    smooth_weight = 1.0 if smooth_weight is None else float(smooth_weight)
+    weights = [smooth_weight] * len(directions)
     _lib.require_device()
     out = consistency.PairResult()
     clock = time.perf_counter
@@ -405,20 +473,29 @@ def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, chec
     unaries = consistency.pair_unaries(images, disparities, unary_weight, volumes)
     out.times["volumes"] = clock() - t0
     conn = T.construct_neighborhood(H, W)
-    alphas = np.ones(conn.shape[1]) * float(smooth_weight)
+    alphas = [np.ones(conn.shape[1]) * smooth_weight] * 2          # per view
 
     t0 = clock()
     d_positions = band.to_device_vector(disparities)
-    for view, unary in zip(out.views, unaries):
+    if contrast is not None:
+        d_conn = torch.from_numpy(np.ascontiguousarray(conn.T.reshape(-1), dtype=np.int32)).cuda()
+        alphas = []
+    for image, view, unary in zip(images, out.views, unaries):
         d_unary = torch.from_numpy(np.asfortranarray(unary).reshape(-1, order="F")).cuda()
-        r = aggregate_device(d_unary, (H, W), disparities, kernel, tol, directions, weights, d_positions=d_positions)
+        if contrast is None:
+            r = aggregate_device(d_unary, (H, W), disparities, kernel, tol, directions, weights, d_positions=d_positions)
+        else:
+            d_image = contrast_mod.image_to_device(image)
+            alphas.append(contrast_mod.edge_weights_device(d_image, np.shape(image), d_conn, contrast)[0].cpu().numpy())
+            wstep = contrast_mod.step_weights_device(d_image, np.shape(image), directions, contrast)
+            r = aggregate_weighted_device(d_unary, (H, W), disparities, kernel, tol, wstep, directions, d_positions=d_positions)
         view.labels = r.labels.cpu().numpy()
         view.dispmap = r.dispmap.cpu().numpy().T
         view.maps.append(view.dispmap)
     out.times["scanline"] = clock() - t0
     t0 = clock()
-    for view, unary in zip(out.views, unaries):
-        view.energy.append(model_energy(unary, conn, alphas, disparities, kernel, tol, view.labels))
+    for view, unary, a in zip(out.views, unaries, alphas):
+        view.energy.append(model_energy(unary, conn, a, disparities, kernel, tol, view.labels))
         view.lower_bound.append(float("nan")); view.iterations.append(0); view.paths.append(0); view.carried.append(False)
     out.times["energy"] = clock() - t0
     t0 = clock()
@@ -430,13 +507,13 @@ def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, chec
     band_plans = {}
     try:
         if candidate_levels:
-            problems = [candidates.CandidateProblem(vol, disparities, unary_weight, view.dispmap, conn, alphas, layout=1)
-                        for vol, view in zip(volumes, out.views)]
+            problems = [candidates.CandidateProblem(vol, disparities, unary_weight, view.dispmap, conn, a, layout=1)
+                        for vol, view, a in zip(volumes, out.views, alphas)]
             consistency.run_band_levels(out, problems, candidate_levels, band_plans, kernel, conn, tol, maxiter, max_relgap,
                                         check_tol, name="propagate", solver=level_solver)
         if band_levels:
-            problems = [band.BandProblem(vol, disparities, unary_weight, view.dispmap, conn, alphas, layout=1)
-                        for vol, view in zip(volumes, out.views)]
+            problems = [band.BandProblem(vol, disparities, unary_weight, view.dispmap, conn, a, layout=1)
+                        for vol, view, a in zip(volumes, out.views, alphas)]
             consistency.run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
                                         solver=level_solver)
     finally:
