@@ -42,7 +42,10 @@ extern "C" {
  * stereo_planes_fit_local / _device (the per-pixel local plane fit).  20: stereo_scanline_aggregate / _device.
  * 21: stereo_scanline_edges_* (scanline aggregation on per-edge positions and weights).
  * 22: stereo_contrast_edge_weights / stereo_contrast_step_weights (smoothness weights from an image),
- * stereo_scanline_aggregate_weighted / _device (scanline aggregation with a weight per pixel and direction). */
+ * stereo_scanline_aggregate_weighted / _device (scanline aggregation with a weight per pixel and direction).
+ * Still 22: stereo_map_filter_max_radius / stereo_map_weighted_median / _device (map filter) -- three added symbols and
+ * no changed signature; tests/test_scanline_weighted_cpu.py pins 22, and the binding that needs them
+ * (stereo_amd/mapfilter.py) refuses a library without them by name. */
 #define STEREO_HIP_ABI_VERSION 22
 
 /* ---- library ---------------------------------------------------------- */
@@ -1326,6 +1329,49 @@ int stereo_scanline_aggregate_weighted_device(const double *unary, int H, int W,
                                               const double *step_weights, int R, double *S, int32_t *labels,
                                               double *map, double *confidence, void *stream, char *err,
                                               size_t errcap);
+
+/* ---- map filter: image-guided weighted median of a disparity map ------------------------ *
+ * No reference counterpart.  d: H x W doubles, column major, (y, x) at y + H*x, pixel id p = y + H*x, N = H*W < 2^31.
+ * radius r, 1 <= r <= stereo_map_filter_max_radius() (4).  Optional: `im`, H x W x C finite doubles as in the section
+ * above, with `params` (both or neither); `pixel_weight`, N doubles, finite and >= 0; `targets`, N int32, a pixel is
+ * a target where its entry is not 0 (NULL: every pixel is).
+ *
+ * Taps of p = (y, x): the window positions (y + dy, x + dx), dx = -r .. r outer, dy = -r .. r inner: TAP ORDER.
+ * A tap q is valid if it lies inside the image and d(q) is finite.  Its weight is
+ *     w_q = rho(g(p, q)) * pixel_weight(q)            (g and rho as above; without im the first factor is 1.0 and not
+ *                                                      multiplied, without pixel_weight there is no second factor;
+ *                                                      with both ONE product, rounded once; the centre is a tap)
+ * At a target p, with every sum formed by rounded additions in tap order, starting from 0.0:
+ *     total   = sum of w_q over the valid taps
+ *     W_le(v) = sum of (d(q) <= v ? w_q : 0.0) over the valid taps
+ *     total > 0 false:  out(p) = d(p) (its bits), source(p) = p, and the pixel is counted in `kept`;
+ *     otherwise:        v* = the smallest d(q) among the valid taps with 2 * W_le(d(q)) >= total,
+ *                       source(p) = the id of the first tap in tap order that is valid, has w_q > 0 and d(q) == v*,
+ *                       out(p) = d(source(p)) (that tap's bits: it says which zero where -0.0 == +0.0 tie).
+ * Rounded addition is monotone, so W_le is monotone in v and the largest value qualifies (its sum is total's own): v* is
+ * the lower weighted median; it is the value of a positive-weight tap (the sum rose at v*), and it does not depend on the
+ * order in which candidates are examined.  At a pixel that is not a target out(p) = d(p), bit for bit whatever it is, and
+ * source(p) = p.  `kept` (one int32) = the number of targets with total > 0 false.
+ * A 4 x N plane map is filtered by taking, per pixel, the plane of source(p).
+ *
+ * One launch: a kernel per radius and per guided / weighted combination, one thread per pixel, a workgroup's tile of d
+ * (and, a channel at a time, of im, then of pixel_weight) with its r-wide halo in LDS; (2r+1)^4 compare-select-add steps
+ * per target.  `source` may be NULL in both forms.  The device form zeroes `kept` on the stream first; the image and
+ * pixel_weight must there be finite (and >= 0): for other values it promises only no access outside its arrays.
+ * Refused with a message, before the device is looked for: H or W below 1; H*W >= 2^31; a radius outside the range;
+ * NULL d, out or kept; im without params or params without im; C < 1 with an image; the ramp's parameter rule above;
+ * out, source or kept equal to an input or to each other; and in the host form an image value that is not finite or
+ * a pixel weight that is negative or not finite, naming the first. */
+int stereo_map_filter_max_radius(void);
+int stereo_map_weighted_median(const double *d, int H, int W, int radius, const double *im, int C,
+                               const stereo_contrast_params *params, const double *pixel_weight,
+                               const int32_t *targets, double *out, int32_t *source, int32_t *kept, char *err,
+                               size_t errcap);
+/* The same on device arrays of the caller, launched on `stream` (hipStream_t, NULL = default) without waiting. */
+int stereo_map_weighted_median_device(const double *d, int H, int W, int radius, const double *im, int C,
+                                      const stereo_contrast_params *params, const double *pixel_weight,
+                                      const int32_t *targets, double *out, int32_t *source, int32_t *kept,
+                                      void *stream, char *err, size_t errcap);
 
 /* ---- device-resident fusion moves --------------------------------------- *
  * The state of one dispmap object kept in HBM across moves: connectivity, weights, points,

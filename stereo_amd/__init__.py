@@ -28,6 +28,8 @@ from . import scanline  # noqa: F401
 from .scanline import solve_pair_ncc_scanline  # noqa: F401
 from . import contrast  # noqa: F401
 from .contrast import Contrast  # noqa: F401
+from . import mapfilter  # noqa: F401
+from .mapfilter import MedianFilter  # noqa: F401
 
 __all__ = ["contrast", "Contrast", "scanline", "solve_pair_ncc_scanline", "plane_candidates", "plane_candidates_inputs", "plane_candidates_apply", "plane_candidates_inputs_device", "plane_candidates_apply_device", "refine_plane_candidates", "PlaneCandidateProblem", "candidates", "candidates_inputs", "candidates_apply", "candidates_inputs_device", "candidates_apply_device", "refine_candidates", "CandidateProblem","trws", "rd", "dispmap_super", "dispmap_ncc", "dispmap_globalstereo", "TrwsPlan", "TrwsState", "PlaneProposal", "vgg_segment_ms", "vgg_segment_gb", "lr_check", "lr_fill", "lr_check_device", "lr_fill_device", "solve_pair_ncc", "solve_pair_ncc_pyramid", "solve_view_ncc_plane_pyramid", "band_inputs", "band_apply", "band_inputs_device", "band_apply_device", "refine_band", "carry_messages", "carry_messages_device", "scale_edge_map", "plane_band_inputs", "plane_band_apply", "plane_band_inputs_device", "plane_band_apply_device", "refine_plane_band", "NccSource", "GlobalstereoSource", "PlaneBandProblem", "StereoHipError", "device_count", "LIB_PATH"]
 

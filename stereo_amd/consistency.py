@@ -173,11 +173,14 @@ class ViewResult:
     `residual`, `filled` and `source` those of the last level's refined map; `maps` keeps the map of every pass and
     `paths` the kernel family that ran it (TrwsPlan.path()).  A pyramid level that starts from an expanded map
      keeps that map and the expansion's candidate numbers as `expanded` and `expand_source`.  `carried`
-    has one entry per pass: the pass started from the previous stage's messages."""
+    has one entry per pass: the pass started from the previous stage's messages.  With post_filter=
+    (DESIGN.md 6.13) `filtered` and `filter_source` are the filter's output on `filled` and its source pixel ids (H x W);
+    None otherwise."""
 
     def __init__(self):
         self.labels = self.dispmap = self.status = self.residual = self.filled = self.source = None
         self.expanded = self.expand_source = None
+        self.filtered = self.filter_source = None       # post_filter= (DESIGN.md 6.13): the filter on `filled`
         self.energy, self.lower_bound, self.iterations, self.maps, self.paths, self.carried = [], [], [], [], [], []
 
 
@@ -195,9 +198,26 @@ class PairResult:
         return self.left, self.right
 
 
-def collect_views(out, plans, to_map, check_tol, stage):
+def filter_views(out, post_filter, images):
+    """post_filter (a mapfilter.MedianFilter, or None: nothing is done) on each view's `filled` map with the view's
+    status and, where the filter has a contrast, the view's own image (`images`: the pair, left first) -> view.filtered,
+    view.filter_source.  Nothing else of the view is touched: later stages start from the unfiltered maps."""
+    if post_filter is None:
+        return
+    from . import mapfilter
+    if not isinstance(post_filter, mapfilter.MedianFilter):
+        raise StereoHipError("post_filter: a mapfilter.MedianFilter is needed (got %r)" % (post_filter,))
+    if post_filter.contrast is not None and images is None:
+        raise StereoHipError("post_filter: a filter with a contrast needs the pair's images")
+    for i, view in enumerate(out.views):
+        view.filtered, view.filter_source, _ = post_filter.apply(view.filled, view.status,
+                                                                 None if images is None else images[i])
+
+
+def collect_views(out, plans, to_map, check_tol, stage, post_filter=None, images=None):
     """One pass of a pair solve into `out` (PairResult): per view the plan's labels, energy, bound, iterations and
-    kernel family, the map `to_map(view index, labels)`; then each map checked against the other and filled."""
+    kernel family, the map `to_map(view index, labels)`; then each map checked against the other and filled; with
+    post_filter the filled maps filtered (filter_views; `images`: the pair, the guides)."""
     t = time.perf_counter()
     for i, (plan, view) in enumerate(zip(plans, out.views)):
         view.labels, en, lb, it = plan.result()
@@ -208,11 +228,13 @@ def collect_views(out, plans, to_map, check_tol, stage):
     for view, other, direction in ((out.left, out.right, 1), (out.right, out.left, -1)):
         view.status, view.residual = lr_check(view.dispmap, other.dispmap, direction, check_tol)
         view.filled, view.source = lr_fill(view.dispmap, view.status)
+    filter_views(out, post_filter, images)
     out.times[stage] = time.perf_counter() - t
 
 
 def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
-                    zero_occluded=False, carry=False, stages=None, scales=False, name="band", solver="trws"):
+                    zero_occluded=False, carry=False, stages=None, scales=False, name="band", solver="trws", post_filter=None,
+                    images=None):
     """The band passes of a pair solve: for every vector of offsets both views (`problems`: one band.BandProblem each,
     standing around the view's current map) build their band problem on the device and run up to `maxiter` iterations
     as a two-member TrwsBatch; the labels are applied, the refined maps checked with `check_tol` and filled
@@ -227,7 +249,8 @@ def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, m
     view the Stage of the last level (with carry).
     solver="scanline" (DESIGN.md 6.11): no plan is made and band_plans stays as it is; each view's level is aggregated in
     turn on the current stream (scanline.solve_level) and collected as a plan's result is: the labels' model energy,
-    bound NaN, iterations 0, path 0.  carry and stages are refused."""
+    bound NaN, iterations 0, path 0.  carry and stages are refused.
+    post_filter, images: passed to every level's collect_views."""
     import torch
     from . import band
     if band.check_solver(solver, carry, stages) == "scanline":
@@ -241,7 +264,7 @@ def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, m
                 view.carried.append(False)
             out.times["%s_%d" % (name, level + 1)] = time.perf_counter() - t0
             collect_views(out, solved, lambda i, labels: problems[i].apply(labels), check_tol,
-                          "%s_%d_check_fill" % (name, level + 1))
+                          "%s_%d_check_fill" % (name, level + 1), post_filter, images)
         return
     N = problems[0].N
     previous = [prob.carry_from(st, scales) for prob, st in zip(problems, stages)] if stages is not None else [None, None]
@@ -260,12 +283,12 @@ def run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, m
             out.stages = [prob.leave(plan) for prob, plan in zip(problems, band_plans[Kb])]
         out.times["%s_%d" % (name, level + 1)] = time.perf_counter() - t0
         collect_views(out, band_plans[Kb], lambda i, labels: problems[i].apply(labels), check_tol,
-                      "%s_%d_check_fill" % (name, level + 1))
+                      "%s_%d_check_fill" % (name, level + 1), post_filter, images)
         previous = [prob.carry_from(st) for prob, st in zip(problems, out.stages)] if carry else [None, None]
 
 
 def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_relgap, check_tol=1.0, refine_iters=0,
-                   band_levels=None, smooth_weight=None, carry=False, volumes=None, contrast=None):
+                   band_levels=None, smooth_weight=None, carry=False, volumes=None, contrast=None, post_filter=None):
     """Both views of a rectified pair: two NCC unary volumes, two TRW-S plans on the image grid with the shared
     positions `disparities`, iterated as one TrwsBatch; labels to maps; each map checked against the other and filled.
     refine_iters > 0: per view, the solver state is saved, the unary columns of the occluded pixels are zeroed and
@@ -283,7 +306,10 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
     the old base is zero), every later one from the level before it; the result's `stages` keeps what
     the last pass leaves.  The full-range passes themselves are what they are without it.
     volumes: the two D x N NCC volumes (left, right) to take in place of pair_volumes(images, disparities) -- a pyramid
-    level's block volumes."""
+    level's block volumes.
+    post_filter: a mapfilter.MedianFilter.  After every check and fill of the solve, band levels
+    included, each view's `filled` map is filtered, guided by the view's own image where the filter has a contrast,
+    into `filtered` / `filter_source`.  Every other field, and what later passes start from, is what it is without."""
     disparities = np.asarray(disparities, dtype=np.float64).reshape(-1)
     if len(images) != 2:
         raise StereoHipError("solve_pair_ncc: images must be the two views of a pair, left first (got %d)" % len(images))
@@ -327,7 +353,7 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
         with TrwsBatch(plans) as batch:
             batch.iterate(maxiter, max_relgap)
         out.times["solve"] = clock() - t0
-        collect_views(out, plans, by_index, check_tol, "check_fill")
+        collect_views(out, plans, by_index, check_tol, "check_fill", post_filter, images)
         for view in out.views:
             view.carried.append(False)
         if refine_iters > 0:
@@ -339,7 +365,7 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
             with TrwsBatch(plans) as batch:   # a fresh batch: a member that max_relgap stopped takes part again
                 batch.iterate(refine_iters, max_relgap)
             out.times["refine"] = clock() - t0
-            collect_views(out, plans, by_index, check_tol, "refine_check_fill")
+            collect_views(out, plans, by_index, check_tol, "refine_check_fill", post_filter, images)
             for view in out.views:
                 view.carried.append(False)
         if carry:
@@ -349,7 +375,8 @@ def solve_pair_ncc(images, disparities, kernel, unary_weight, tol, maxiter, max_
             problems = [band.BandProblem(vol, disparities, unary_weight, view.dispmap, conn, a, layout=1)
                         for vol, view, a in zip(volumes, out.views, alphas)]
             run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
-                            zero_occluded=refine_iters > 0, carry=carry, stages=out.stages if carry else None)
+                            zero_occluded=refine_iters > 0, carry=carry, stages=out.stages if carry else None,
+                            post_filter=post_filter, images=images)
     finally:
         for plan in plans + [p for pair in band_plans.values() for p in pair]:
             plan.close()

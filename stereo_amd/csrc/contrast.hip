@@ -9,12 +9,15 @@
 #include <string>
 
 #include "common.h"
+#include "contrast_rule.h"
 #include "stereo_hip.h"
 
 namespace {
 
+using stereo::contrast;
 using stereo::fail;
 using stereo::guarded;
+using stereo::ramp;
 
 constexpr int kBlock = 256;
 constexpr int kMaxDirections = 8;
@@ -22,23 +25,6 @@ constexpr int kMaxDirections = 8;
 struct Directions {
   int dy[kMaxDirections], dx[kMaxDirections];
 };
-
-// g(a, b); `ok` is cleared when a channel's difference is not finite
-__device__ __forceinline__ double contrast(const double *__restrict__ im, int64_t N, int C, int64_t a, int64_t b, bool &ok) {
-  double g = 0.0;
-  for (int c = 0; c < C; ++c) {
-    const double d = fabs(im[a + N * c] - im[b + N * c]);
-    ok = ok && isfinite(d);
-    g = fmax(g, d);
-  }
-  return g;
-}
-
-__device__ __forceinline__ double ramp(double g, const stereo_contrast_params &p) {
-  if (g <= p.g0) return p.w_high;
-  if (g >= p.g1) return p.w_low;
-  return p.w_high + (p.w_low - p.w_high) * ((g - p.g0) / (p.g1 - p.g0));
-}
 
 __global__ void __launch_bounds__(kBlock)
     contrast_edge_kernel(const double *__restrict__ im, int64_t N, int C, const uint32_t *__restrict__ conn, int64_t E,
@@ -84,11 +70,7 @@ int check_image(const std::string &w, const void *im, int H, int W, int C, const
   if ((int64_t)H * (int64_t)W >= ((int64_t)1 << 31))
     return fail(w + ": H * W must be below 2^31 (pixel ids are int32)", err, errcap);
   if (!im || !p) return fail(w + ": im and params must not be NULL", err, errcap);
-  const double v[4] = {p->w_high, p->w_low, p->g0, p->g1};
-  for (double x : v)
-    if (!(x >= 0.0) || !std::isfinite(x))
-      return fail(w + ": w_high, w_low, g0 and g1 must be finite and non-negative", err, errcap);
-  if (p->g0 > p->g1) return fail(w + ": g0 must not be above g1", err, errcap);
+  if (const char *wrong = stereo::contrast_params_error(*p); *wrong) return fail(w + ": " + wrong, err, errcap);
   return 0;
 }
 

@@ -354,6 +354,24 @@ class dispmap_super:
         self.filled_dispmap, self.filled_source = consistency.lr_fill(d, self.consistency) if fill else (None, None)
         return self.consistency, self.filled_dispmap
 
+    def filter_map(self, post_filter):
+        """The map filter (no reference counterpart) on the map a preceding cross_check(fill=True) left:
+        post_filter (a mapfilter.MedianFilter) on self.filled_dispmap with self.consistency and, where the filter has a
+        contrast, the object's reference image -- for a mirrored object the flipped one it holds, un-flipped to the
+        columns current_dispmap() and the filled map speak in.  Sets self.filtered_dispmap and self.filtered_source (pixel
+        ids in those columns) and returns the map."""
+        from . import mapfilter
+        if not getattr(self, "_row_shift_views", False):
+            raise StereoHipError("filter_map: %s reaches its second view through a projection, not a row shift; the "
+                                 "left-right check it follows is defined for dispmap_ncc" % type(self).__name__)
+        if not isinstance(post_filter, mapfilter.MedianFilter):
+            raise StereoHipError("filter_map: a mapfilter.MedianFilter is needed (got %r)" % (post_filter,))
+        if getattr(self, "filled_dispmap", None) is None:
+            raise StereoHipError("filter_map: there is no filled map; call cross_check(other, fill=True) first")
+        self.filtered_dispmap, self.filtered_source, _ = post_filter.apply(self.filled_dispmap, self.consistency,
+                                                                           self._unflip(self.images[0]))
+        return self.filtered_dispmap
+
     def refine_band(self, levels, maxiter=None, carry=False, solver="trws"):
         raise StereoHipError("refine_band: %s does not take its unary from the NCC sampler; band refinement is defined "
                              "for dispmap_ncc" % type(self).__name__)

@@ -422,7 +422,7 @@ def solve_level(prob, level, kernel, tol, zero_columns=None):
 
 def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, check_tol=1.0, directions=DIRECTIONS_8,
                             smooth_weight=None, candidate_levels=None, band_levels=None, maxiter=30, max_relgap=0.0,
-                            volumes=None, level_solver="trws", contrast=None):
+                            volumes=None, level_solver="trws", contrast=None, post_filter=None):
     """Both views of a rectified pair without a full-range solve.  In this order: the two NCC volumes
     (consistency.pair_volumes, or `volumes`); each view's unary_weight * (1 - ncc) aggregated on the device along
     `directions`, every direction weighing `smooth_weight` (default 1); the two maps checked against each other with
@@ -436,6 +436,8 @@ def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, chec
     step weights (contrast.step_weights_device) and edge weights (contrast.edge_weights_device on the image grid) come
     from that view's own image, in the columns its unary is in; the aggregation is aggregate_weighted_device, and
     model_energy and the candidate and band levels, with either level_solver, get that view's edge weights as alphas.
+    post_filter: a mapfilter.MedianFilter: after every check and fill, candidate and band levels
+    included, each view's `filled` map filtered into `filtered` / `filter_source`, as in consistency.solve_pair_ncc.
     -> consistency.PairResult."""
     import torch
     from . import candidates
@@ -502,6 +504,7 @@ def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, chec
     for view, other, direction in ((out.left, out.right, 1), (out.right, out.left, -1)):
         view.status, view.residual = consistency.lr_check(view.dispmap, other.dispmap, direction, check_tol)
         view.filled, view.source = consistency.lr_fill(view.dispmap, view.status)
+    consistency.filter_views(out, post_filter, images)
     out.times["check_fill"] = clock() - t0
 
     band_plans = {}
@@ -510,12 +513,12 @@ def solve_pair_ncc_scanline(images, disparities, kernel, unary_weight, tol, chec
             problems = [candidates.CandidateProblem(vol, disparities, unary_weight, view.dispmap, conn, a, layout=1)
                         for vol, view, a in zip(volumes, out.views, alphas)]
             consistency.run_band_levels(out, problems, candidate_levels, band_plans, kernel, conn, tol, maxiter, max_relgap,
-                                        check_tol, name="propagate", solver=level_solver)
+                                        check_tol, name="propagate", solver=level_solver, post_filter=post_filter, images=images)
         if band_levels:
             problems = [band.BandProblem(vol, disparities, unary_weight, view.dispmap, conn, a, layout=1)
                         for vol, view, a in zip(volumes, out.views, alphas)]
             consistency.run_band_levels(out, problems, band_levels, band_plans, kernel, conn, tol, maxiter, max_relgap, check_tol,
-                                        solver=level_solver)
+                                        solver=level_solver, post_filter=post_filter, images=images)
     finally:
         for plan in (p for pair in band_plans.values() for p in pair):
             plan.close()
